@@ -29,6 +29,9 @@ Extra objects on the line:
                       bytes 4(n+1) + 4 nnz (+4 nnz weighted) + 8 n W per launch / HIP-event duration
   cpu_baseline        the dense CPU oracle (the reference's algorithm incl. densification; oracle/dense_ref.py)
                       timed on the host cores, rank 0, N=1 only, on a bounded sample of the same workload
+  dump_outputs        with ``--dump-outputs DIR`` only: where the outputs of the headline leg's last timed step were written
+                      (inputs and initial weights are seeded: the same arguments give the same inputs in every run, so two builds
+                      can be compared output for output)
 """
 import argparse
 import json
@@ -82,7 +85,32 @@ def parse():
                    help="experiment: Python's cyclic garbage collector off during the timed steps (gc.disable() after a gc.collect()): does "
                         "the idle gap at the forward -> backward turn of some traced steps come from a collection pause?")
     p.add_argument('--plain-adam', action='store_true', help='torch.optim.Adam without fused=True (one kernel per parameter group)')
+    p.add_argument('--dump-outputs', metavar='DIR',
+                   help="after the timed steps, write what the headline leg's last timed step computed (rank 0) as DIR/<name>.npy, float32: "
+                        "logits, loss, grad.<parameter> and param.<parameter> (after the optimiser's update); at most 64 MB in all, larger "
+                        "arrays are cut to a fixed seeded sample of their flattened elements")
     return p.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(path, arrays):
+    """``arrays`` {name: float32 ndarray} -> path/<name>.npy.  If they hold more than DUMP_LIMIT_BYTES together, every array above an
+    equal share is replaced by the sorted sample of its flattened elements that numpy's RandomState(0) picks: the same positions for
+    the same shapes, so that two builds' dumps compare element for element.  Returns a summary for the JSON line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // 4 // max(len(arrays), 1)
+    cut = sum(a.size for a in arrays.values()) * 4 > DUMP_LIMIT_BYTES
+    sampled, total = [], 0
+    for name, a in sorted(arrays.items()):
+        if cut and a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, share, replace=False))]
+            sampled.append(name)
+        np.save(os.path.join(path, name + '.npy'), a)
+        total += a.nbytes
+    return {'dir': path, 'arrays': len(arrays), 'bytes': total, 'sampled': sampled}
 
 
 def source_hash():
@@ -281,16 +309,27 @@ def main():
     torch.autograd.set_multithreading_enabled(False)     # backward on the calling thread: no engine-thread hand-off per node
 
     def step(b):
-        _, loss = dp(b)
+        logits, loss = dp(b)
         if loss.dim():                  # train.py:179 torch.mean(cls_loss): one loss per replica there, a scalar per process here
             loss = torch.mean(loss)
         opt.zero_grad()
         loss.backward()
         opt.step()
-        return loss
+        return logits, loss
 
-    def run_leg(leg, with_kernel_timing):
-        """W untimed + exactly K timed steps, bracketed by barrier + synchronize; returns the leg's measurements."""
+    def step_outputs(logits, loss):
+        """Host float32 copies of what the caller of a step receives from it: logits and loss, and in the model every parameter's
+        gradient and updated value."""
+        outs = {'logits': logits, 'loss': loss}
+        for k, p in model.named_parameters():
+            if p.grad is not None:
+                outs['grad.' + k] = p.grad
+            outs['param.' + k] = p
+        return {k: v.detach().float().cpu().numpy() for k, v in outs.items()}
+
+    def run_leg(leg, with_kernel_timing, dump=False):
+        """W untimed + exactly K timed steps, bracketed by barrier + synchronize; returns the leg's measurements (with ``dump``: and
+        the outputs of its last timed step)."""
         lists_, cpu_, dev_ = make_batches(leg)
         model.gemm_mode = 1 if leg == 'split' else 2 if leg == 'half' else args.gemm_mode      # (cgc_gemm_f32_ws's mode; the headline leg is exact unless asked otherwise)
         for i in range(args.warmup):
@@ -313,7 +352,7 @@ def main():
             timer_.start()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            loss_ = step(dev_[i % len(dev_)])
+            logits_, loss_ = step(dev_[i % len(dev_)])
         torch.cuda.synchronize()
         own = time.perf_counter() - t0          # this rank's own clock: before it waits for the others
         if world > 1:
@@ -326,6 +365,8 @@ def main():
             import gc
             gc.enable()
         res = dict(leg=leg, lists=lists_, cpu_batches=cpu_, timer=timer_, loss=loss_)
+        if dump and rank == 0:
+            res['outputs'] = step_outputs(logits_, loss_)      # now: the next leg trains the same model on
         if world > 1:
             ar = dp.allreduce_ms()
             t = torch.tensor([el, own, -own, (sum(ar) / len(ar)) if ar else 0.0], device=dev, dtype=torch.float64)
@@ -341,7 +382,8 @@ def main():
             raise SystemExit('non-finite loss')
         return res
 
-    results = [run_leg(leg, (not args.no_kernel_timing) and (i == 0 or leg in ('split', 'half'))) for i, leg in enumerate(legs)]
+    results = [run_leg(leg, (not args.no_kernel_timing) and (i == 0 or leg in ('split', 'half')), dump=i == 0 and args.dump_outputs is not None)
+               for i, leg in enumerate(legs)]
     model.gemm_mode = args.gemm_mode
     head = results[0]
     strong = head['leg'] == 'strong'
@@ -511,6 +553,8 @@ def main():
                             out[obj]['mfma_busy_stale'] = True
         if world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args, cpu_batches)
+        if args.dump_outputs is not None:
+            out['dump_outputs'] = write_outputs(args.dump_outputs, head['outputs'])
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

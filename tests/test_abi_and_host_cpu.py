@@ -108,18 +108,25 @@ def test_partition_by_cumulative_node_count():
 
 
 def test_oracle_matches_golden():
-    """The oracle itself against the reference-generated vectors (the pin)."""
+    """The oracle itself against the reference-generated vectors (the pin).  The algorithm is pinned in float64, where the
+    evaluation order of the host does not matter: logits, loss and every gradient to 1e-9 of the reference's float64 fixture.  The
+    fp32 evaluation depends on the host's summation order (intra-op thread count, BLAS code path): on the fixtures' own host and
+    thread count it reproduces them to < 1e-5; on other hosts and thread counts logits differ by up to 1.04e-5 and gradients by up
+    to 7.4e-4 (medium_plain: readout maxima fp32 cannot decide, tests/discrete.py) -- held to the output tolerance of the parity
+    tests, 1e-4, and to that decision-noise magnitude, 1e-3."""
+    import discrete
     from util import CASES, rel_err
     for name in CASES:
+        discrete.check_machinery_against_reference_fp64(name)
         cfg, batch, sd, out, grad, sd3 = load_case(name)
         m = build_model(dense_ref.SoftPoolingGcnEncoder, cfg)
         m.load_state_dict(sd)
         m.train()
         logits, loss = m(batch)
         loss.backward()
-        assert rel_err(logits, out['logits']) < 1e-5 and rel_err(loss, out['loss']) < 1e-5
+        assert rel_err(logits, out['logits']) < 1e-4 and rel_err(loss, out['loss']) < 1e-4
         for k, p in m.named_parameters():
-            assert rel_err(p.grad, grad[k]) < 1e-5, (name, k)
+            assert rel_err(p.grad, grad[k]) < 1e-3, (name, k)
 
 
 def test_device_collate_front_end_matches_host_collate(torch_kernels):

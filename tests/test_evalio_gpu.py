@@ -214,6 +214,39 @@ def test_bench_single_leg_flags():
     assert rec['scaling'] == 'weak' and rec['config']['global_batch'] == 8 and 'strong_value' not in rec and 'weak_value' not in rec
 
 
+def test_bench_dump_outputs_are_the_same_run_after_run(tmp_path):
+    """``--dump-outputs DIR`` writes the last timed step's logits, loss, every parameter's gradient and its value after the update as
+    float32 .npy files, within 64 MB; inputs and initial weights are seeded and the step is bitwise reproducible
+    (test_training_step_is_deterministic), so two runs with the same arguments write the same arrays.  ``--steps`` is the number of
+    timed steps the line reports and divides by."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    recs = []
+    for run in ('a', 'b'):
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '4', '--nodes', '300',
+               '--maxn', '600', '--no-cpu-baseline', '--no-split-leg', '--pool', '2', '--dump-outputs', str(tmp_path / run)]
+        out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+    for rec in recs:
+        assert rec['steps'] == 3 and rec['ms_per_step'] > 0 and abs(rec['value'] - 4 * 3 / (rec['ms_per_step'] * 3e-3)) < 0.05 * rec['value']
+    names = sorted(os.listdir(str(tmp_path / 'a')))
+    assert names == sorted(os.listdir(str(tmp_path / 'b')))
+    params = [n[len('param.'):] for n in names if n.startswith('param.')]
+    assert params and sorted('grad.' + n for n in params) == [n for n in names if n.startswith('grad.')]
+    assert 'logits.npy' in names and 'loss.npy' in names and len(names) == 2 + 2 * len(params)
+    arrays = {n: (np.load(str(tmp_path / 'a' / n)), np.load(str(tmp_path / 'b' / n))) for n in names}
+    assert arrays['logits.npy'][0].shape == (4, 3) and arrays['loss.npy'][0].shape == ()
+    assert np.isfinite(arrays['loss.npy'][0]) and not recs[0]['dump_outputs']['sampled']
+    assert sum(a.nbytes for a, _ in arrays.values()) == recs[0]['dump_outputs']['bytes'] <= 64 << 20
+    for n, (a, b) in arrays.items():
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+
 def test_one_epoch_example_runs_the_reference_training_loop():
     """BASELINE.json configs[0]/[1] plumbing: examples/train_synthetic.py = the reference's loop (train.py:174-184: model(data) ->
     torch.mean(cls_loss) -> zero_grad / backward / step, StepLR, evaluate) over 200 synthetic graphs of ~300 nodes, shipped flags
