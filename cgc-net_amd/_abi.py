@@ -3,7 +3,7 @@ import ctypes as C
 
 P, I, F, D, L = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_int64
 
-ABI_VERSION = 5      # = CGC_ABI_VERSION of include/cgc_hip.h these prototypes were written against (tests compare the two)
+ABI_VERSION = 6      # = CGC_ABI_VERSION of include/cgc_hip.h these prototypes were written against (tests compare the two)
 
 PROTOTYPES = {
     'cgc_abi_version': [],
@@ -75,6 +75,8 @@ PROTOTYPES = {
     'cgc_head_fwd': [P, I, I, I, I, I, I, P, P, P, P, P, F, C.c_uint64, P, P, P, P],
     'cgc_head_bwd': [P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P],
     'cgc_adam_step': [P, P, I, P, D, D, D, D, D, F, F, P],
+    'cgc_sgd_step': [P, P, I, P, D, D, D, D, F, P],
+    'cgc_rmsprop_step': [P, P, I, P, D, D, D, D, D, F, P],
     'cgc_timing_create': [I],
     'cgc_timing_attach': [P],
     'cgc_timing_count': [P],

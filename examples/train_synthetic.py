@@ -22,6 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import cgc_net_amd  # noqa: E402,F401
 from cgc_net_amd import network  # noqa: E402
 from cgc_net_amd.data import DataListLoader, SyntheticCellGraphs  # noqa: E402
+from cgc_net_amd.optim import init_optim  # noqa: E402
 from cgc_net_amd.parallel import DataParallel  # noqa: E402
 
 
@@ -46,6 +47,8 @@ def main():
     ap.add_argument('--batch-size', type=int, default=4)           # parallel_train.sh:2
     ap.add_argument('--epochs', type=int, default=1)
     ap.add_argument('--plain', action='store_true', help='without --jk --norm_adj --drop 0.2')
+    ap.add_argument('--optim', choices=['adam', 'sgd', 'rmsprop'], default=None,
+                    help="the reference's --optim through cgc_net_amd.optim.init_optim (one-launch update); default: torch.optim.Adam")
     args = ap.parse_args()
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -66,7 +69,10 @@ def main():
     model = network.SoftPoolingGcnEncoder(args.max_num_nodes, 16, 20, 20, True, True, 20, 3, 0.1, [50], concat=True,
                                           gcn_name='SAGE', load_data_sparse=True, **flags)
     model = DataParallel(model.to(device))
-    optimizer = torch.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-4)
+    if args.optim is None:
+        optimizer = torch.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-4)
+    else:                                      # train.py:142 init_optim(args.optim, ...), given the module for the one-launch path
+        optimizer = init_optim(args.optim, model.parameters(), 1e-3, 1e-4, model=model.module)
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=10, gamma=0.1)
 
     for epoch in range(args.epochs):

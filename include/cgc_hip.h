@@ -45,8 +45,9 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *   4: round 6 (removed: cgc_adj_prep_fwd2, cgc_adj_grad_operands, cgc_zero_diag and cgc_level_desc.flags bit 0 -- the thin-operand
  *      adjacency gradient; a descriptor with bit 0 set is refused.  Added: cgc_graph_build_local, cgc_graph_local_max_nodes)
  *   5: round 6 (mode CGC_GEMM_SPLIT_F16 of cgc_gemm_f32_ws / cgc_gemm_f32_cat_ws; cgc_level_desc.flags bit 2; cgc_gemm_half_count, cgc_gemm_half_ws_floats, cgc_gemm_half_min_work;
- *      cgc_gemm_ws_floats() grew by the mode's scale slots: workspaces sized by an older library are too small for the tail split) */
-#define CGC_ABI_VERSION 5
+ *      cgc_gemm_ws_floats() grew by the mode's scale slots: workspaces sized by an older library are too small for the tail split)
+ *   6: added cgc_sgd_step, cgc_rmsprop_step (one-launch SGD and RMSprop on the tables of cgc_adam_step) */
+#define CGC_ABI_VERSION 6
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -497,6 +498,20 @@ typedef struct {
 } cgc_adam_seg;
 int cgc_adam_step(const void* segs, const void* blocks, int nblocks, const float* const* grad_buffers, double lr, double beta1,
                   double beta2, double weight_decay, double eps, float step, float grad_mul, cgc_stream_t stream);
+
+/* ==== The reference's other optimisers (common/utils.py:122-127: torch.optim.SGD / RMSprop, momentum 0.9) as ONE launch each, on the
+ * same two tables as cgc_adam_step (no second layout; cgc_opt_seg is another name for the row).  What the two state columns hold:
+ *   SGD:     m = momentum_buffer (NULL when momentum is 0), v unused (NULL)
+ *   RMSprop: m = square_avg, v = momentum_buffer (NULL when momentum is 0)
+ * SGD: weight decay, buf = momentum * buf + (1 - dampening) * g, p -= lr * buf -- torch._fused_sgd_'s arithmetic (double scalars,
+ * float state).  RMSprop (not centred): torch.optim.RMSprop(foreach=True)'s sequence of float kernels.  grad_mul scales the
+ * gradients first.  nblocks <= 0: nothing to do, 0.  NULL tables or negative momentum: CGC_EINVAL, nothing launched.  A segment
+ * whose rule needs a state pointer that is NULL is left untouched. */
+typedef cgc_adam_seg cgc_opt_seg;
+int cgc_sgd_step(const void* segs, const void* blocks, int nblocks, const float* const* grad_buffers, double lr, double momentum,
+                 double dampening, double weight_decay, float grad_mul, cgc_stream_t stream);
+int cgc_rmsprop_step(const void* segs, const void* blocks, int nblocks, const float* const* grad_buffers, double lr, double alpha,
+                     double eps, double weight_decay, double momentum, float grad_mul, cgc_stream_t stream);
 
 /* ==== Measurement hook (csrc/timing.hip): HIP events around every launch of the dominant 128 x 128 GEMM (tag 1) and of the wide
  * SpMM (tag 2), recorded on the stream of the launch, whoever asked for it (per-operator call or step sequencer).  One observer
