@@ -137,9 +137,7 @@ template <> struct Vec<4> {
 // rows of more than 1024 floats (16-byte lanes, 5+ chunks per lane: the cluster-count-wide tensors) are read as streams
 template <int VEC, int MAXJ>
 __device__ __forceinline__ void load_wide(Vec<VEC>& x, const float* p) {
-#ifndef CGC_NO_STREAM_LOADS      // (-DCGC_NO_STREAM_LOADS: plain loads, for A/B timing through tools/variant_lib.sh)
   if constexpr (VEC == 4 && MAXJ >= 5) x.load_stream(p);
   else
-#endif
     x.load(p);
 }

@@ -71,9 +71,8 @@ struct KContigLoader {
     }
   }
   static __device__ __forceinline__ unsigned tile_soffset(int /*ld*/, int k0) { return (unsigned)k0 * 4u; }   // bytes from the operand base
-  template <int AUX = 0>
   __device__ __forceinline__ void load_buf_part(int i, __amdgpu_buffer_rsrc_t rsrc, const unsigned (&off)[PER_T], unsigned soff) {
-    reg[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i], soff, AUX));
+    reg[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i], soff, 0));
   }
   // Partial k-tile (k_lim % 4 == 0), still branch-free: units past the end of K re-read the last valid 16 bytes of their
   // row and are zeroed with a select -- the guarded loader above costs ~0.75 of a full tile's time on top of its own.
@@ -155,9 +154,8 @@ struct MnContigLoader {
     }
   }
   static __device__ __forceinline__ unsigned tile_soffset(int ld, int k0) { return (unsigned)k0 * (unsigned)ld * 4u; }
-  template <int AUX = 0>
   __device__ __forceinline__ void load_buf_part(int i, __amdgpu_buffer_rsrc_t rsrc, const unsigned (&off)[PER_T], unsigned soff) {
-    reg[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i], soff, AUX));
+    reg[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i], soff, 0));
   }
   // Partial k-tile: rows (k) past the end re-read row k_lim-1 and are zeroed.
   __device__ __forceinline__ void load_fast_masked(const float* __restrict__ base, int ld, int col0, int col_last4, int k0, int k_lim) {
@@ -196,16 +194,8 @@ __device__ __forceinline__ void fetch_frag(const float* __restrict__ tile, int k
 
 // FAST: every operand segment qualifies for the unguarded 16-byte loaders (decided on the host, gemm_all_fast): the kernel then
 // contains no guarded loader and no conditional inside a k-loop phase.  !FAST: the guarded element-wise loaders throughout.
-// cache policy of the pinned operand loads (buffer-load aux bits; 2 = nt: streaming) -- -DCGC_GEMM_A_AUX / _B_AUX for A/B timing
-#ifndef CGC_GEMM_A_AUX
-#define CGC_GEMM_A_AUX 0
-#endif
-#ifndef CGC_GEMM_B_AUX
-#define CGC_GEMM_B_AUX 0
-#endif
 template <int WGM, int WGN, int TM, int TN, bool TA, bool TB, bool FAST>
 __global__ __launch_bounds__(256, 2) void k_gemm_f32(const GemmArgs a) {   // 2 waves per SIMD = 2 workgroups per CU (the LDS budget)
-  GT_MARK(0)
   constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
   constexpr int LDA_S = TA ? BM + 4 : KC_LD;   // TA: A stored [K,M] -> k-major tile; else row-major [m][k]
   constexpr int LDB_S = TB ? KC_LD : BN + 4;   // TB: B stored [N,K] -> row-major [n][k]; else k-major
@@ -237,10 +227,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f32(const GemmArgs a) {   // 2 
   if (m0 >= M) return;
   const int N = a.N;
 
-#ifdef CGC_GEMM_TRACE
-  if (TM == 2 && TN == 2 && threadIdx.x == 0 && blockIdx.x < 65536)
-    g_gemm_trace[blockIdx.x][5] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | __builtin_amdgcn_s_getreg((31 << 11) | 4);
-#endif
   const bool vecA = (a.lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(A) & 15u) == 0);
   const bool vecB = (a.ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(B) & 15u) == 0);
 
@@ -335,7 +321,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f32(const GemmArgs a) {   // 2 
   // (measured: the FAST kernel is 1-2 % faster on the step's big products -- the guarded tail was NOT what the K = 40 segment of
   // the assignment Linear paid for; that was round quantisation, see the tail split.  A variant with no conditional inside any
   // phase (separate STORE / LAST flavours, parity-alternating epilogue loop) compiled to 256 VGPRs + 500-800 spilled registers.)
-#ifndef CGC_GEMM_NOPIN      // (-DCGC_GEMM_NOPIN: the compiler's own order with flat-address loads, for A/B timing)
   unsigned offA[LoaderA::PER_T], offB[LoaderB::PER_T];
   __amdgpu_buffer_rsrc_t rsrcA, rsrcB;
   if constexpr (FAST) {
@@ -345,23 +330,17 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f32(const GemmArgs a) {   // 2 
     rsrcA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, 0xffffffff, 0x00020000);
     rsrcB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(B), 0, 0xffffffff, 0x00020000);
   }
-#endif
   auto phase = [&](auto mode_c, int kt, auto cur_c, LoaderA& ls_a, LoaderB& ls_b, LoaderA& ll_a, LoaderB& ll_b) {
     constexpr int MODE = decltype(mode_c)::value;
     constexpr int cur = decltype(cur_c)::value;
     bool has_next = true;
     if constexpr (MODE == PH_FULL) {
-#ifndef CGC_X_NOLOAD          // (CGC_X_*: timing experiments that break the result -- tools/variant_lib.sh; never defined in the build)
-#ifndef CGC_GEMM_NOPIN
       if constexpr (FAST) {     // (issued inside the k groups below)
         static_assert(LoaderA::PER_T <= BK / 8 && LoaderB::PER_T <= BK / 8, "one load per operand and k group");
-      } else
-#endif
-      {
+      } else {
         ll_a.load_fast(A, a.lda, m0, a_last, (kt + 2) * BK);
         ll_b.load_fast(B, a.ldb, n0, b_last, (kt + 2) * BK);
       }
-#endif
     } else if constexpr (MODE == PH_MASK) {
       if (kt + 2 < kend) fetch_seg(ll_a, ll_b, seg, kt + 2, m0, a_last, n0, b_last);
       has_next = kt + 1 < kend;
@@ -388,17 +367,12 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f32(const GemmArgs a) {   // 2 
     for (int j = 0; j < TN; ++j) fetch_frag<!TB, LDB_S>(bs + (TB ? j * 32 * KC_LD : j * 32), 0, l31, lhi, bv[0][j]);
 #pragma unroll
     for (int kb = 0; kb < BK / 8; ++kb) {
-#ifdef CGC_X_NOREAD
-      if (MODE != PH_FULL && kb + 1 < BK / 8) {
-#else
       if (kb + 1 < BK / 8) {
-#endif
 #pragma unroll
         for (int i = 0; i < TM; ++i) fetch_frag<TA, LDA_S>(as + (TA ? i * 32 : i * 32 * KC_LD), kb + 1, l31, lhi, av[(kb + 1) & 1][i]);
 #pragma unroll
         for (int j = 0; j < TN; ++j) fetch_frag<!TB, LDB_S>(bs + (TB ? j * 32 * KC_LD : j * 32), kb + 1, l31, lhi, bv[(kb + 1) & 1][j]);
       }
-#ifndef CGC_GEMM_NOPIN
       if constexpr (MODE == PH_FULL && FAST) {
         // pinned interleave (FULL phases): the k group's 16 MFMAs in four runs of TM*TN, and behind each run ONE kind of other work --
         // the next group's fragment reads (issued above, in front of the first run), this group's share of the LDS writes of tile
@@ -417,14 +391,13 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f32(const GemmArgs a) {   // 2 
             if (kb < LoaderB::PER_T) ls_b.store_part(kb, bn);
           }
           if (t == 2) {
-            if (kb < LoaderA::PER_T) ll_a.template load_buf_part<CGC_GEMM_A_AUX>(kb, rsrcA, offA, LoaderA::tile_soffset(a.lda, (kt + 2) * BK));
-            if (kb < LoaderB::PER_T) ll_b.template load_buf_part<CGC_GEMM_B_AUX>(kb, rsrcB, offB, LoaderB::tile_soffset(a.ldb, (kt + 2) * BK));
+            if (kb < LoaderA::PER_T) ll_a.load_buf_part(kb, rsrcA, offA, LoaderA::tile_soffset(a.lda, (kt + 2) * BK));
+            if (kb < LoaderB::PER_T) ll_b.load_buf_part(kb, rsrcB, offB, LoaderB::tile_soffset(a.ldb, (kt + 2) * BK));
           }
           __builtin_amdgcn_sched_barrier(0);
         }
         continue;
       }
-#endif
       if (MODE == PH_FULL || kb < nkb) {
 #pragma unroll
       for (int t = 0; t < 4; ++t)
@@ -434,20 +407,12 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f32(const GemmArgs a) {   // 2 
           for (int j = 0; j < TN; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[kb & 1][j][t], av[kb & 1][i][t], acc[i][j], 0, 0, 0);   // C^T tile: see gemm_epilogue
       }
-#ifdef CGC_X_NOWRITE
-      if (MODE != PH_FULL && has_next) {
-#else
       if (has_next) {
-#endif
         if (kb < LoaderA::PER_T) ls_a.store_part(kb, an);
         if (kb < LoaderB::PER_T) ls_b.store_part(kb, bn);
       }
     }
-#ifdef CGC_X_NOBAR
-    if (MODE != PH_FULL) __syncthreads();
-#else
     __syncthreads();
-#endif
   };
   typedef std::integral_constant<int, PH_FULL> FULL_;
   typedef std::integral_constant<int, PH_MASK> MASK_;
@@ -463,7 +428,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f32(const GemmArgs a) {   // 2 
       if (kbeg + 1 < kend) fetch_seg(la0, lb0, seg, kbeg + 1, m0, a_last, n0, b_last);
     }
     __syncthreads();
-    GT_MARK(1)
     int kt = kbeg;
     const int fast_end = nk_full < kend ? nk_full : kend;
     for (; kt + 3 < fast_end; kt += 2) {     // both phases prefetch full tiles of the main pair (kt+2, kt+3 < nk_full)
@@ -497,7 +461,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f32(const GemmArgs a) {   // 2 
     }
   }
 
-  GT_MARK(2)
   if (S > 1) {
     // piece of a tail tile: the raw accumulators go to this piece's slab (k_gemm_fixup adds the S slabs of the tile and applies
     // alpha / beta / bias).  Slab order = register order, 16 bytes per lane: every store instruction writes 1 KiB contiguous.
@@ -515,7 +478,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f32(const GemmArgs a) {   // 2 
   // epilogue (the last phase ended with a barrier: nobody reads operand tiles any more, the LDS is free for the parking strips)
   static_assert(4 * 32 * (TN * 32 + 4) <= 2 * A_SZ + 2 * B_SZ, "epilogue parking region exceeds the operand LDS");
   gemm_epilogue<TM, TN>(a, C, M, N, m0 + wm * TM * 32, n0 + wn * TN * 32, acc, lds + wave * 32 * (TN * 32 + 4), lane);
-  GT_MARK(3)
 }
 
 template <int WGM, int WGN, int TM, int TN, bool TA, bool TB>
@@ -655,47 +617,19 @@ template <int WGM, int WGN, int TM, int TN>
 static int launch_cfg(const GemmArgs& a0, int transA, int transB, int batch, int m_extent, int k_extent, bool short_k, float* ws,
                       int64_t ws_floats, hipStream_t stream) {
   constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
-  GemmArgs a = a0;
-  a.tiles_n = ceil_div(a.N, BN);
-  static const int map_mode = getenv("CGC_GEMM_MAP") ? atoi(getenv("CGC_GEMM_MAP")) : 3;
-  a.map_mode = map_mode;
-  const long long per_batch = (long long)ceil_div(m_extent, BM) * a.tiles_n;
-  const long long tiles = per_batch * batch;
-  if (per_batch <= 0 || tiles > 0x7ffffff0LL) return CGC_EINVAL;
-  a.per_batch = (int)per_batch;
-  a.nb = batch;
-  a.ws = nullptr;
-  a.resident = 0;
-  a.s_max = 1;
+  GemmPlan<WGM, WGN, TM, TN> plan;
+  if (!plan.init(a0, batch, m_extent, k_extent, BK)) return CGC_EINVAL;
   if (transA && transB) return CGC_EINVAL;
-  // tail split: pipelined kernel only, long reductions only (a piece keeps >= 3 k-tiles), slabs must fit the workspace
-  static const int split_on = getenv("CGC_GEMM_SPLIT") ? atoi(getenv("CGC_GEMM_SPLIT")) : 1;
-  int extra = 0;
-  // the smaller tile shapes hold more workgroups per CU than the 512 the split is sized for: they only split when the launch is
-  // clearly under-filled (the thin level-2 products of a 4-graph shard: 72 workgroups walking 36 k-tiles each = 36 us of pure
-  // latency; as 504 pieces of 5 k-tiles + fix-up: 14 us)
-  static const int small_max = getenv("CGC_GEMM_SMALL_SPLIT") ? atoi(getenv("CGC_GEMM_SMALL_SPLIT")) : 384;
+  // tail split: pipelined kernel only, long reductions only (a piece keeps >= 3 k-tiles).  The smaller tile shapes hold more
+  // workgroups per CU than the 512 the split is sized for: they only split when the launch is clearly under-filled (the thin
+  // level-2 products of a 4-graph shard: 72 workgroups walking 36 k-tiles each = 36 us of pure latency; as 504 pieces of 5 k-tiles
+  // + fix-up: 14 us)
   const bool big = BM == 128 && BN == 128;
-  if (!short_k && ws != nullptr && split_on && (big || split_on >= 2 || tiles <= small_max)) {
-    long long kt = ceil_div(k_extent, BK);
-    for (int i = 0; i < a.nx; ++i) kt += ceil_div(a.xK[i], BK);
-    const int s_max = (int)(kt / 3 < 12 ? kt / 3 : 12);
-    const long long max_pieces = kResident + kResident / 2;            // L * S <= 1.5 R by construction (TileMap::init)
-    if (s_max >= 2 && max_pieces * BM * BN <= ws_floats) {
-      a.ws = ws;
-      a.resident = kResident;
-      a.s_max = s_max;
-      extra = (int)max_pieces;
-    }
-  }
-  dim3 grid((unsigned)(tiles + extra)), block(256);
-  int xk = 0;
-  for (int i = 0; i < a.nx; ++i) xk += a.xK[i];
-  const int trec = (BM == 128 && BN == 128 && !short_k)
-                       ? cgc_timing_begin(CGC_TAG_GEMM_128, a.M, a.N, a.K, batch, a.ragged, a.ragged ? (a.ragged == 1 ? m_extent : k_extent) : 0, xk, stream)
-                       : -1;
-  static const int fast_on = getenv("CGC_GEMM_FAST") ? atoi(getenv("CGC_GEMM_FAST")) : 1;   // CGC_GEMM_FAST=0: A-B timing against the guarded kernel
-  const bool fast = fast_on && gemm_all_fast(a, transA, transB, batch, m_extent, k_extent);
+  if (!short_k && ws != nullptr && (big || plan.tiles <= 384)) plan.tail_split(ws, ws_floats, 3, kResident);
+  if (big && !short_k) plan.timing_begin(m_extent, k_extent, stream);
+  const GemmArgs& a = plan.a;
+  const dim3 grid = plan.grid(), block(256);
+  const bool fast = gemm_all_fast(a, transA, transB, batch, m_extent, k_extent);
   if (short_k) {
     if (!transA && !transB) hipLaunchKernelGGL((k_gemm_f32_shortk<WGM, WGN, TM, TN, false, false>), grid, block, 0, stream, a);
     else if (!transA) hipLaunchKernelGGL((k_gemm_f32_shortk<WGM, WGN, TM, TN, false, true>), grid, block, 0, stream, a);
@@ -710,18 +644,11 @@ static int launch_cfg(const GemmArgs& a0, int transA, int transB, int batch, int
     else hipLaunchKernelGGL((k_gemm_f32<WGM, WGN, TM, TN, true, false, false>), grid, block, 0, stream, a);
   }
   CGC_RETURN_IF_LAUNCH_FAILED();
-  if (a.ws != nullptr) {
-    // at most min(T, R - 1) tail tiles; which ones (if any) is decided on the device exactly as in the kernel above
-    const long long lmax = tiles < kResident ? tiles : kResident - 1;
-    hipLaunchKernelGGL((k_gemm_fixup<WGM, WGN, TM, TN>), dim3((unsigned)(lmax * 4 * TM * TN)), dim3(64), 0, stream, a);
-    CGC_RETURN_IF_LAUNCH_FAILED();
-  }
-  cgc_timing_end(trec, stream);
-  return 0;
+  return plan.finish(stream);
 }
 
 // tuning hook (tools/gemm_cfg_sweep.py): 0 = automatic tile selection (default)
-static int g_force_cfg = getenv("CGC_GEMM_CFG") ? atoi(getenv("CGC_GEMM_CFG")) : 0;
+static int g_force_cfg = 0;
 extern "C" int cgc_gemm_tuning(int cfg) {
   const int old = g_force_cfg;
   g_force_cfg = cfg;
@@ -737,12 +664,8 @@ static int gemm_dispatch(GemmArgs& a, int transA, int transB, int batch, int max
                          hipStream_t stream) {
   const int M = a.M, N = a.N, K = a.K, ragged = a.ragged;
   if (batch <= 0 || N <= 0) return 0;
-#ifdef CGC_GEMM_ONLY_128   // compile-time experiments on the dominant kernel alone (not part of the build)
-  return launch_cfg<2, 2, 2, 2>(a, transA, transB, batch, ragged == 1 ? max_ragged : M, ragged >= 2 ? max_ragged : K, false, ws, ws_floats, stream);
-#endif
-  // the tail split is tuned for the 128 x 128 tile (512 resident workgroups); the other pipelined tile shapes use it for under-filled
-  // launches only (launch_cfg; CGC_GEMM_SPLIT=2: always)
-  float* const ws_any = ws;
+  // (the tail split is tuned for the 128 x 128 tile, 512 resident workgroups; the other pipelined tile shapes use it for under-filled
+  // launches only: launch_cfg)
   if (ragged == 1 && (transA || a.gptr == nullptr)) return CGC_EINVAL;
   if (ragged == 2 && (!transA || transB || a.gptr == nullptr || a.nx > 0)) return CGC_EINVAL;
   if (ragged == 3 && (!transA || transB || a.nx > 0 || max_ragged <= 0 || K <= 0 || batch % ceil_div(K, max_ragged) != 0)) return CGC_EINVAL;
@@ -753,16 +676,13 @@ static int gemm_dispatch(GemmArgs& a, int transA, int transB, int batch, int max
   // tile shape by output aspect: the hot contractions are (>=1140) x (>=1140); the skinny ones are K- or output-bound.
   // `fill` = workgroups a 128-row tiling would launch; below ~448 (256 CUs x 2 resident) the tile is halved in M.
   const int k_extent = ragged >= 2 ? max_ragged : K;
-  static const int shortk_max = getenv("CGC_GEMM_SHORTK") ? atoi(getenv("CGC_GEMM_SHORTK")) : 160;
-  static const int fill_min = getenv("CGC_GEMM_FILL") ? atoi(getenv("CGC_GEMM_FILL")) : 448;
+  constexpr int shortk_max = 160, fill_min = 448;
   const bool sk = k_extent <= shortk_max && a.nx == 0;
   const long long fill = (long long)ceil_div(m_extent, 128) * batch;
   // the 128 x 128 pipelined route; mode CGC_GEMM_SPLIT_BF16: as six bf16 MFMA pairs on 256 x 128 tiles (gemm_split.hip) when every
   // operand segment is fit for unguarded 16-byte loads; otherwise -- and for every other route -- the exact kernel
-  static const int force_mode = getenv("CGC_GEMM_MODE") ? atoi(getenv("CGC_GEMM_MODE")) : -1;      // experiments: overrides the argument
   // mode CGC_GEMM_SPLIT_F16: as three fp16 MFMA pairs of operands scaled per batch item (gemm_half.hip), same tiles, same condition
-  const int eff_mode = force_mode >= 0 ? force_mode : mode;
-  const bool want_split = eff_mode == CGC_GEMM_SPLIT_BF16, want_half = eff_mode == CGC_GEMM_SPLIT_F16;
+  const bool want_split = mode == CGC_GEMM_SPLIT_BF16, want_half = mode == CGC_GEMM_SPLIT_F16;
   auto big_route = [&](bool shortk, float* w) -> int {
     if ((want_split || want_half) && !shortk && !(transA && transB) && gemm_all_fast(a, transA, transB, batch, m_extent, k_extent)) {
       int rc = want_half ? gemm_half_launch(a, transA, transB, batch, m_extent, k_extent, w, ws_floats, stream) : CGC_EINVAL;
@@ -771,42 +691,42 @@ static int gemm_dispatch(GemmArgs& a, int transA, int transB, int batch, int max
     }
     return launch_cfg<2, 2, 2, 2>(a, transA, transB, batch, m_extent, k_extent, shortk, w, ws_floats, stream);
   };
-  // experiment hook: CGC_GEMM_CFG = 1..6 forces a tile shape (128x128, 128x64, 64x128, 64x64, 128x32, 32x128), +10 forces the
+  // tuning hook (cgc_gemm_tuning): 1..6 forces a tile shape (128x128, 128x64, 64x128, 64x64, 128x32, 32x128), +10 forces the
   // pipelined kernel, +20 the short-K kernel
   const int force = g_force_cfg;
   if (force > 0) {
     const bool fsk = force >= 20 ? true : force >= 10 ? false : sk;
     switch (force % 10) {
       case 1: return big_route(fsk, ws);
-      case 2: return launch_cfg<4, 1, 1, 2>(a, transA, transB, batch, m_extent, k_extent, fsk, ws_any, ws_floats, stream);
-      case 3: return launch_cfg<1, 4, 2, 1>(a, transA, transB, batch, m_extent, k_extent, fsk, ws_any, ws_floats, stream);
-      case 4: return launch_cfg<2, 2, 1, 1>(a, transA, transB, batch, m_extent, k_extent, fsk, ws_any, ws_floats, stream);
-      case 5: return launch_cfg<4, 1, 1, 1>(a, transA, transB, batch, m_extent, k_extent, fsk, ws_any, ws_floats, stream);
-      case 6: return launch_cfg<1, 4, 1, 1>(a, transA, transB, batch, m_extent, k_extent, fsk, ws_any, ws_floats, stream);
+      case 2: return launch_cfg<4, 1, 1, 2>(a, transA, transB, batch, m_extent, k_extent, fsk, ws, ws_floats, stream);
+      case 3: return launch_cfg<1, 4, 2, 1>(a, transA, transB, batch, m_extent, k_extent, fsk, ws, ws_floats, stream);
+      case 4: return launch_cfg<2, 2, 1, 1>(a, transA, transB, batch, m_extent, k_extent, fsk, ws, ws_floats, stream);
+      case 5: return launch_cfg<4, 1, 1, 1>(a, transA, transB, batch, m_extent, k_extent, fsk, ws, ws_floats, stream);
+      case 6: return launch_cfg<1, 4, 1, 1>(a, transA, transB, batch, m_extent, k_extent, fsk, ws, ws_floats, stream);
       default: break;
     }
   }
-  if (N <= 32) return launch_cfg<4, 1, 1, 1>(a, transA, transB, batch, m_extent, k_extent, sk, ws_any, ws_floats, stream);          // 128 x 32
+  if (N <= 32) return launch_cfg<4, 1, 1, 1>(a, transA, transB, batch, m_extent, k_extent, sk, ws, ws_floats, stream);          // 128 x 32
   if (N <= 64) {
-    if (m_extent > 64 && fill < fill_min) return launch_cfg<2, 2, 1, 1>(a, transA, transB, batch, m_extent, k_extent, sk, ws_any, ws_floats, stream);   // 64 x 64
-    return launch_cfg<4, 1, 1, 2>(a, transA, transB, batch, m_extent, k_extent, sk, ws_any, ws_floats, stream);                                     // 128 x 64
+    if (m_extent > 64 && fill < fill_min) return launch_cfg<2, 2, 1, 1>(a, transA, transB, batch, m_extent, k_extent, sk, ws, ws_floats, stream);   // 64 x 64
+    return launch_cfg<4, 1, 1, 2>(a, transA, transB, batch, m_extent, k_extent, sk, ws, ws_floats, stream);                                     // 128 x 64
   }
-  if (m_extent <= 32) return launch_cfg<1, 4, 1, 1>(a, transA, transB, batch, m_extent, k_extent, sk, ws_any, ws_floats, stream);   // 32 x 128
-  if (m_extent <= 64) return launch_cfg<1, 4, 2, 1>(a, transA, transB, batch, m_extent, k_extent, sk, ws_any, ws_floats, stream);   // 64 x 128
+  if (m_extent <= 32) return launch_cfg<1, 4, 1, 1>(a, transA, transB, batch, m_extent, k_extent, sk, ws, ws_floats, stream);   // 32 x 128
+  if (m_extent <= 64) return launch_cfg<1, 4, 2, 1>(a, transA, transB, batch, m_extent, k_extent, sk, ws, ws_floats, stream);   // 64 x 128
   if (fill * ceil_div(N, 128) < fill_min) {   // too few 128x128 tiles to fill the chip (tools/gemm_cfg_sweep.py over the step's shapes)
     if (N <= 128) {                           // one column tile: long reductions stream A through 128x32 tiles (4 column tiles share the
       if (k_extent > 256 && m_extent > 128)   // A panel in L2; [32 x 1140 x 1140] x [1140 x 114]: 200 -> 155 us), short ones take 64x64
-        return launch_cfg<4, 1, 1, 1>(a, transA, transB, batch, m_extent, k_extent, sk, ws_any, ws_floats, stream);
-      return launch_cfg<2, 2, 1, 1>(a, transA, transB, batch, m_extent, k_extent, sk, ws_any, ws_floats, stream);
+        return launch_cfg<4, 1, 1, 1>(a, transA, transB, batch, m_extent, k_extent, sk, ws, ws_floats, stream);
+      return launch_cfg<2, 2, 1, 1>(a, transA, transB, batch, m_extent, k_extent, sk, ws, ws_floats, stream);
     }
     if (transA) {
       // long reductions (S^T P of a 4-graph shard: 324 tiles of 57 k-tiles): whole 128 x 128 tiles, cut in two along K, beat
       // twice as many 128 x 64 tiles (235 -> 208 us).  (More pieces per tile -- 3 = 1.9 rounds of a third -- were measured
       // too: 204 us, and a cost model that picked the piece count by rounds x length made the small tails slower.)
       if (!sk && ws != nullptr && k_extent >= 24 * BK) return big_route(sk, ws);
-      return launch_cfg<4, 1, 1, 2>(a, transA, transB, batch, m_extent, k_extent, sk, ws_any, ws_floats, stream);
+      return launch_cfg<4, 1, 1, 2>(a, transA, transB, batch, m_extent, k_extent, sk, ws, ws_floats, stream);
     }
-    return launch_cfg<1, 4, 2, 1>(a, transA, transB, batch, m_extent, k_extent, sk, ws_any, ws_floats, stream);
+    return launch_cfg<1, 4, 2, 1>(a, transA, transB, batch, m_extent, k_extent, sk, ws, ws_floats, stream);
   }
   return big_route(sk, ws);                        // 128 x 128
 }
@@ -818,7 +738,7 @@ static void gemm_fill(GemmArgs& a, int M, int N, int K, float alpha, const float
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
   a.strideA = strideA; a.strideB = strideB; a.strideC = strideC;
   a.alpha = alpha; a.beta = beta; a.ragged = ragged; a.tiles_n = 0;
-  a.per_batch = a.nb = 0; a.ws = nullptr; a.resident = 0; a.s_max = 1; a.map_mode = 0; a.chunk = 0; a.scale = nullptr;
+  a.per_batch = a.nb = 0; a.ws = nullptr; a.resident = 0; a.s_max = 1; a.chunk = 0; a.scale = nullptr;
   a.nx = 0;
   for (int i = 0; i < 2; ++i) { a.xA[i] = a.xB[i] = nullptr; a.xlda[i] = a.xldb[i] = a.xK[i] = 0; a.xsA[i] = a.xsB[i] = 0; }
 }

@@ -1,8 +1,6 @@
 // Shared pieces of the matrix-core GEMM kernels (gemm.hip: exact fp32 MFMA; gemm_split.hip: fp32 products as six bf16 MFMA pairs):
 // argument block, tile map with tail split, per-item operand bases, the epilogue through LDS, the fix-up kernel of the tail split.
 #pragma once
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "common.hpp"
@@ -20,7 +18,6 @@ struct GemmArgs {
   float alpha, beta;
   int ragged;
   int tiles_n;
-  int map_mode;   // bit 0: compact tile list for ragged M, bit 1: K-balanced dealing for ragged K (TileMap)
   int per_batch;  // tiles of one batch item at the largest extent; the 1-D grid holds per_batch * nb ids (+ tail pieces)
   int nb;         // batch items
   // tail split (see TileMap): slabs of raw accumulators for the pieces of the tail tiles; nullptr = every tile is computed whole
@@ -40,16 +37,6 @@ struct GemmArgs {
 };
 
 #define BK 32
-#ifdef CGC_GEMM_TRACE      // experiment build (tools/gemm_wg_timeline.py): per-workgroup timestamps of the 128 x 128 kernel's phases
-__device__ unsigned long long g_gemm_trace[65536][6];
-#define GT_MARK(slot_) \
-  if (TM == 2 && TN == 2 && threadIdx.x == 0 && blockIdx.x < 65536) g_gemm_trace[blockIdx.x][slot_] = wall_clock64();
-extern "C" int cgc_gemm_trace_read(unsigned long long* host, int n) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_gemm_trace), sizeof(unsigned long long) * 6 * (size_t)n);
-}
-#else
-#define GT_MARK(slot_)
-#endif
 enum { PH_FULL = 0, PH_MASK = 1, PH_ANY = 4 };   // flavours of a k-loop phase (k_gemm_f32)
 #define KC_LD 36   // LDS row stride (words) of a row-major [mn][k] tile: 16-byte aligned rows, conflict-free ds_read_b128
 
@@ -115,7 +102,7 @@ struct TileMap {
     mode = 0;
     incl = t = rank = 0;
     T = (unsigned)a.per_batch * nb;
-    if (a.ragged == 1 && nb <= 64 && (a.map_mode & 1)) {
+    if (a.ragged == 1 && nb <= 64) {
       mode = 1;
       const int ext = lane < (int)nb ? a.gptr[lane + 1] - a.gptr[lane] : 0;
       t = (ext + BM - 1) / BM;                     // m-tile rows of graph `lane`
@@ -125,7 +112,7 @@ struct TileMap {
         if (lane >= o) incl += up;
       }
       T = (unsigned)__shfl(incl, 63) * a.tiles_n;  // real tiles of the launch
-    } else if (a.ragged == 2 && nb <= 64 && (nb & 7u) == 0 && (a.map_mode & 2)) {
+    } else if (a.ragged == 2 && nb <= 64 && (nb & 7u) == 0) {
       mode = 2;
       const int ext = lane < (int)nb ? a.gptr[lane + 1] - a.gptr[lane] : -1;
       for (int j = 0; j < (int)nb; ++j) {
@@ -379,3 +366,62 @@ __global__ __launch_bounds__(64) void k_gemm_fixup(const GemmArgs a) {
   gemm_epilogue<1, 1>(a, tb.C, tb.M, a.N, m0 + (wm * TM + i) * 32, n0 + (wn * TN + j) * 32, acc, park, lane);
 }
 
+
+// Host side of a launch on WGM x WGN workgroups of TM x TN accumulators (gemm.hip: launch_cfg; gemm_split.hip, gemm_half.hip): the
+// tile counts, the tail-split set-up, the timing record and the fix-up launch.  The caller launches its own main kernel on grid().
+template <int WGM, int WGN, int TM, int TN>
+struct GemmPlan {
+  static constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
+  GemmArgs a;
+  long long tiles = 0;   // tiles of the launch
+  long long kt = 0;      // k-tiles of one tile's reduction, the extra K segments included
+  int extra = 0;         // grid room for the pieces of the tail tiles
+  int trec = -1;
+
+  // false: the grid would overflow (the caller returns CGC_EINVAL)
+  bool init(const GemmArgs& a0, int batch, int m_extent, int k_extent, int k_tile) {
+    a = a0;
+    a.tiles_n = ceil_div(a.N, BN);
+    const long long per_batch = (long long)ceil_div(m_extent, BM) * a.tiles_n;
+    tiles = per_batch * batch;
+    if (per_batch <= 0 || tiles > 0x7ffffff0LL) return false;
+    a.per_batch = (int)per_batch;
+    a.nb = batch;
+    a.ws = nullptr;
+    a.resident = 0;
+    a.s_max = 1;
+    kt = ceil_div(k_extent, k_tile);
+    for (int i = 0; i < a.nx; ++i) kt += ceil_div(a.xK[i], k_tile);
+    return true;
+  }
+  // tail split (TileMap): a piece keeps >= min_kt k-tiles, a tail tile is cut into <= 12 pieces, and the slabs of up to
+  // 1.5 x resident pieces (L * S <= 1.5 R by construction) must fit the workspace
+  void tail_split(float* ws, long long ws_floats, int min_kt, int resident) {
+    const int s_max = (int)(kt / min_kt < 12 ? kt / min_kt : 12);
+    const long long max_pieces = resident + resident / 2;
+    if (s_max >= 2 && max_pieces * BM * BN <= ws_floats) {
+      a.ws = ws;
+      a.resident = resident;
+      a.s_max = s_max;
+      extra = (int)max_pieces;
+    }
+  }
+  dim3 grid() const { return dim3((unsigned)(tiles + extra)); }
+  void timing_begin(int m_extent, int k_extent, hipStream_t stream) {
+    int xk = 0;
+    for (int i = 0; i < a.nx; ++i) xk += a.xK[i];
+    trec = cgc_timing_begin(CGC_TAG_GEMM_128, a.M, a.N, a.K, a.nb, a.ragged, a.ragged ? (a.ragged == 1 ? m_extent : k_extent) : 0, xk,
+                            stream);
+  }
+  // behind the main kernel: the fix-up of at most min(T, R - 1) tail tiles (which ones, if any, is decided on the device exactly
+  // as in the main kernel), then the end of the timing record
+  int finish(hipStream_t stream) {
+    if (a.ws != nullptr) {
+      const long long lmax = tiles < a.resident ? tiles : a.resident - 1;
+      hipLaunchKernelGGL((k_gemm_fixup<WGM, WGN, TM, TN>), dim3((unsigned)(lmax * 4 * TM * TN)), dim3(64), 0, stream, a);
+      CGC_RETURN_IF_LAUNCH_FAILED();
+    }
+    cgc_timing_end(trec, stream);
+    return 0;
+  }
+};

@@ -88,9 +88,6 @@ __device__ __forceinline__ void half_micro(int sidx, HalfGroup (&gs)[6], const f
     s.hp[0] = pack_f16(s.x[0], s.x[1]);
     s.hp[1] = pack_f16(s.x[2], s.x[3]);
   } else if (st == 1) {
-#ifdef H_ABL_NOSPLIT      // (timing-only ablations, tools/variant_lib.sh: the result is wrong)
-    return;
-#endif
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       s.r[2 * h] = resid_lo(s.hp[h], s.x[2 * h]);
@@ -98,17 +95,9 @@ __device__ __forceinline__ void half_micro(int sidx, HalfGroup (&gs)[6], const f
     }
     asm volatile("" : "+v"(s.r[0]), "+v"(s.r[1]), "+v"(s.r[2]), "+v"(s.r[3]));
   } else if (st == 2) {
-#ifdef H_ABL_NOSPLIT
-    s.lp[0] = s.hp[0];
-    s.lp[1] = s.hp[1];
-    return;
-#endif
     s.lp[0] = pack_f16(s.r[0], s.r[1]);
     s.lp[1] = pack_f16(s.r[2], s.r[3]);
   } else {
-#ifdef H_ABL_NOWRITE
-    return;
-#endif
     if (u < 4) {
       LoaderA::put(wa, u, 0, s.hp[0], s.hp[1]);
       LoaderA::put(wa, u, H_PLA, s.lp[0], s.lp[1]);
@@ -257,12 +246,9 @@ __device__ __forceinline__ void half_body(const GemmArgs& a, const int b, const 
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fb[POS][j][PB_[t]]), __builtin_bit_cast(f16x8, fa[POS][i][PA_[t]]),
                                                            acc[i][j], 0, 0, 0);
       // the next tile's fragments into the other register set: 12 reads of 16 bytes (8 for a half tile)
-#ifndef H_ABL_NOFRAG
       if (m < 8) { if ((m >> 1) < NA) fa[POS ^ 1][m >> 1][m & 1] = frag16(rstage + fa_off + (m >> 1) * 32 * SROW + (m & 1) * H_PLA); }
       else if (m < 12) fb[POS ^ 1][(m - 8) >> 1][m & 1] = frag16(rstage + fb_off + ((m - 8) >> 1) * 32 * SROW + (m & 1) * H_PLB);
-#endif
       half_micro<LoaderA, LoaderB, !FULL>(m, gs, ra[POS], rb[POS], wa, wb, k0s, klims, sa, sb);
-#ifndef H_ABL_NOLOAD
       if (m >= 13 && m < 13 + NFA) {            // (group 3 of A took its values at m = 12)
         if constexpr (FULL) ra[POS][m - 13] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrcA, offA[m - 13], soffA, 0));
         else ra[POS][m - 13] = LoaderA::load_any(m - 13, tnext.A, tnext.lda, m0, a_last, tnext.k0, tnext.klim);
@@ -271,12 +257,9 @@ __device__ __forceinline__ void half_body(const GemmArgs& a, const int b, const 
         if constexpr (FULL) rb[POS][m - 21] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrcB, offB[m - 21], soffB, 0));
         else rb[POS][m - 21] = LoaderB::load_any(m - 21, tnext.B, tnext.ldb, n0, b_last, tnext.k0, tnext.klim);
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
     }
-#ifndef H_ABL_NOBAR
     __syncthreads();
-#endif
   };
   typedef std::true_type FULL_;
   typedef std::false_type ANY_;
@@ -424,7 +407,7 @@ static const int kHalfResident = 256;
 
 static int64_t g_half_launches = 0;
 // tile x k-tile steps below which gemm_half_launch declines (tuning hook, tests: 0 = never decline)
-static int64_t g_half_min_work = getenv("CGC_HALF_MIN_WORK") ? atoll(getenv("CGC_HALF_MIN_WORK")) : 28000;
+static int64_t g_half_min_work = 28000;
 extern "C" int64_t cgc_gemm_half_min_work(int64_t v) {
   const int64_t old = __atomic_load_n(&g_half_min_work, __ATOMIC_RELAXED);
   if (v >= 0) __atomic_store_n(&g_half_min_work, v, __ATOMIC_RELAXED);
@@ -441,52 +424,21 @@ int gemm_half_launch(const GemmArgs& a0, int transA, int transB, int batch, int 
                      hipStream_t stream) {
   if (transA && transB) return CGC_EINVAL;
   if (ws == nullptr || ws_floats < H_SCALE_FLOATS || batch > 65535) return CGC_EINVAL;
-  GemmArgs a = a0;
-  a.tiles_n = ceil_div(a.N, S_BN);
-  static const int map_mode = getenv("CGC_GEMM_MAP") ? atoi(getenv("CGC_GEMM_MAP")) : 3;
-  a.map_mode = map_mode;
-  const long long per_batch = (long long)ceil_div(m_extent, S_BM) * a.tiles_n;
-  const long long tiles = per_batch * batch;
-  if (per_batch <= 0 || tiles > 0x7ffffff0LL) return CGC_EINVAL;
+  GemmPlan<2, 2, 4, 2> plan;
+  if (!plan.init(a0, batch, m_extent, k_extent, SBK)) return CGC_EINVAL;
   const int ta = ceil_div(m_extent, S_BM);
-  const long long slots = (long long)batch * (ta + a.tiles_n);
+  const long long slots = (long long)batch * (ta + plan.a.tiles_n);
   if (slots > H_SCALE_FLOATS) return CGC_EINVAL;
   // The mode pays once the product kernel's saving (~30 % of the bf16 kernel's time) exceeds its own fixed cost (the slot fill, the
   // maximum pass: two launches and one more trip over the operands).  Measured on the step's six products at 32 / 16 / 8 / 4 graphs
   // (profiles/r06_configurations.txt): ahead of the bf16 mode by 18 / 17 / 10 % down to 8 graphs (37-47 k tile x k-tile steps per
   // product), behind it by 6 % at 4 (19-23 k) and at C1 = 180 (5 k).  Below 28 k steps the caller runs the bf16 kernel instead.
-  const long long min_work = __atomic_load_n(&g_half_min_work, __ATOMIC_RELAXED);
-  {
-    long long kt = ceil_div(k_extent, SBK);
-    for (int i = 0; i < a.nx; ++i) kt += ceil_div(a.xK[i], SBK);
-    if (tiles * kt < min_work) return CGC_EINVAL;
-  }
-  a.per_batch = (int)per_batch;
-  a.nb = batch;
-  a.ws = nullptr;
-  a.resident = 0;
-  a.s_max = 1;
-  ws_floats -= H_SCALE_FLOATS;
-  unsigned* scale = reinterpret_cast<unsigned*>(ws + ws_floats);
-  a.scale = scale;
-  int extra = 0;
-  static const int split_on = getenv("CGC_GEMM_SPLIT") ? atoi(getenv("CGC_GEMM_SPLIT")) : 1;
-  if (split_on) {
-    long long kt = ceil_div(k_extent, SBK);
-    for (int i = 0; i < a.nx; ++i) kt += ceil_div(a.xK[i], SBK);
-    const int s_max = (int)(kt / 8 < 12 ? kt / 8 : 12);                 // a piece keeps >= 8 k-tiles: the pipeline is five deep
-    const long long max_pieces = kHalfResident + kHalfResident / 2;
-    if (s_max >= 2 && max_pieces * S_BM * S_BN <= ws_floats) {
-      a.ws = ws;
-      a.resident = kHalfResident;
-      a.s_max = s_max;
-      extra = (int)max_pieces;
-    }
-  }
-  int xk = 0;
-  for (int i = 0; i < a.nx; ++i) xk += a.xK[i];
-  const int trec = cgc_timing_begin(CGC_TAG_GEMM_128, a.M, a.N, a.K, batch, a.ragged, a.ragged ? (a.ragged == 1 ? m_extent : k_extent) : 0,
-                                    xk, stream);
+  if (plan.tiles * plan.kt < __atomic_load_n(&g_half_min_work, __ATOMIC_RELAXED)) return CGC_EINVAL;
+  unsigned* scale = reinterpret_cast<unsigned*>(ws + (ws_floats - H_SCALE_FLOATS));
+  plan.a.scale = scale;
+  plan.tail_split(ws, ws_floats - H_SCALE_FLOATS, 8, kHalfResident);    // a piece keeps >= 8 k-tiles: the pipeline is five deep
+  plan.timing_begin(m_extent, k_extent, stream);
+  const GemmArgs& a = plan.a;
   {
     const hipError_t e = hipMemsetAsync(scale, 0, sizeof(unsigned) * (size_t)slots, stream);
     if (e != hipSuccess) return (int)e;
@@ -494,7 +446,7 @@ int gemm_half_launch(const GemmArgs& a0, int transA, int transB, int batch, int 
   // ~4 workgroups per CU for each operand, a panel's rows shared by up to 64 of them
   auto subs = [&](int panels) { const long long n = (long long)batch * panels; const int v = n >= 1024 ? 1 : ceil_div(1024, (int)n); return v > 64 ? 64 : v; };
   const int sub_a = subs(ta), sub_b = subs(a.tiles_n);
-  dim3 grid((unsigned)(tiles + extra)), block(256), mgrid((unsigned)(ta * sub_a + a.tiles_n * sub_b), (unsigned)batch);
+  const dim3 grid = plan.grid(), block(256), mgrid((unsigned)(ta * sub_a + a.tiles_n * sub_b), (unsigned)batch);
 #define HALF_LAUNCH(TA_, TB_)                                                                               \
   do {                                                                                                      \
     static bool attr__[CGC_MAX_DEVICES] = {};                                                               \
@@ -508,11 +460,5 @@ int gemm_half_launch(const GemmArgs& a0, int transA, int transB, int batch, int 
 #undef HALF_LAUNCH
   CGC_RETURN_IF_LAUNCH_FAILED();
   __atomic_fetch_add(&g_half_launches, 1, __ATOMIC_RELAXED);
-  if (a.ws != nullptr) {
-    const long long lmax = tiles < kHalfResident ? tiles : kHalfResident - 1;
-    hipLaunchKernelGGL((k_gemm_fixup<2, 2, 4, 2>), dim3((unsigned)(lmax * 4 * 4 * 2)), dim3(64), 0, stream, a);
-    CGC_RETURN_IF_LAUNCH_FAILED();
-  }
-  cgc_timing_end(trec, stream);
-  return 0;
+  return plan.finish(stream);
 }

@@ -313,12 +313,10 @@ __global__ __launch_bounds__(256, 1) void k_gemm_split(const GemmArgs a) {
   tj = __builtin_amdgcn_readfirstlane(tj);
   const TileBase tb(a, b);
   const int rows_left = tb.M - (tile_id / a.tiles_n) * S_BM;
-#ifndef S_NO_HALF            // (-DS_NO_HALF: A/B timing builds)
   if (S == 1 && rows_left <= 128) {
     split_body<TA, TB, true>(a, b, tile_id, piece, S, tj, slds);
     return;
   }
-#endif
   split_body<TA, TB, false>(a, b, tile_id, piece, S, tj, slds);
 }
 
@@ -335,38 +333,13 @@ extern "C" int64_t cgc_gemm_split_count(void) { return __atomic_load_n(&g_split_
 int gemm_split_launch(const GemmArgs& a0, int transA, int transB, int batch, int m_extent, int k_extent, float* ws, int64_t ws_floats,
                       hipStream_t stream) {
   if (transA && transB) return CGC_EINVAL;
-  GemmArgs a = a0;
-  a.tiles_n = ceil_div(a.N, S_BN);
-  static const int map_mode = getenv("CGC_GEMM_MAP") ? atoi(getenv("CGC_GEMM_MAP")) : 3;
-  a.map_mode = map_mode;
-  const long long per_batch = (long long)ceil_div(m_extent, S_BM) * a.tiles_n;
-  const long long tiles = per_batch * batch;
-  if (per_batch <= 0 || tiles > 0x7ffffff0LL) return CGC_EINVAL;
-  // k offsets are 32-bit scalar byte offsets (16 k rows of an [K, .] operand at a time): same limits as the exact kernel checked
-  a.per_batch = (int)per_batch;
-  a.nb = batch;
-  a.ws = nullptr;
-  a.resident = 0;
-  a.s_max = 1;
-  int extra = 0;
-  static const int split_on = getenv("CGC_GEMM_SPLIT") ? atoi(getenv("CGC_GEMM_SPLIT")) : 1;
-  if (ws != nullptr && split_on) {
-    long long kt = ceil_div(k_extent, SBK);
-    for (int i = 0; i < a.nx; ++i) kt += ceil_div(a.xK[i], SBK);
-    const int s_max = (int)(kt / 8 < 12 ? kt / 8 : 12);                 // a piece keeps >= 8 k-tiles: the pipeline is five deep
-    const long long max_pieces = kSplitResident + kSplitResident / 2;
-    if (s_max >= 2 && max_pieces * S_BM * S_BN <= ws_floats) {
-      a.ws = ws;
-      a.resident = kSplitResident;
-      a.s_max = s_max;
-      extra = (int)max_pieces;
-    }
-  }
-  int xk = 0;
-  for (int i = 0; i < a.nx; ++i) xk += a.xK[i];
-  const int trec = cgc_timing_begin(CGC_TAG_GEMM_128, a.M, a.N, a.K, batch, a.ragged, a.ragged ? (a.ragged == 1 ? m_extent : k_extent) : 0,
-                                    xk, stream);
-  dim3 grid((unsigned)(tiles + extra)), block(256);
+  // (k offsets are 32-bit scalar byte offsets, 16 k rows of an [K, .] operand at a time: same limits as the exact kernel checked)
+  GemmPlan<2, 2, 4, 2> plan;
+  if (!plan.init(a0, batch, m_extent, k_extent, SBK)) return CGC_EINVAL;
+  if (ws != nullptr) plan.tail_split(ws, ws_floats, 8, kSplitResident);      // a piece keeps >= 8 k-tiles: the pipeline is five deep
+  plan.timing_begin(m_extent, k_extent, stream);
+  const GemmArgs& a = plan.a;
+  const dim3 grid = plan.grid(), block(256);
 #define SPLIT_LAUNCH(TA_, TB_)                                                                              \
   do {                                                                                                      \
     static bool attr__[CGC_MAX_DEVICES] = {};                                                               \
@@ -379,11 +352,5 @@ int gemm_split_launch(const GemmArgs& a0, int transA, int transB, int batch, int
 #undef SPLIT_LAUNCH
   CGC_RETURN_IF_LAUNCH_FAILED();
   __atomic_fetch_add(&g_split_launches, 1, __ATOMIC_RELAXED);
-  if (a.ws != nullptr) {
-    const long long lmax = tiles < kSplitResident ? tiles : kSplitResident - 1;
-    hipLaunchKernelGGL((k_gemm_fixup<2, 2, 4, 2>), dim3((unsigned)(lmax * 4 * 4 * 2)), dim3(64), 0, stream, a);
-    CGC_RETURN_IF_LAUNCH_FAILED();
-  }
-  cgc_timing_end(trec, stream);
-  return 0;
+  return plan.finish(stream);
 }

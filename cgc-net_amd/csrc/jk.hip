@@ -9,8 +9,6 @@
 // recomputes the gate activations, back-propagates through time in registers, and writes the gate gradients and the cell
 // inputs TRANSPOSED ([4H+1][3*npad], [C+2H+1][3*npad]) so that every weight / bias / attention gradient falls out of one
 // batched NT GEMM per direction (cgc_gemm_f32) followed by the deterministic slice reduction.
-#include <stdlib.h>
-
 #include "jk.hpp"
 
 template <int C>
@@ -337,11 +335,8 @@ extern "C" int cgc_jk_lstm_fwd(const float* xs, int n, int npad, int C, const fl
   if (npad < n) return CGC_EINVAL;
   JkWeights w;
   fill_weights(w, lstm, w_att, b_att);
-  static const int k_mfma = getenv("CGC_JK_MFMA") != nullptr ? atoi(getenv("CGC_JK_MFMA")) : 1;
-  if (k_mfma) {
-    const int rc = jk_mfma_fwd(xs, n, npad, C, w, out, HS, CS, as_stream(stream));
-    if (rc != CGC_EINVAL) return rc;          // unaligned buffers: the thread-per-direction kernel takes any alignment
-  }
+  const int rc = jk_mfma_fwd(xs, n, npad, C, w, out, HS, CS, as_stream(stream));
+  if (rc != CGC_EINVAL) return rc;            // unaligned buffers: the thread-per-direction kernel takes any alignment
   switch (C) {
 #define X(C_) case C_: return launch_jk_fwd<C_>(xs, n, npad, w, out, HS, CS, as_stream(stream));
     JK_FOR_EACH_C(X)
@@ -357,11 +352,8 @@ extern "C" int cgc_jk_lstm_bwd(const float* xs, const float* dout, int n, int np
   if (npad < n) return CGC_EINVAL;
   JkWeights w;
   fill_weights(w, lstm, w_att, b_att);
-  static const int k_mfma = getenv("CGC_JK_MFMA") != nullptr ? atoi(getenv("CGC_JK_MFMA")) : 1;
-  if (k_mfma) {
-    const int rc = jk_mfma_bwd(xs, dout, n, npad, C, w, HS, CS, dxs, DGT, INT, as_stream(stream));
-    if (rc != CGC_EINVAL) return rc;
-  }
+  const int rc = jk_mfma_bwd(xs, dout, n, npad, C, w, HS, CS, dxs, DGT, INT, as_stream(stream));
+  if (rc != CGC_EINVAL) return rc;
   switch (C) {
 #define X(C_) case C_: return launch_jk_bwd<C_>(xs, dout, n, npad, w, HS, CS, dxs, DGT, INT, DHC, as_stream(stream));
     JK_FOR_EACH_C(X)

@@ -11,21 +11,15 @@
 // row = unit) are staged once per workgroup in LDS in fragment order and read back as conflict-free ds_read_b128.
 // fp32 MFMA keeps the exact fp32 FMA chain (1e-4 parity budget); the thread-per-direction kernels in jk.hip ran at ~7 %
 // of the fp32 peak (1 wave/SIMD, LDS-broadcast bound), these run the same arithmetic at matrix-core rate.
+// This one-wave layout (round 2) remains in the staged backward k_jk_bwd_mfma; the forward and the backward with in-kernel
+// parameter gradients run on the unit-split kernels further down (eight waves per tile).
 #include "jk.hpp"
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
-#ifndef JKM_WAVES
-#define JKM_WAVES 2      // workgroups per CU the register allocation aims for (2 x 57 KB of LDS)
-#endif
-#ifndef JKM_FWD_UNROLL
-#define JKM_FWD_UNROLL 1    // recurrence rolled: 10-15 % faster than fully unrolled (less register pressure, same MFMA stream)
-#endif
-#ifndef JKB_TILES
-#define JKB_TILES 2          // node tiles per backward workgroup (x 2 directions = 4 waves, one per SIMD; 4 tiles = 2 waves per
-                             // SIMD under a 256-register cap measured 10-100 % slower: spills and coarser work units)
-#endif
-#define JKB_THREADS (JKB_TILES * 128)
+constexpr int JKB_TILES = 2;     // node tiles per backward workgroup (x 2 directions = 4 waves, one per SIMD; 4 tiles = 2 waves per
+                                 // SIMD under a 256-register cap measured 10-100 % slower: spills and coarser work units)
+constexpr int JKB_THREADS = JKB_TILES * 128;
 
 template <int C>
 struct JkM {
@@ -38,34 +32,21 @@ struct JkM {
   static constexpr int A_OFF = B_OFF + 2 * 4 * 32;             // w_att [d][32], then b_att
   static constexpr int S_OFF = A_OFF + 2 * 32 + 4;             // score exchange [node half 2][d 2][t 3][32]
   static constexpr int TOTAL = S_OFF + 2 * 2 * 3 * 32;
-  static constexpr size_t lds_bytes = sizeof(float) * TOTAL;
-  static constexpr int PG_FLOATS = (8 * 16 + 16 + 1) * 64;        // parameter-gradient partial of one wave
   static_assert(H <= 32 && C % 4 == 0, "one 32-row tile per gate; 16-byte x fragments");
 };
 
-#ifdef CGC_JK_PRECISE
-__device__ __forceinline__ float fast_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ float fast_tanh(float x) { return tanhf(x); }
-#define JK_EXP expf
-#else
 // Reciprocal of d in [1, inf]: v_rcp_f32 (1 ulp) instead of the correctly rounded division sequence the library's compile flags
 // turn __frcp_rn / `1.f / d` into (v_div_scale x 2, v_rcp, five FMAs, v_div_fmas, v_div_fixup: ten instructions, five times per
 // hidden unit and recurrence step in kernels that issue 8 vector instructions per MFMA).  The error stays RELATIVE (what the
-// medium_shipped margins are sensitive to: see fast_tanh) and below that of the __expf in front of it.  JK_RCP_NEWTON adds one
-// Newton step (two FMAs, ~0.5 ulp; the argument is clamped so that d stays finite: rcp(inf) = 0 and 0 * inf would poison it).
-#ifndef JK_RCP_NEWTON
-#define JK_RCP_NEWTON 1      // round 6: on.  Plain v_rcp_f32 (1 ulp) moved medium_shipped's worst margin against the reference's float64 gradients from
-#endif                       // 3.1e-5 to 9.9e-5 (GCN_embed_3.gcn1.bias amplifies a relative error of the gates a thousandfold); with the Newton step: see DESIGN
-#if JK_RCP_NEWTON
+// medium_shipped margins are sensitive to: see fast_tanh) and below that of the __expf in front of it.  One Newton step follows
+// (two FMAs, ~0.5 ulp; the argument is clamped so that d stays finite: rcp(inf) = 0 and 0 * inf would poison it): plain v_rcp_f32
+// (1 ulp) moved medium_shipped's worst margin against the reference's float64 gradients from 3.1e-5 to 9.9e-5 (GCN_embed_3.gcn1.bias
+// amplifies a relative error of the gates a thousandfold); with the Newton step: see DESIGN.
 __device__ __forceinline__ float jk_rcp(float d) {
   const float r = __builtin_amdgcn_rcpf(d);
   return fmaf(fmaf(-d, r, 1.f), r, r);
 }
 __device__ __forceinline__ float fast_sigmoid(float x) { return jk_rcp(1.f + __expf(fminf(-x, 87.f))); }
-#else
-__device__ __forceinline__ float jk_rcp(float d) { return __builtin_amdgcn_rcpf(d); }
-__device__ __forceinline__ float fast_sigmoid(float x) { return jk_rcp(1.f + __expf(-x)); }
-#endif
 // tanh with a few ulp of RELATIVE error everywhere.  The one-line form 2 / (1 + exp(-2x)) - 1 has ~2e-7 of ABSOLUTE error, i.e.
 // 2e-6 relative at |x| = 0.1 and 2e-4 at 1e-3 -- cell states and gate inputs of a freshly initialised LSTM are that small, and on
 // the reference-generated medium_shipped fixture the network amplifies it a thousandfold (a one-ulp perturbation of the parameters
@@ -79,8 +60,6 @@ __device__ __forceinline__ float fast_tanh(float x) {
   const float small = ax * fmaf(x2, fmaf(x2, fmaf(x2, fmaf(x2, 62.f / 2835.f, -17.f / 315.f), 2.f / 15.f), -1.f / 3.f), 1.f);
   return copysignf(ax < 0.25f ? small : big, x);
 }
-#define JK_EXP __expf
-#endif
 
 template <int C>
 __device__ __forceinline__ void jkm_fill(const JkWeights& w, float* lds, int nthreads) {
@@ -117,142 +96,18 @@ __device__ __forceinline__ void jkm_fill(const JkWeights& w, float* lds, int nth
   if (threadIdx.x == 0) lds[M::A_OFF + 64] = w.b_att[0];
 }
 
-template <int C>
-__global__ __launch_bounds__(256, JKM_WAVES) void k_jk_fwd_mfma(const float* __restrict__ xs, int n, int npad, const JkWeights w,
-                                                     float* __restrict__ out, float* __restrict__ HS, float* __restrict__ CS) {
-  using M = JkM<C>;
-  constexpr int H = M::H, XG = M::XG, HG = M::HG, NQ = M::NQ;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  jkm_fill<C>(w, lds, 256);
-  __syncthreads();
-  const int lane = threadIdx.x & 63, l31 = lane & 31, lhi = lane >> 5;
-  const int wave = threadIdx.x >> 6, d = wave & 1, half = wave >> 1;
-  const float4* Wl = reinterpret_cast<const float4*>(lds) + (size_t)d * 4 * NQ * 64 + l31 * 2 + lhi;   // + (g*NQ + q)*64
-  const float* Bl = lds + M::B_OFF + d * 128 + 4 * lhi;          // + g*32 + 8q'
-  const float* Al = lds + M::A_OFF + d * 32 + 4 * lhi;           // + 8q'
-  float* Sx = lds + M::S_OFF + half * 192;                       // [d][t][32]
-  const int ntiles = (n + 31) / 32;
-
-  for (int base = blockIdx.x * 2; base < ntiles; base += gridDim.x * 2) {
-    const int node = (base + half) * 32 + l31;
-    const bool valid = node < n, keep = node < npad && base + half < ntiles;
-    const float* xrow = xs + (size_t)(valid ? node : 0) * 3 * C + 4 * lhi;
-    floatx16 cst, hst;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { cst[r] = 0.f; hst[r] = 0.f; }
-
-#pragma unroll JKM_FWD_UNROLL
-    for (int s = 0; s < 3; ++s) {
-      const int t = d ? 2 - s : s;
-      floatx16 acc[4];
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 b = *reinterpret_cast<const float4*>(Bl + g * 32 + 8 * q);
-          acc[g][4 * q + 0] = b.x; acc[g][4 * q + 1] = b.y; acc[g][4 * q + 2] = b.z; acc[g][4 * q + 3] = b.w;
-        }
-      // input part: B operand = x_t fragment of this lane's node
-#pragma unroll
-      for (int q = 0; q < XG; ++q) {
-        float4 xf = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (valid && (8 * q + 4 * lhi < C)) xf = *reinterpret_cast<const float4*>(xrow + t * C + 8 * q);
-        float4 a[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) a[g] = Wl[(g * NQ + q) * 64];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].x, xf.x, acc[g], 0, 0, 0);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].y, xf.y, acc[g], 0, 0, 0);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].z, xf.z, acc[g], 0, 0, 0);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].w, xf.w, acc[g], 0, 0, 0);
-      }
-      // recurrent part: B operand = h_{t-1}, straight from the registers the previous step left it in (zero at s = 0)
-      if (s > 0) {
-#pragma unroll
-        for (int q = 0; q < HG; ++q) {
-          float4 a[4];
-#pragma unroll
-          for (int g = 0; g < 4; ++g) a[g] = Wl[(g * NQ + XG + q) * 64];
-#pragma unroll
-          for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].x, hst[4 * q + 0], acc[g], 0, 0, 0);
-#pragma unroll
-          for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].y, hst[4 * q + 1], acc[g], 0, 0, 0);
-#pragma unroll
-          for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].z, hst[4 * q + 2], acc[g], 0, 0, 0);
-#pragma unroll
-          for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].w, hst[4 * q + 3], acc[g], 0, 0, 0);
-        }
-      }
-      // LSTM cell, register by register (unit j = (r&3) + 8(r>>2) + 4*lhi of this lane's node)
-      float p = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 wa = *reinterpret_cast<const float4*>(Al + 8 * q);
-        const float was[4] = {wa.x, wa.y, wa.z, wa.w};
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int r = 4 * q + u, j = u + 8 * q + 4 * lhi;
-          const float gi = fast_sigmoid(acc[0][r]), gf = fast_sigmoid(acc[1][r]);
-          const float gg = fast_tanh(acc[2][r]), go = fast_sigmoid(acc[3][r]);
-          const float c = gf * cst[r] + gi * gg;
-          const float h = go * fast_tanh(c);
-          cst[r] = c;
-          hst[r] = h;
-          p = fmaf(was[u], h, p);
-          if (8 * q + u < H && j < H && keep) {      // (first clause prunes whole padded groups at compile time)
-            const size_t slot = (size_t)((d * 3 + t) * H + j) * npad + node;
-            HS[slot] = h;
-            CS[slot] = c;
-          }
-        }
-      }
-      p += __shfl_xor(p, 32);
-      if (lhi == 0) Sx[(d * 3 + t) * 32 + l31] = p;
-    }
-    __syncthreads();
-    float sc[3];
-#pragma unroll
-    for (int t = 0; t < 3; ++t) sc[t] = Sx[t * 32 + l31] + Sx[(3 + t) * 32 + l31] + lds[M::A_OFF + 64];
-    const float m = fmaxf(sc[0], fmaxf(sc[1], sc[2]));
-    float a3[3], den = 0.f;
-#pragma unroll
-    for (int t = 0; t < 3; ++t) { a3[t] = JK_EXP(sc[t] - m); den += a3[t]; }
-    const float inv = 1.f / den;
-    if (d == 0 && valid) {
-#pragma unroll
-      for (int q = 0; q < XG; ++q) {
-        if (8 * q + 4 * lhi < C) {
-          const float4 x0 = *reinterpret_cast<const float4*>(xrow + 0 * C + 8 * q);
-          const float4 x1 = *reinterpret_cast<const float4*>(xrow + 1 * C + 8 * q);
-          const float4 x2 = *reinterpret_cast<const float4*>(xrow + 2 * C + 8 * q);
-          float4 o;
-          o.x = (a3[0] * x0.x + a3[1] * x1.x + a3[2] * x2.x) * inv;
-          o.y = (a3[0] * x0.y + a3[1] * x1.y + a3[2] * x2.y) * inv;
-          o.z = (a3[0] * x0.z + a3[1] * x1.z + a3[2] * x2.z) * inv;
-          o.w = (a3[0] * x0.w + a3[1] * x1.w + a3[2] * x2.w) * inv;
-          *reinterpret_cast<float4*>(out + (size_t)node * C + 8 * q + 4 * lhi) = o;
-        }
-      }
-    }
-    __syncthreads();          // the score exchange buffer is rewritten by the next tile
-  }
-}
-
-// Backward on the matrix cores.  Same tiling (one wave = 32 nodes x one direction, lane = node).  Per recurrence step, last
-// to first: the gate pre-activations are recomputed with the forward's MFMAs (h_{t-1}, c_{t-1} come back from HS / CS as
+// Staged backward on the matrix cores (cgc_jk_lstm_bwd).  One wave = 32 nodes x one direction, lane = node, as described at the
+// top of this file.  Per recurrence step, last to first: the gate pre-activations are recomputed with the forward's MFMAs (h_{t-1}, c_{t-1} come back from HS / CS as
 // coalesced loads already in operand layout), the cell backward runs per register, and the four gate-gradient tiles q_g --
 // still "lane = node, register = unit" -- are directly the B operand of  d[h_{t-1} | x_t]^T = W^T . q  (A operand = W^T,
 // read out of the SAME LDS image the forward uses, strided: 4-way bank conflicts, irrelevant next to 128 MFMAs), whose
 // accumulator layout hands dh_{t-1} to the next step in registers and dx_t as 16-byte fragments.  Gate gradients and cell
 // inputs are written transposed (DGT / INT, see jk.hip) for the parameter-gradient GEMM.
-template <int C, bool PG>
+template <int C>
 __global__ __launch_bounds__(JKB_THREADS) void k_jk_bwd_mfma(const float* __restrict__ xs, const float* __restrict__ dout, int n, int npad,
                                                      const JkWeights w, const float* __restrict__ HS, const float* __restrict__ CS,
                                                      float* __restrict__ dxs, float* __restrict__ DGT, float* __restrict__ INT,
-                                                     float* __restrict__ PART) {
+                                                     float* __restrict__ /* unused: keeps the argument layout */) {
   using M = JkM<C>;
   constexpr int H = M::H, XG = M::XG, HG = M::HG, NQ = M::NQ;
   constexpr int NG = 4 * H + 1, NI = C + 2 * H + 1;
@@ -274,27 +129,9 @@ __global__ __launch_bounds__(JKB_THREADS) void k_jk_bwd_mfma(const float* __rest
   float* dgt = DGT + (size_t)d * NG * ktot;
   float* inT = INT + (size_t)d * NI * ktot;
   const int ntiles = npad / 32;
-  // PG: parameter gradients accumulated here.  dW[(g,j)][kin] = sum_node q_g[node][j] * in[node][kin] contracts over the
-  // LANE dimension of the layout above, so q and the cell inputs take one trip through a per-wave LDS tile ([node][36]) to
-  // come back with lane = row / column and the node pair as the MFMA k index.  8 persistent accumulator tiles per wave:
-  // (gate g) x (inputs: h part with the bias column at 31 | x part); attention-weight gradients per lane.
-  float* Qw = lds + M::TOTAL + JKB_TILES * 192 + JKB_TILES * 2 * 3 * XG * 64 * 4 + (size_t)wave * 3 * 32 * 36;
-  float* Iw = Qw + 32 * 36;                       // two input tiles
-  floatx16 dW[PG ? 4 : 1][2];
-  floatx16 wacc;
-  float bacc = 0.f;
-  if (PG) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { dW[g][0][r] = 0.f; dW[g][1][r] = 0.f; }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) wacc[r] = 0.f;
-  }
 
   for (int base = blockIdx.x * JKB_TILES; base < ntiles; base += gridDim.x * JKB_TILES) {
     const int node = (base + half) * 32 + l31;
-    if (PG && base * 32 >= n) break;            // padding tiles contribute nothing
     if (base * 32 >= n) {            // all tiles of this workgroup pass are padding columns: they must read as zero in the GEMM
       for (int t = 0; t < 3; ++t) {
         const size_t col = (size_t)t * npad + node;
@@ -332,7 +169,7 @@ __global__ __launch_bounds__(JKB_THREADS) void k_jk_bwd_mfma(const float* __rest
       const float m = fmaxf(sc[0], fmaxf(sc[1], sc[2]));
       float den = 0.f;
 #pragma unroll
-      for (int t = 0; t < 3; ++t) { a3[t] = JK_EXP(sc[t] - m); den += a3[t]; }
+      for (int t = 0; t < 3; ++t) { a3[t] = __expf(sc[t] - m); den += a3[t]; }
       const float inv = 1.f / den;
       float da[3] = {0.f, 0.f, 0.f}, mean = 0.f;
 #pragma unroll
@@ -360,11 +197,8 @@ __global__ __launch_bounds__(JKB_THREADS) void k_jk_bwd_mfma(const float* __rest
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dhc[r] = 0.f; dcc[r] = 0.f; }
 
-    // (the staged variant is ~7 % faster with the recurrence rolled, the in-kernel-gradient variant ~20 % slower)
-#ifndef JKB_PG_UNROLL
-#define JKB_PG_UNROLL 3
-#endif
-#pragma clang loop unroll_count(PG ? JKB_PG_UNROLL : 1)
+    // (~7 % faster with the recurrence rolled)
+#pragma clang loop unroll_count(1)
     for (int s = 2; s >= 0; --s) {
       const int t = d ? 2 - s : s, tprev = d ? t + 1 : t - 1;
       const size_t col = (size_t)t * npad + node;
@@ -425,13 +259,13 @@ __global__ __launch_bounds__(JKB_THREADS) void k_jk_bwd_mfma(const float* __rest
         }
       }
       // ---- cell backward per (node, unit); acc[g] is overwritten with d loss / d pre-activation of gate g
-      if (!PG && lhi == 0) {
+      if (lhi == 0) {
         dgt[(size_t)(4 * H) * ktot + col] = dst;
         inT[(size_t)(C + H) * ktot + col] = 1.f;
       }
 #pragma unroll
       for (int q = 0; q < XG; ++q) {
-        if (!PG && 8 * q + 4 * lhi < C) {
+        if (8 * q + 4 * lhi < C) {
           inT[(size_t)(8 * q + 4 * lhi + 0) * ktot + col] = xt[q].x;
           inT[(size_t)(8 * q + 4 * lhi + 1) * ktot + col] = xt[q].y;
           inT[(size_t)(8 * q + 4 * lhi + 2) * ktot + col] = xt[q].z;
@@ -455,66 +289,13 @@ __global__ __launch_bounds__(JKB_THREADS) void k_jk_bwd_mfma(const float* __rest
           const float qi = dc * gg * gi * (1.f - gi), qf = dc * cprev[r] * gf * (1.f - gf);
           const float qg = dc * gi * (1.f - gg * gg), qo = dh * th * go * (1.f - go);
           acc[0][r] = qi; acc[1][r] = qf; acc[2][r] = qg; acc[3][r] = qo;
-          if (PG) wacc[r] = fmaf(dst, go * th, wacc[r]);          // d w_att[j] += ds_t * h_t[j]
-          if (!PG && 8 * q + u < H && j < H) {
+          if (8 * q + u < H && j < H) {
             dgt[(size_t)(0 * H + j) * ktot + col] = qi;
             dgt[(size_t)(1 * H + j) * ktot + col] = qf;
             dgt[(size_t)(2 * H + j) * ktot + col] = qg;
             dgt[(size_t)(3 * H + j) * ktot + col] = qo;
             inT[(size_t)(C + j) * ktot + col] = hprev[r];
             inT[(size_t)(C + H + 1 + j) * ktot + col] = go * th;
-          }
-        }
-      }
-      if (PG) {
-        if (lhi == 0) bacc += dst;                                // d b_att (one lane half per node)
-        // inputs of this step, node-major: tile 0 = h_{t-1} (+ 1.0 at column 31: the bias column), tile 1 = x_t
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (q < HG) v = make_float4(hprev[4 * q + 0], hprev[4 * q + 1], hprev[4 * q + 2], hprev[4 * q + 3]);
-          if (q == 3 && lhi == 1) v.w = 1.f;
-          *reinterpret_cast<float4*>(Iw + l31 * 36 + 8 * q + 4 * lhi) = v;
-          float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (q < XG) xv = xt[q];
-          *reinterpret_cast<float4*>(Iw + 32 * 36 + l31 * 36 + 8 * q + 4 * lhi) = xv;
-        }
-        __builtin_amdgcn_wave_barrier();
-#ifndef JKB_BF_RELOAD
-#define JKB_BF_RELOAD 0      // 1: the input fragments are read from the LDS tile again for every gate (32 registers less held)
-#endif
-        float bf[2][16];
-        if (!JKB_BF_RELOAD) {
-#pragma unroll
-          for (int kk = 0; kk < 16; ++kk) {
-            bf[0][kk] = Iw[(2 * kk + lhi) * 36 + l31];
-            bf[1][kk] = Iw[32 * 36 + (2 * kk + lhi) * 36 + l31];
-          }
-        }
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          if (JKB_BF_RELOAD) {
-#pragma unroll
-            for (int kk = 0; kk < 16; ++kk) {
-              bf[0][kk] = Iw[(2 * kk + lhi) * 36 + l31];
-              bf[1][kk] = Iw[32 * 36 + (2 * kk + lhi) * 36 + l31];
-            }
-          }
-          __builtin_amdgcn_wave_barrier();
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (q < HG) v = make_float4(acc[g][4 * q + 0], acc[g][4 * q + 1], acc[g][4 * q + 2], acc[g][4 * q + 3]);
-            *reinterpret_cast<float4*>(Qw + l31 * 36 + 8 * q + 4 * lhi) = v;
-          }
-          __builtin_amdgcn_wave_barrier();
-          float af[16];
-#pragma unroll
-          for (int kk = 0; kk < 16; ++kk) af[kk] = Qw[(2 * kk + lhi) * 36 + l31];
-#pragma unroll
-          for (int kk = 0; kk < 16; ++kk) {
-            dW[g][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk], bf[0][kk], dW[g][0], 0, 0, 0);
-            dW[g][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk], bf[1][kk], dW[g][1], 0, 0, 0);
           }
         }
       }
@@ -564,22 +345,9 @@ __global__ __launch_bounds__(JKB_THREADS) void k_jk_bwd_mfma(const float* __rest
     }
     __syncthreads();
   }
-  if (PG) {       // this wave's partial parameter gradients: [8 tiles x 16 registers | 16 attention registers | bias] x 64 lanes
-    float* pw = PART + ((size_t)d * gridDim.x * JKB_TILES + (size_t)blockIdx.x * JKB_TILES + half) * JkM<C>::PG_FLOATS + lane;
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) pw[((g * 2 + m) * 16 + r) * 64] = dW[g][m][r];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) pw[(128 + r) * 64] = wacc[r];
-    pw[144 * 64] = bacc;
-  }
 }
 
-// parameter-gradient partials -> G [2][4H+1][C+2H+1] (the layout ops.py reads: rows = gate pre-activations then the
-// attention score, columns = x (C) | h_{t-1} (H) | 1 | h_t (H)), two deterministic stages
+// first of the two deterministic stages that reduce k_jku_bwd's parameter-gradient partials: sums of 16 partials each
 __global__ void k_jk_pg_fold(const float* __restrict__ part, int P, int P2, int per, float* __restrict__ tmp) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x, p2 = blockIdx.y, d = blockIdx.z;
   if (e >= per) return;
@@ -590,85 +358,8 @@ __global__ void k_jk_pg_fold(const float* __restrict__ part, int P, int P2, int 
   tmp[((size_t)d * P2 + p2) * per + e] = a;
 }
 
-template <int C>
-__global__ void k_jk_pg_finish(const float* __restrict__ tmp, int P2, float* __restrict__ G) {
-  constexpr int H = JkM<C>::H, per = JkM<C>::PG_FLOATS, NG = 4 * H + 1, NI = C + 2 * H + 1;
-  const int e = blockIdx.x * blockDim.x + threadIdx.x, d = blockIdx.y;
-  if (e >= per) return;
-  const int slot = e >> 6, lane = e & 63, lhi = lane >> 5, kin = lane & 31;
-  const float* src = tmp + (size_t)d * P2 * per;
-  if (slot < 128) {
-    const int tile = slot >> 4, r = slot & 15, g = tile >> 1, m = tile & 1;
-    const int j = (r & 3) + 8 * (r >> 2) + 4 * lhi;
-    int col = -1;
-    if (m == 0) col = kin < H ? C + kin : (kin == 31 ? C + H : -1);
-    else col = kin < C ? kin : -1;
-    if (j >= H || col < 0) return;
-    float a = 0.f;
-    for (int k = 0; k < P2; ++k) a += src[(size_t)k * per + e];
-    G[((size_t)d * NG + g * H + j) * NI + col] = a;
-  } else if (kin == 0) {                        // per-lane (= per-node) sums: fold the 32 lanes of this half
-    const int r = slot - 128;
-    if (slot < 144) {
-      const int j = (r & 3) + 8 * (r >> 2) + 4 * lhi;
-      if (j >= H) return;
-      float a = 0.f;
-      for (int k = 0; k < P2; ++k)
-        for (int l = 0; l < 32; ++l) a += src[(size_t)k * per + slot * 64 + lhi * 32 + l];
-      G[((size_t)d * NG + 4 * H) * NI + C + H + 1 + j] = a;
-    } else if (lhi == 0 && d == 0) {
-      float a = 0.f;
-      for (int k = 0; k < P2; ++k)
-        for (int l = 0; l < 32; ++l) a += src[(size_t)k * per + slot * 64 + l];
-      G[((size_t)4 * H) * NI + C + H] = a;
-    }
-  }
-}
-
-// the same second stage writing the parameter gradients straight into the flat buffer of cgc_jk_unpack_param_grads (per direction
-// dW_ih [4H,C] | dW_hh [4H,H] | db_ih [4H] | db_hh [4H], then d att.weight [2H], d att.bias): no G, no memset, no unpack kernel.
-// Same summation order per element as k_jk_pg_finish.
-template <int C>
-__global__ void k_jk_pg_finish_flat(const float* __restrict__ tmp, int P2, float* __restrict__ flat) {
-  constexpr int H = JkM<C>::H, per = JkM<C>::PG_FLOATS;
-  constexpr int per_dir = 4 * H * C + 4 * H * H + 8 * H, total = 2 * per_dir + 2 * H + 1;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  int d, row = 0, col = 0, att = -1;               // G coordinates of flat element i: (d, row = g*H + j, col) or an attention entry
-  if (i < 2 * per_dir) {
-    d = i / per_dir;
-    int e = i - d * per_dir;
-    if (e < 4 * H * C) { row = e / C; col = e % C; }
-    else if ((e -= 4 * H * C) < 4 * H * H) { row = e / H; col = C + e % H; }
-    else { e -= 4 * H * H; row = e % (4 * H); col = C + H; }
-  } else {
-    const int e = i - 2 * per_dir;
-    if (e < 2 * H) { d = e / H; att = e % H; }
-    else { d = 0; att = H; }                        // attention bias
-  }
-  const float* src = tmp + (size_t)d * P2 * per;
-  float a = 0.f;
-  if (att < 0) {
-    const int g = row / H, j = row - g * H;
-    const int m = col < C ? 1 : 0;                 // tile: m = 1 the x part, m = 0 the h part with the bias column at lane 31
-    const int kin = col < C ? col : (col == C + H ? 31 : col - C);
-    const int lhi = (j >> 2) & 1, r = (j & 3) + 4 * (j >> 3);
-    const int e = ((g * 2 + m) * 16 + r) * 64 + lhi * 32 + kin;
-    for (int k = 0; k < P2; ++k) a += src[(size_t)k * per + e];
-  } else if (att < H) {
-    const int j = att, lhi = (j >> 2) & 1, r = (j & 3) + 4 * (j >> 3), slot = 128 + r;
-    for (int k = 0; k < P2; ++k)
-      for (int l = 0; l < 32; ++l) a += src[(size_t)k * per + slot * 64 + lhi * 32 + l];
-  } else {
-    for (int k = 0; k < P2; ++k)
-      for (int l = 0; l < 32; ++l) a += src[(size_t)k * per + 144 * 64 + l];
-  }
-  flat[i] = a;
-}
-
-
 // =====================================================================================================================
-// Unit-split kernels (round 3).  The kernels above give one wave a whole (32-node tile, direction): 368 MFMAs per recurrence
+// Unit-split kernels (round 3).  The kernel above gives one wave a whole (32-node tile, direction): 368 MFMAs per recurrence
 // step in the backward, 8 persistent accumulator tiles, 213 spilled registers, and ~100 us of strictly serial work per tile --
 // the launch is as long as its longest wave however few nodes there are (3 x 107 us at 4 graphs per GPU).  Here EIGHT waves
 // share a tile: wave (d, w) owns direction d and the hidden units 8w .. 8w+7.  Its M tile of the transposed gate product is
@@ -830,7 +521,7 @@ __global__ __launch_bounds__(512) void k_jku_fwd(const float* __restrict__ xs, i
       const float m = fmaxf(sc[0], fmaxf(sc[1], sc[2]));
       float a3[3], den = 0.f;
 #pragma unroll
-      for (int t = 0; t < 3; ++t) { a3[t] = JK_EXP(sc[t] - m); den += a3[t]; }
+      for (int t = 0; t < 3; ++t) { a3[t] = __expf(sc[t] - m); den += a3[t]; }
       const float inv = 1.f / den;
       const int q = ww;
       if (valid && 8 * q + 4 * lhi < C) {
@@ -849,7 +540,7 @@ __global__ __launch_bounds__(512) void k_jku_fwd(const float* __restrict__ xs, i
   }
 }
 
-// Backward, unit-split (parameter gradients accumulated in-kernel; the staged variant stays with k_jk_bwd_mfma<C, false>).
+// Backward, unit-split (parameter gradients accumulated in-kernel; the staged backward is k_jk_bwd_mfma).
 template <int C>
 __global__ __launch_bounds__(512) void k_jku_bwd(const float* __restrict__ xs, const float* __restrict__ dout, int n, int npad,
                                                  const JkWeights w, const float* __restrict__ HS, const float* __restrict__ CS,
@@ -927,7 +618,7 @@ __global__ __launch_bounds__(512) void k_jku_bwd(const float* __restrict__ xs, c
       const float m = fmaxf(sc[0], fmaxf(sc[1], sc[2]));
       float den = 0.f, mean = 0.f;
 #pragma unroll
-      for (int t = 0; t < 3; ++t) { a3[t] = JK_EXP(sc[t] - m); den += a3[t]; }
+      for (int t = 0; t < 3; ++t) { a3[t] = __expf(sc[t] - m); den += a3[t]; }
       const float inv = 1.f / den;
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
@@ -1209,26 +900,49 @@ __global__ void k_jku_finish_G(const float* __restrict__ tmp, int P2, float* __r
   G[i] = v;
 }
 
-// CGC_JK_UNITSPLIT=0: the one-wave-per-(tile, direction) kernels (A-B timing)
-static const int g_unit_split = getenv("CGC_JK_UNITSPLIT") ? atoi(getenv("CGC_JK_UNITSPLIT")) : 1;
-
 template <int C>
-static int launch_fwd_us(const float* xs, int n, int npad, const JkWeights& w, float* out, float* HS, float* CS, hipStream_t st) {
+static int launch_fwd(const float* xs, int n, int npad, const JkWeights& w, float* out, float* HS, float* CS, hipStream_t st) {
   constexpr size_t lds = sizeof(float) * JkU<C>::FWD_TOTAL;
   static bool attr_set[CGC_MAX_DEVICES] = {};
   cgc_allow_lds(reinterpret_cast<const void*>(&k_jku_fwd<C>), (int)lds, attr_set);
   int grid = ceil_div(n, 32);
-  static const int fgrid = getenv("CGC_JKU_FGRID") ? atoi(getenv("CGC_JKU_FGRID")) : 512;
-  if (grid > fgrid) grid = fgrid;             // persistent over the 32-node tiles
+  if (grid > 512) grid = 512;                 // persistent over the 32-node tiles
   hipLaunchKernelGGL(k_jku_fwd<C>, dim3(grid), dim3(512), lds, st, xs, n, npad, w, out, HS, CS);
   CGC_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
 
-// flat != nullptr: gradients in parameter order (cgc_jk_unpack_param_grads' layout); else G [2][4H+1][C+2H+1]
+int jk_mfma_fwd(const float* xs, int n, int npad, int C, const JkWeights& w, float* out, float* HS, float* CS, hipStream_t st) {
+  if ((reinterpret_cast<uintptr_t>(xs) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u)) return CGC_EINVAL;
+  switch (C) {
+    case 4: return launch_fwd<4>(xs, n, npad, w, out, HS, CS, st);
+    case 8: return launch_fwd<8>(xs, n, npad, w, out, HS, CS, st);
+    case 12: return launch_fwd<12>(xs, n, npad, w, out, HS, CS, st);
+    case 16: return launch_fwd<16>(xs, n, npad, w, out, HS, CS, st);
+    case 20: return launch_fwd<20>(xs, n, npad, w, out, HS, CS, st);
+    default: return CGC_EINVAL;
+  }
+}
+
+// staged backward: gate gradients and cell inputs to DGT / INT for the parameter-gradient GEMM
 template <int C>
-static int launch_bwd_us(const float* xs, const float* dout, int n, int npad, const JkWeights& w, const float* HS, const float* CS,
-                         float* dxs, float* G, float* ws, hipStream_t st, float* flat) {
+static int launch_bwd(const float* xs, const float* dout, int n, int npad, const JkWeights& w, const float* HS, const float* CS,
+                      float* dxs, float* DGT, float* INT, hipStream_t st) {
+  const size_t lds = sizeof(float) * (JkM<C>::TOTAL + JKB_TILES * 192) + sizeof(float4) * JKB_TILES * 2 * 3 * JkM<C>::XG * 64;
+  static bool attr_set[CGC_MAX_DEVICES] = {};
+  cgc_allow_lds(reinterpret_cast<const void*>(&k_jk_bwd_mfma<C>), (int)lds, attr_set);
+  int grid = ceil_div(npad / 32, JKB_TILES);
+  if (grid > 256) grid = 256;                 // one workgroup per CU
+  hipLaunchKernelGGL(k_jk_bwd_mfma<C>, dim3(grid), dim3(JKB_THREADS), lds, st, xs, dout, n, npad, w, HS, CS, dxs, DGT, INT, nullptr);
+  CGC_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}
+
+// backward with in-kernel parameter gradients.  flat != nullptr: gradients in parameter order (cgc_jk_unpack_param_grads'
+// layout); else G [2][4H+1][C+2H+1]
+template <int C>
+static int launch_bwd_params(const float* xs, const float* dout, int n, int npad, const JkWeights& w, const float* HS, const float* CS,
+                             float* dxs, float* G, float* ws, hipStream_t st, float* flat) {
   constexpr size_t lds = sizeof(float) * JkU<C>::BWD_TOTAL;
   static bool attr_set[CGC_MAX_DEVICES] = {};
   cgc_allow_lds(reinterpret_cast<const void*>(&k_jku_bwd<C>), (int)lds, attr_set);
@@ -1251,76 +965,23 @@ static int launch_bwd_us(const float* xs, const float* dout, int n, int npad, co
   return 0;
 }
 
-template <int C>
-static int launch_fwd(const float* xs, int n, int npad, const JkWeights& w, float* out, float* HS, float* CS, hipStream_t st) {
-  if (g_unit_split) return launch_fwd_us<C>(xs, n, npad, w, out, HS, CS, st);
-  static bool attr_set[CGC_MAX_DEVICES] = {};
-  cgc_allow_lds(reinterpret_cast<const void*>(&k_jk_fwd_mfma<C>), (int)JkM<C>::lds_bytes, attr_set);
-  const int ntiles = ceil_div(n, 32);
-  int grid = ceil_div(ntiles, 2);
-  if (grid > 512) grid = 512;                 // 2 workgroups per CU (LDS), persistent over the 64-node tile pairs
-  hipLaunchKernelGGL(k_jk_fwd_mfma<C>, dim3(grid), dim3(256), JkM<C>::lds_bytes, st, xs, n, npad, w, out, HS, CS);
-  CGC_RETURN_IF_LAUNCH_FAILED();
-  return 0;
-}
-
-int jk_mfma_fwd(const float* xs, int n, int npad, int C, const JkWeights& w, float* out, float* HS, float* CS, hipStream_t st) {
-  if ((reinterpret_cast<uintptr_t>(xs) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u)) return CGC_EINVAL;
-  switch (C) {
-    case 4: return launch_fwd<4>(xs, n, npad, w, out, HS, CS, st);
-    case 8: return launch_fwd<8>(xs, n, npad, w, out, HS, CS, st);
-    case 12: return launch_fwd<12>(xs, n, npad, w, out, HS, CS, st);
-    case 16: return launch_fwd<16>(xs, n, npad, w, out, HS, CS, st);
-    case 20: return launch_fwd<20>(xs, n, npad, w, out, HS, CS, st);
-    default: return CGC_EINVAL;
-  }
-}
-
-template <int C, bool PG>
-static int launch_bwd(const float* xs, const float* dout, int n, int npad, const JkWeights& w, const float* HS, const float* CS,
-                      float* dxs, float* DGT, float* INT, float* G, float* ws, hipStream_t st, float* flat = nullptr) {
-  if (PG && g_unit_split) return launch_bwd_us<C>(xs, dout, n, npad, w, HS, CS, dxs, G, ws, st, flat);
-  size_t lds = sizeof(float) * (JkM<C>::TOTAL + JKB_TILES * 192) + sizeof(float4) * JKB_TILES * 2 * 3 * JkM<C>::XG * 64;
-  if (PG) lds += sizeof(float) * JKB_TILES * 2 * 3 * 32 * 36;
-  static bool attr_set[CGC_MAX_DEVICES] = {};
-  cgc_allow_lds(reinterpret_cast<const void*>(&k_jk_bwd_mfma<C, PG>), (int)lds, attr_set);
-  int grid = ceil_div(PG ? ceil_div(n, 32) : npad / 32, JKB_TILES);
-  if (grid > 256) grid = 256;                 // one workgroup per CU
-  hipLaunchKernelGGL((k_jk_bwd_mfma<C, PG>), dim3(grid), dim3(JKB_THREADS), lds, st, xs, dout, n, npad, w, HS, CS, dxs, DGT, INT, ws);
-  CGC_RETURN_IF_LAUNCH_FAILED();
-  if (PG) {
-    constexpr int per = JkM<C>::PG_FLOATS, NG = 4 * JkM<C>::H + 1, NI = C + 2 * JkM<C>::H + 1;
-    const int P = grid * JKB_TILES, P2 = ceil_div(P, 16);
-    float* tmp = ws + (size_t)2 * P * per;
-    hipLaunchKernelGGL(k_jk_pg_fold, dim3(ceil_div(per, 256), P2, 2), dim3(256), 0, st, ws, P, P2, per, tmp);
-    if (flat != nullptr) {
-      constexpr int H = JkM<C>::H, total = 2 * (4 * H * C + 4 * H * H + 8 * H) + 2 * H + 1;
-      hipLaunchKernelGGL(k_jk_pg_finish_flat<C>, dim3(ceil_div(total, 256)), dim3(256), 0, st, tmp, P2, flat);
-    } else {
-      (void)hipMemsetAsync(G, 0, sizeof(float) * 2 * NG * NI, st);
-      hipLaunchKernelGGL(k_jk_pg_finish<C>, dim3(ceil_div(per, 256), 2), dim3(256), 0, st, tmp, P2, G);
-    }
-    CGC_RETURN_IF_LAUNCH_FAILED();
-  }
-  return 0;
-}
-
 int jk_mfma_bwd(const float* xs, const float* dout, int n, int npad, int C, const JkWeights& w, const float* HS, const float* CS,
                 float* dxs, float* DGT, float* INT, hipStream_t st) {
   if ((reinterpret_cast<uintptr_t>(xs) & 15u) || (reinterpret_cast<uintptr_t>(dout) & 15u) || (reinterpret_cast<uintptr_t>(dxs) & 15u) ||
       npad % (32 * JKB_TILES) != 0)
     return CGC_EINVAL;
   switch (C) {
-    case 4: return launch_bwd<4, false>(xs, dout, n, npad, w, HS, CS, dxs, DGT, INT, nullptr, nullptr, st);
-    case 8: return launch_bwd<8, false>(xs, dout, n, npad, w, HS, CS, dxs, DGT, INT, nullptr, nullptr, st);
-    case 12: return launch_bwd<12, false>(xs, dout, n, npad, w, HS, CS, dxs, DGT, INT, nullptr, nullptr, st);
-    case 16: return launch_bwd<16, false>(xs, dout, n, npad, w, HS, CS, dxs, DGT, INT, nullptr, nullptr, st);
-    case 20: return launch_bwd<20, false>(xs, dout, n, npad, w, HS, CS, dxs, DGT, INT, nullptr, nullptr, st);
+    case 4: return launch_bwd<4>(xs, dout, n, npad, w, HS, CS, dxs, DGT, INT, st);
+    case 8: return launch_bwd<8>(xs, dout, n, npad, w, HS, CS, dxs, DGT, INT, st);
+    case 12: return launch_bwd<12>(xs, dout, n, npad, w, HS, CS, dxs, DGT, INT, st);
+    case 16: return launch_bwd<16>(xs, dout, n, npad, w, HS, CS, dxs, DGT, INT, st);
+    case 20: return launch_bwd<20>(xs, dout, n, npad, w, HS, CS, dxs, DGT, INT, st);
     default: return CGC_EINVAL;
   }
 }
 
-// workspace floats of the fused-parameter-gradient backward: partials of <= 512 waves per direction + their first fold
+// workspace floats of the fused-parameter-gradient backward (part of the ABI, unchanged since round 2): 2 x 512 partials of
+// (8 x 16 + 16 + 1) x 64 floats and their first fold, more than k_jku_bwd's <= 256 partials of JkU<C>::PG_FLOATS and their fold need
 int64_t jk_mfma_bwd_ws_floats(int C) {
   const int64_t per = (8 * 16 + 16 + 1) * 64;
   (void)C;
@@ -1332,11 +993,11 @@ int jk_mfma_bwd_flat(const float* xs, const float* dout, int n, int npad, int C,
   if ((reinterpret_cast<uintptr_t>(xs) & 15u) || (reinterpret_cast<uintptr_t>(dout) & 15u) || (reinterpret_cast<uintptr_t>(dxs) & 15u))
     return CGC_EINVAL;
   switch (C) {
-    case 4: return launch_bwd<4, true>(xs, dout, n, npad, w, HS, CS, dxs, nullptr, nullptr, nullptr, ws, st, flat);
-    case 8: return launch_bwd<8, true>(xs, dout, n, npad, w, HS, CS, dxs, nullptr, nullptr, nullptr, ws, st, flat);
-    case 12: return launch_bwd<12, true>(xs, dout, n, npad, w, HS, CS, dxs, nullptr, nullptr, nullptr, ws, st, flat);
-    case 16: return launch_bwd<16, true>(xs, dout, n, npad, w, HS, CS, dxs, nullptr, nullptr, nullptr, ws, st, flat);
-    case 20: return launch_bwd<20, true>(xs, dout, n, npad, w, HS, CS, dxs, nullptr, nullptr, nullptr, ws, st, flat);
+    case 4: return launch_bwd_params<4>(xs, dout, n, npad, w, HS, CS, dxs, nullptr, ws, st, flat);
+    case 8: return launch_bwd_params<8>(xs, dout, n, npad, w, HS, CS, dxs, nullptr, ws, st, flat);
+    case 12: return launch_bwd_params<12>(xs, dout, n, npad, w, HS, CS, dxs, nullptr, ws, st, flat);
+    case 16: return launch_bwd_params<16>(xs, dout, n, npad, w, HS, CS, dxs, nullptr, ws, st, flat);
+    case 20: return launch_bwd_params<20>(xs, dout, n, npad, w, HS, CS, dxs, nullptr, ws, st, flat);
     default: return CGC_EINVAL;
   }
 }
@@ -1346,11 +1007,11 @@ int jk_mfma_bwd_params(const float* xs, const float* dout, int n, int npad, int 
   if ((reinterpret_cast<uintptr_t>(xs) & 15u) || (reinterpret_cast<uintptr_t>(dout) & 15u) || (reinterpret_cast<uintptr_t>(dxs) & 15u))
     return CGC_EINVAL;
   switch (C) {
-    case 4: return launch_bwd<4, true>(xs, dout, n, npad, w, HS, CS, dxs, nullptr, nullptr, G, ws, st);
-    case 8: return launch_bwd<8, true>(xs, dout, n, npad, w, HS, CS, dxs, nullptr, nullptr, G, ws, st);
-    case 12: return launch_bwd<12, true>(xs, dout, n, npad, w, HS, CS, dxs, nullptr, nullptr, G, ws, st);
-    case 16: return launch_bwd<16, true>(xs, dout, n, npad, w, HS, CS, dxs, nullptr, nullptr, G, ws, st);
-    case 20: return launch_bwd<20, true>(xs, dout, n, npad, w, HS, CS, dxs, nullptr, nullptr, G, ws, st);
+    case 4: return launch_bwd_params<4>(xs, dout, n, npad, w, HS, CS, dxs, G, ws, st, nullptr);
+    case 8: return launch_bwd_params<8>(xs, dout, n, npad, w, HS, CS, dxs, G, ws, st, nullptr);
+    case 12: return launch_bwd_params<12>(xs, dout, n, npad, w, HS, CS, dxs, G, ws, st, nullptr);
+    case 16: return launch_bwd_params<16>(xs, dout, n, npad, w, HS, CS, dxs, G, ws, st, nullptr);
+    case 20: return launch_bwd_params<20>(xs, dout, n, npad, w, HS, CS, dxs, G, ws, st, nullptr);
     default: return CGC_EINVAL;
   }
 }

@@ -465,9 +465,6 @@ extern "C" int cgc_l2norm_act_bn(const float* h, int n, int F, int normalize, in
 // ------------------------------------------------------------------------------------------------
 // y = BN(act(hn))   (elementwise; y may be a column slice of a wider buffer: ldy)
 // ------------------------------------------------------------------------------------------------
-#ifndef CGC_BNAPPLY_UR
-#define CGC_BNAPPLY_UR 1
-#endif
 template <int VEC, int MAXJ>
 __global__ __launch_bounds__(256) void k_bn_act_apply(const BnApplyPtrs p0, const BnApplyPtrs p1, int n, int F, int lpr, int act, int ldy) {
   const BnApplyPtrs& p = blockIdx.y ? p1 : p0;
@@ -512,28 +509,21 @@ __global__ __launch_bounds__(256) void k_bn_act_apply(const BnApplyPtrs p0, cons
   auto rows = [&](auto act_c) {
     constexpr int ACT = decltype(act_c)::value;
     const int last = F - VEC;                            // (F >= VEC: F % VEC == 0 and F > 0)
-    constexpr int UR = (VEC == 4 && MAXJ == 5) ? CGC_BNAPPLY_UR : 1;      // adjacent rows per pass (-DCGC_BNAPPLY_UR; 1: 96 us, 2: 103, 4: 91 on [57.7k, 1140])
-    for (int base = rg.gwave * rg.rpw * UR; base < n; base += rg.nwaves * rg.rpw * UR) {
-      Vec<VEC> x[UR][MAXJ];
+    // (one row per pass: two or four adjacent rows per pass measured 103 / 91 us against 96 on [57.7k, 1140])
+    for (int base = rg.gwave * rg.rpw; base < n; base += rg.nwaves * rg.rpw) {
+      const int row = base + rg.sub;
+      const bool rowok = row < n;
+      Vec<VEC> x[MAXJ];
 #pragma unroll
-      for (int u = 0; u < UR; ++u) {
-        const int row = min(base + u * rg.rpw + rg.sub, n - 1);
+      for (int j = 0; j < MAXJ; ++j) load_wide<VEC, MAXJ>(x[j], hn + (size_t)min(row, n - 1) * F + min((rg.sl + lpr * j) * VEC, last));
 #pragma unroll
-        for (int j = 0; j < MAXJ; ++j) load_wide<VEC, MAXJ>(x[u][j], hn + (size_t)row * F + min((rg.sl + lpr * j) * VEC, last));
-      }
+      for (int j = 0; j < MAXJ; ++j) {
+        const int c = (rg.sl + lpr * j) * VEC;
 #pragma unroll
-      for (int u = 0; u < UR; ++u) {
-        const int row = base + u * rg.rpw + rg.sub;
-        const bool rowok = row < n;
-#pragma unroll
-        for (int j = 0; j < MAXJ; ++j) {
-          const int c = (rg.sl + lpr * j) * VEC;
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) x[u][j].v[v] = fmaf(act_fwd(x[u][j].v[v], ACT) - mu[j][v], sc[j][v], sh[j][v]);
-          if (rowok && c < F) {
-            x[u][j].store(y + (size_t)row * ldy + c);
-            if (y2 != nullptr) x[u][j].store(y2 + (size_t)row * ldy2 + c);
-          }
+        for (int v = 0; v < VEC; ++v) x[j].v[v] = fmaf(act_fwd(x[j].v[v], ACT) - mu[j][v], sc[j][v], sh[j][v]);
+        if (rowok && c < F) {
+          x[j].store(y + (size_t)row * ldy + c);
+          if (y2 != nullptr) x[j].store(y2 + (size_t)row * ldy2 + c);
         }
       }
     }

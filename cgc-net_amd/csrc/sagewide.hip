@@ -17,8 +17,6 @@
 //     the extra address arithmetic costs the second wave per SIMD, 186 us instead of 125 us).
 //   * persistent workgroups stride over the row tiles; at the end each leaves one slot row [2, F] of column sums, folded in a
 //     fixed order in fp64 by k_stats_finalize (rowops.hip): deterministic.
-#include <stdlib.h>
-
 #include "common.hpp"
 
 #define L2_EPS 1e-12f
@@ -160,8 +158,8 @@ __global__ __launch_bounds__(256, 1) void k_sage_wide_fwd(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// Round 4: the same operator as ONE pass of the matrix cores.  Timing ablations of the kernel above (tools/variant_lib.sh,
-// -DCGC_X_SW_*): 149 us with everything, 133 without the stores, 126 without the statistics, 103 without either -- it is bound by
+// Round 4: the same operator as ONE pass of the matrix cores.  Timing ablations of the kernel above (measured in round 4):
+// 149 us with everything, 133 without the stores, 126 without the statistics, 103 without either -- it is bound by
 // its own arithmetic: two rank-K passes of dependent 10-MFMA chains with one accumulator live (W in 90 registers leaves room for
 // no more), not by the 263 MB it writes.  Here W lives in LDS instead ([K][F] k-major: the B fragment of MFMA step s is one
 // conflict-free ds_read_b32), EIGHT waves share it and a 32-row tile (wave w owns NTW column tiles; two waves per SIMD inside one
@@ -240,11 +238,7 @@ __global__ __launch_bounds__(512, 1) void k_sage_wide_fwd8(const float* __restri
     for (int s = 0; s < KS; ++s) {
       const float* __restrict__ wrow = Wl + (size_t)(2 * s + lhi) * Fp + c_base + l31;
 #pragma unroll
-#ifndef CGC_X8_NOMFMA
       for (int t = 0; t < NTW; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], wrow[t * 32], acc[t], 0, 0, 0);
-#else
-      for (int t = 0; t < NTW; ++t) acc[t][s] += av[s] * wrow[t * 32];
-#endif
     }
     // The next row tile's A fragments are requested HERE -- behind this tile's MFMAs, in front of the norm reduction -- and waited for
     // in front of this tile's stores (the empty asm below).  vmcnt counts loads and stores in issue order: a wait for loads that
@@ -323,15 +317,11 @@ __global__ __launch_bounds__(512, 1) void k_sage_wide_fwd8(const float* __restri
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float v = acc[t][r] * rin[r];
-#ifndef CGC_X8_NOSTATS
           const float d = act_fwd(v, ACT) - shift[t];
           a1 += d;
           a2 = fmaf(d, d, a2);
-#endif
-#ifndef CGC_X8_NOSTORE
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc_hn, voff,
                                                 (unsigned)(row0 + (r & 3) + 8 * (r >> 2)) * (unsigned)ldh * 4u, 0);
-#endif
         }
       } else {
 #pragma unroll
@@ -493,10 +483,7 @@ __device__ __forceinline__ void load_rows(__amdgpu_buffer_rsrc_t rsrc, int row0,
 }
 
 template <int KS, int ACT>
-#ifndef CGC_SWC_WAVES
-#define CGC_SWC_WAVES 3
-#endif
-__global__ __launch_bounds__(256, CGC_SWC_WAVES) void k_sage_wide_cols(const float* __restrict__ agg, int lda, const float* __restrict__ W,
+__global__ __launch_bounds__(256, 3) void k_sage_wide_cols(const float* __restrict__ agg, int lda, const float* __restrict__ W,
                                                            const float* __restrict__ bias, int n, int K, int F,
                                                            const float* __restrict__ rinv, float* __restrict__ hn, int ldh,
                                                            float* __restrict__ ws, int row_tiles, int chunks, int ngroups) {
@@ -552,11 +539,7 @@ __global__ __launch_bounds__(256, CGC_SWC_WAVES) void k_sage_wide_cols(const flo
 #pragma unroll
     for (int s = 0; s < KS; ++s)
 #pragma unroll
-#ifndef CGC_SWC_NOMFMA
       for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bw[t][s], acc[t], 0, 0, 0);
-#else
-      for (int t = 0; t < NT; ++t) acc[t][s % 16] = av[s] + bw[t][s];        // (timing ablation: no matrix instruction, no chain)
-#endif
     // This tile's row factors and the next tile's A fragments are requested behind this tile's MFMAs and waited for in front of its
     // stores (vmcnt counts loads and stores in issue order: see k_sage_wide_fwd8).  (Requesting them INSIDE the chains -- step s's
     // fragment as soon as step s has consumed the current one -- was measured: 67 -> 71 us.)
@@ -601,17 +584,11 @@ __global__ __launch_bounds__(256, CGC_SWC_WAVES) void k_sage_wide_cols(const flo
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float v = acc[t][r] * rin[r];
-#ifndef CGC_SWC_NOSTATS
           const float d = act_fwd(v, ACT) - shift[t];
           a1 += d;
           a2 = fmaf(d, d, a2);
-#endif
-#ifndef CGC_SWC_NOSTORE
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc_hn, voff,
                                                 (unsigned)(row0 + (r & 3) + 8 * (r >> 2)) * (unsigned)ldh * 4u, 0);
-#else
-          asm volatile("" ::"v"(v));          // (timing ablation: the value stays computed, nothing is stored)
-#endif
         }
       } else {
 #pragma unroll
@@ -680,16 +657,14 @@ extern "C" int cgc_sage_wide_fwd(const float* agg, int lda, const float* W, cons
     const int ks = K <= 16 ? 8 : K <= 20 ? 10 : 16;
     // the single-pass 8-wave kernel when W fits the LDS next to nothing else ([2 ks][Fp] floats + 2 KB): one workgroup per CU
     // round 5: row norms from the K x K quadratic form, then one wave per 32 rows x 96 columns (see k_sage_wide_cols)
-    static const int use_cols = getenv("CGC_SAGE_WIDE_COLS") ? atoi(getenv("CGC_SAGE_WIDE_COLS")) : 1;
-    static const int cols_chunks = getenv("CGC_SAGE_WIDE_CHUNKS") ? atoi(getenv("CGC_SAGE_WIDE_CHUNKS")) : 256;
     // (small launches keep the one-kernel form: at 7200 rows -- a 4-graph shard -- two more launches cost more than the wave-level kernel saves)
-    static const int cols_min_rows = getenv("CGC_SAGE_WIDE_COLS_MIN") ? atoi(getenv("CGC_SAGE_WIDE_COLS_MIN")) : 12288;
-    if (use_cols && normalize && K <= 21 && n >= cols_min_rows && n >= 64 && (long long)n * ldh * 4 < (1LL << 31) && (reinterpret_cast<uintptr_t>(hn) & 7u) == 0 &&
+    constexpr int cols_chunks = 256, cols_min_rows = 12288;
+    if (normalize && K <= 21 && n >= cols_min_rows && (long long)n * ldh * 4 < (1LL << 31) && (reinterpret_cast<uintptr_t>(hn) & 7u) == 0 &&
         aligned16(rinv) && (size_t)n * ldh * 4 >= sizeof(double) * (size_t)(K * (K + 1) / 2 + K + 1) && ((long long)(n - 1) * lda + K) * 4 < (1LL << 31) &&
         // G is parked in the first bytes of hn and overwritten by the projection: with hn a column window of a wider buffer (ldh > F)
         // it must fit row 0's own F floats, or it would land in columns [F, ldh) that belong to the enclosing buffer
         (ldh == F || (size_t)F * 4 >= sizeof(double) * (size_t)(K * (K + 1) / 2 + K + 1))) {
-      int per = ceil_div(row_tiles, cols_chunks > 0 ? cols_chunks : 256);
+      int per = ceil_div(row_tiles, cols_chunks);
       int chunks = ceil_div(row_tiles, per);
       if (stats && chunks > cap) { chunks = cap > 0 ? cap : 1; }
       const int ngroups = ceil_div(ceil_div(F, 32), SWC_TILES);
@@ -716,10 +691,9 @@ extern "C" int cgc_sage_wide_fwd(const float* agg, int lda, const float* W, cons
       if (stats) return launch_stats_finalize(ws, chunks, F, count, eps, momentum, running_mean, running_var, mean, istd, num_batches_tracked, st);
       return 0;
     }
-    static const int use8 = getenv("CGC_SAGE_WIDE8") ? atoi(getenv("CGC_SAGE_WIDE8")) : 1;
     const int ntw8 = F <= 8 * 5 * 32 ? 5 : 7, Fp = 8 * ntw8 * 32;
     const size_t lds8 = sizeof(float) * ((size_t)2 * ks * Fp + 512 + 256);
-    if (use8 && F <= 8 * 7 * 32 && lds8 <= 156 * 1024 && n >= 64 && (long long)n * ldh * 4 < (1LL << 31)) {
+    if (F <= 8 * 7 * 32 && lds8 <= 156 * 1024 && n >= 64 && (long long)n * ldh * 4 < (1LL << 31)) {
       int wg8 = row_tiles < 256 ? row_tiles : 256;
       if (stats && wg8 > cap) wg8 = cap > 0 ? cap : 1;
 #define SW8_ONE(KS_, NTW_, ACT_)                                                                                                       \

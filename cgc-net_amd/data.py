@@ -117,8 +117,8 @@ class Batch(Data):
             ec = [int(d.edge_index.shape[1]) for d in data_list]
             out._eptr = torch.tensor([0] + list(np.cumsum(ec)), dtype=torch.int32)
             out._etotal, out._emax = int(sum(ec)), int(max(ec))
-        # every item says its nodes are listed grid cell by grid cell (spatial_order): the wide aggregation may stage neighbour unions
-        # of consecutive rows in LDS (graph.BatchGraph.spatial -> cgc_spmm_graphs visit bit 2)
+        # every item says its nodes are listed grid cell by grid cell (spatial_order): a note that travels on to the wide
+        # aggregation (graph.BatchGraph.spatial -> cgc_spmm_graphs visit bit 2); the node order itself is what speeds it up
         if all(getattr(d, '_spatial', False) for d in data_list):
             out._spatial = True
         return out

@@ -80,8 +80,7 @@ class BatchGraph(object):
         g = cls(x.shape[0], cls.node_counts_of(batch), x.device, getattr(batch, '_dense_rows', None), getattr(batch, '_gptr', None))
         # the nodes of every graph are listed grid cell by grid cell (data.spatial_order; the Batch says so).  What makes the wide
         # aggregation faster on such a batch is the node ORDER itself (the gather's re-reads hit nearer caches); the note only
-        # travels on as cgc_spmm_graphs' visit bit 2, which the default gather kernel ignores (it selects the experimental LDS-staged
-        # kernel under CGC_SPMM_PATCH=1).  Never about results.
+        # travels on as cgc_spmm_graphs' visit bit 2, which the gather kernel does not read.  Never about results.
         g.spatial = bool(getattr(batch, '_spatial', False))
         # the collate's note that the edge list is grouped by graph (Batch._eptr), if it still describes this edge_index
         eptr = getattr(batch, '_eptr', None)

@@ -74,7 +74,8 @@ class KernelSpec(object):
         with w_k = val[perm[k]] / val[k] / 1 and pre/post optional.  x, out: [n, width] contiguous.
         gptr/num_graphs/nmax (optional): the rows are a batch of graphs with block-diagonal adjacency
         (first row of each graph, count, largest graph) -- a layout hint, the result is the same.
-        visit (optional, scheduling hint): 1 = x was just written in ascending row order, 2 = by a ragged batched gemm.
+        visit (optional, scheduling hint, bits 0-1): 1 = x was just written in ascending row order, 2 = by a ragged batched gemm;
+        bit 2 (+4) notes that the nodes of every graph are listed grid cell by grid cell.  Higher bits are ignored.
         ld (optional): row stride of x and out when the rows are padded (wide rows only; needs gptr).
         gorder (optional, scheduling only): int32 [num_graphs] visiting sequence of the graphs (wide rows)."""
         raise NotImplementedError

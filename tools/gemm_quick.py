@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The dominant GEMM alone, on the step's flat shapes (58761 x 1140 x 1140, rows on 1152-float strides: the FAST 128 x 128 kernel),
-NN / NT / TN, each timed over a few launches after a long warm-up (the clock ramps over milliseconds).  CGC_LIB selects a variant
-library (tools/variant_lib.sh).  usage: python tools/gemm_quick.py [reps]"""
+NN / NT / TN, each timed over a few launches after a long warm-up (the clock ramps over milliseconds).  CGC_LIB selects another
+build of the library.  usage: python tools/gemm_quick.py [reps]"""
 import os
 import sys
 

@@ -10,7 +10,7 @@ route and prints, per product:
   * top-2 share: for 8192 sampled outputs (i, j), the share of sum_k |a_ik| |b_kj| carried by its two largest terms (median / 99th
     percentile / max).  N(0, 1) inputs at K = 1140: ~0.007; family 'skewk': ~1.0.
 
-GPU only.  Writes nothing; redirect stdout (tools/r06_measure.sh -> profiles/r06_operand_range_along_k.txt)."""
+GPU only.  Writes nothing; redirect stdout (profiles/r06_operand_range_along_k.txt was made so)."""
 import os
 import sys
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Time cgc_sage_wide_fwd (with statistics) at one shape and check it against the fp64 product.
-usage: sage_wide_bench.py [n K F reps]   env: CGC_SAGE_WIDE_COLS=0|1, CGC_SAGE_WIDE_CHUNKS=..."""
+usage: sage_wide_bench.py [n K F reps]"""
 import os
 import sys
 
@@ -53,7 +53,6 @@ nr = h.norm(dim=1, keepdim=True).clamp_min(1e-12)
 ref = h / nr
 o = torch.relu(ref)
 err = float((hn.double() - ref).abs().max())
-print('n %d K %d F %d: %.1f us per call [fill_: %.1f us] (%.2f TB/s of hn written)  max |hn - fp64| %.2e  rinv rel %.2e  mean %.2e  istd rel %.2e  [cols=%s chunks=%s]' % (
+print('n %d K %d F %d: %.1f us per call [fill_: %.1f us] (%.2f TB/s of hn written)  max |hn - fp64| %.2e  rinv rel %.2e  mean %.2e  istd rel %.2e' % (
     n, Kin, F, us, fill_us, n * F * 4 / us / 1e6, err, float((rinv.double() * nr[:, 0] - 1).abs().max()),
-    float((mean.double() - o.mean(0)).abs().max()), float((istd.double() * torch.sqrt(o.var(0, unbiased=False) + 1e-5) - 1).abs().max()),
-    os.environ.get('CGC_SAGE_WIDE_COLS', '1'), os.environ.get('CGC_SAGE_WIDE_CHUNKS', '256')))
+    float((mean.double() - o.mean(0)).abs().max()), float((istd.double() * torch.sqrt(o.var(0, unbiased=False) + 1e-5) - 1).abs().max())))

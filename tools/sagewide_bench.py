@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""cgc_sage_wide_fwd alone at the C3 shape ([57.7k, 20] -> [57.7k, 1140], statistics on): 20 launches back to back per sample, median of 5 samples (kernel + statistics finalize).  CGC_LIB selects a
-variant library (tools/variant_lib.sh).  GPU only."""
+"""cgc_sage_wide_fwd alone at the C3 shape ([57.7k, 20] -> [57.7k, 1140], statistics on): 20 launches back to back per sample, median of 5 samples (kernel + statistics finalize).  CGC_LIB selects
+another build of the library.  GPU only."""
 import os
 import sys
 

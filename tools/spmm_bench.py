@@ -60,6 +60,5 @@ for W in widths:
         after = sorted(tt[2:])[len(tt[2:]) // 2]
         by = 8.0 * n * W + 4.0 * (n + 1) + 4.0 * nnz
         print('%-24s n=%d nnz=%d W=%5d  %8.1f us  %7.1f GB/s algorithmic (%.1f%% of 8 TB/s); right after its producer '
-              '%.1f us (%.1f%%)  [env %s]' % (
-            name, n, nnz, W, ms * 1e3, by / ms / 1e6, by / ms / 1e6 / 80.0, after * 1e3, by / after / 1e6 / 80.0,
-            {k: v for k, v in os.environ.items() if k.startswith('CGC_SPMM')}))
+              '%.1f us (%.1f%%)' % (
+            name, n, nnz, W, ms * 1e3, by / ms / 1e6, by / ms / 1e6 / 80.0, after * 1e3, by / after / 1e6 / 80.0))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The thin level-2 products alone: [32 x 1140 x 1140] x [32 x 1140 x N], N = 20 / 40 / 114, NN and TN, automatic tile choice and
 forced configurations (cgc_gemm_tuning: 1..6 = 128x128, 128x64, 64x128, 64x64, 128x32, 32x128; +10 pipelined kernel).
-env CGC_GEMM_SPLIT=0 switches the tail split off (read once per process)."""
+To time them with the tail split off, set HipKernels.tail_split = False on the kernel table before the calls."""
 import os
 import sys
 
