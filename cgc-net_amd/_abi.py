@@ -3,7 +3,7 @@ import ctypes as C
 
 P, I, F, D, L = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_int64
 
-ABI_VERSION = 6      # = CGC_ABI_VERSION of include/cgc_hip.h these prototypes were written against (tests compare the two)
+ABI_VERSION = 7      # = CGC_ABI_VERSION of include/cgc_hip.h these prototypes were written against (tests compare the two)
 
 PROTOTYPES = {
     'cgc_abi_version': [],
@@ -91,6 +91,14 @@ PROTOTYPES = {
     'cgc_level_grad_layout_of': [P, P],
     'cgc_level_fwd': [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
     'cgc_level_bwd': [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
+    'cgc_level_fwd_reg': [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
+    'cgc_level_bwd_reg': [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
+    # DiffPool regularisers (csrc/diffpool_reg.hip)
+    'cgc_diffpool_reg_ws_floats': [],
+    'cgc_diffpool_reg_fwd': [P, I, I, I, P, P, I, P, L, P, D, D, P, P, P, P, P],
+    'cgc_diffpool_reg_bwd_prep': [P, P, D, D, P, P, P, P, I, I, P, P],
+    'cgc_diffpool_reg_entropy_bwd': [P, I, I, I, P, P, I, P],
+    'cgc_diffpool_reg_adj_bwd': [P, L, P, P, I, P],
 }
 
 

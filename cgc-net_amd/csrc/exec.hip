@@ -378,6 +378,9 @@ struct Level {
   bool dense, pool, tall;
   // saved arena
   float *At, *An, *invd, *ge1, *agg0, *pair[2], *xcat, *aggk[2], *hp3, *cat_e, *HS, *CS, *jk_out, *x12, *S, *P;
+  float *G, *keep;                // DiffPool regularisers (flags bit 3): G = S^T S [B, C, C], keep[0] = sqrt(T) (csrc/diffpool_reg.hip)
+  bool reg;
+  double reg_numel, reg_rows;     // B N N and B N, N = the dense padding (npad at level 1, the previous level's clusters after)
   int* arg;
   LayerS L[6];
   // gradient layout
@@ -401,6 +404,10 @@ struct Level {
     ldW = wide_ld(C);
     npad_jk = up(n > 1 ? n : 1, 1024);
     seg_nmax = dense ? R : d.npad;
+    reg = pool && (d.flags & 8);
+    const double N = dense ? R : d.npad;
+    reg_numel = (double)B * N * N;
+    reg_rows = (double)B * N;
     memset(&gl, 0, sizeof(gl));
   }
 
@@ -445,6 +452,11 @@ struct Level {
       x12 = a.f((size_t)n * 2 * AH);
       S = a.f((size_t)n * ldC);
       P = a.f((size_t)n * ldP);
+    }
+    G = keep = nullptr;
+    if (reg) {
+      G = a.f((size_t)B * C * C);
+      keep = a.f(4);
     }
   }
   int width_in(int k) const { return (k == 0 || k == 3) ? fin : (k < 3 ? H : AH); }
@@ -502,8 +514,31 @@ int aggregate_t(const Ctx& c, const Level& L, const cgc_graph* g, const int* gpt
   return bgemm(c, T3{L.An, L.B, L.R, L.R, L.R}, T3{const_cast<float*>(dy), L.B, L.R, w, ldy}, T3{dx, L.B, L.R, w, w}, 1, 0);
 }
 
+// DiffPool regularisers of the level (flags bit 3; csrc/diffpool_reg.hip): G = S^T S (the call shape of A' = S^T (A S)), then the
+// partial sums and reg_out = [link, ent]
+int reg_fwd(const Ctx& c, Level& L, const cgc_graph* g, const int* gptr, const float* A_in, const float* A_out, float* reg_out) {
+  const cgc_level_desc& d = L.d;
+  const int C = L.C, B = L.B;
+  if (!L.dense) {
+    TRY(gemm(c, 1, 0, C, C, 0, L.S, L.ldC, L.S, L.ldC, 0.f, L.G, C, nullptr, B, 0, 0, (int64_t)C * C, gptr, 2, d.nmax));
+  } else {
+    const T3 s3{L.S, B, L.R, C, L.ldC};
+    TRY(bgemm(c, s3, s3, T3{L.G, B, C, C, C}, 1, 0));
+  }
+  const size_t m = c.scratch->mark();
+  float* ws = c.scratch->f((size_t)cgc_diffpool_reg_ws_floats());
+  if (L.dense)
+    CALL(cgc_diffpool_reg_fwd(L.S, L.n, C, L.ldC, L.G, A_out, B, d.renorm ? L.At : A_in, (int64_t)L.n * L.R, nullptr, L.reg_numel, L.reg_rows,
+                              ws, reg_out, reg_out + 1, L.keep, c.s));
+  else
+    CALL(cgc_diffpool_reg_fwd(L.S, L.n, C, L.ldC, L.G, A_out, B, g->val, 0, g->rowptr, L.reg_numel, L.reg_rows, ws, reg_out, reg_out + 1,
+                              L.keep, c.s));
+  c.scratch->release(m);
+  return 0;
+}
+
 int level_fwd(const Ctx& c, Level& L, const cgc_block_params* emb, const cgc_block_params* pl, const cgc_jk_params* jk, const cgc_graph* g,
-              const int* gptr, const float* x_in, const float* A_in, float* readout, float* x_out, float* A_out) {
+              const int* gptr, const float* x_in, const float* A_in, float* readout, float* x_out, float* A_out, float* reg_out = nullptr) {
   const cgc_level_desc& d = L.d;
   const int n = L.n, H = L.H, AH = L.AH, wp = L.wp, C = L.C;
   if (L.dense)
@@ -582,6 +617,7 @@ int level_fwd(const Ctx& c, Level& L, const cgc_block_params* emb, const cgc_blo
     TRY(bgemm(c, a3, s3, p3, 0, 0));
     TRY(bgemm(c, s3, p3, T3{A_out, L.B, C, C, C}, 1, 0));
   }
+  if (L.reg) TRY(reg_fwd(c, L, g, gptr, A_in, A_out, reg_out));
   return 0;
 }
 
@@ -669,7 +705,7 @@ int level_bwd_blocks(const Ctx& c, Level& L, const cgc_block_params* emb, const 
 
 int level_bwd(const Ctx& c, Level& L, const cgc_block_params* emb, const cgc_block_params* pl, const cgc_jk_params* jk, const cgc_graph* g,
               const int* gptr, const float* x_in, const float* A_in, const float* d_readout, const float* d_xo, const float* d_ao, float* grads,
-              float* d_x_in, float* d_A_in) {
+              float* d_x_in, float* d_A_in, const float* d_reg = nullptr) {
   const cgc_level_desc& d = L.d;
   Arena& sc = *c.scratch;
   const int n = L.n, H = L.H, AH = L.AH, wp = L.wp, C = L.C, D = L.D, B = L.B, R = L.R;
@@ -677,6 +713,16 @@ int level_bwd(const Ctx& c, Level& L, const cgc_block_params* emb, const cgc_blo
   CALL(cgc_segment_max_bwd_full(d_readout, L.arg, gptr, B, D, L.seg_nmax, d_embed, c.s));
   float *dx12 = nullptr, *gAt = nullptr;
   if (L.pool) {
+    // DiffPool regularisers (flags bit 3): the link loss's -2 c_l (A + A^T) S term is the existing backward fed dA' - 2 c_l I (a
+    // copy: d_ao may be autograd's buffer); 4 c_l S G and the entropy term are added to dS below; at level 2, + 2 c_l A~ to d(A~)
+    float *Gs = nullptr, *coef = nullptr;
+    if (L.reg) {
+      float* dao = sc.f((size_t)B * C * C);
+      Gs = sc.f((size_t)B * C * C);
+      coef = sc.f(4);
+      CALL(cgc_diffpool_reg_bwd_prep(d_reg, L.keep, L.reg_numel, L.reg_rows, d_ao, dao, L.G, Gs, B, C, coef, c.s));
+      d_ao = dao;
+    }
     const size_t m0 = sc.mark();
     float* ds = sc.f((size_t)n * L.ldC);
     if (!L.dense) {
@@ -686,6 +732,7 @@ int level_bwd(const Ctx& c, Level& L, const cgc_block_params* emb, const cgc_blo
                                    c.s));                                                                                          // dS = A^T dP
       TRY(gemm_x1(c, 0, 1, 0, C, C, L.P, L.ldC, d_ao, C, 1.f, ds, L.ldC, nullptr, B, 0, (int64_t)C * C, 0, gptr, 1, d.nmax, L.embed(), D, 0, d_xo,
                   D, (int64_t)C * D, D));                                                                  // + P dA'^T + X dX'^T
+      if (L.reg) TRY(gemm(c, 0, 0, 0, C, C, L.S, L.ldC, Gs, C, 1.f, ds, L.ldC, nullptr, B, 0, (int64_t)C * C, 0, gptr, 1, d.nmax));   // + 4 c_l S G
       TRY(gemm(c, 0, 0, 0, D, C, L.S, L.ldC, d_xo, D, 1.f, d_embed, D, nullptr, B, 0, (int64_t)C * D, 0, gptr, 1, d.nmax));     // dX += S dX'
     } else {
       // (allocated below ds / de on purpose: it outlives them -- see the release further down)
@@ -701,7 +748,12 @@ int level_bwd(const Ctx& c, Level& L, const cgc_block_params* emb, const cgc_blo
       TRY(bgemm(c, a3, dP3, ds3, 1, 0, 1.f));                 // dS += A~^T dP
       TRY(bgemm(c, e3, dxo, ds3, 0, 1, 1.f));                 // dS += X dX'^T
       TRY(bgemm(c, s3, dxo, T3{d_embed, B, R, D, D}, 0, 0, 1.f));   // dX += S dX'
+      if (L.reg) {
+        TRY(bgemm(c, s3, T3{Gs, B, C, C, C}, ds3, 0, 0, 1.f));                        // dS += 4 c_l S G
+        CALL(cgc_diffpool_reg_adj_bwd(a3.p, (int64_t)n * R, coef, gAt, 1, c.s));     // d(A~) += 2 c_l A~
+      }
     }
+    if (L.reg) CALL(cgc_diffpool_reg_entropy_bwd(L.S, n, C, L.ldC, coef, ds, L.ldC, c.s));
     // Linear over cat + softmax backward (ops._LinearCat.backward)
     float* dz = sc.f((size_t)n * L.ldC);
     {
@@ -743,7 +795,8 @@ extern "C" int cgc_level_supported(const cgc_level_desc* d) {
   if (d->level == 1 && (d->nmax < 1 || d->npad < d->nmax)) return 0;
   if (d->C > 0 && (d->AH < 1 || d->H + d->AH > 256 || (2 * d->AH) % 4 != 0)) return 0;
   if (d->C == 0 && d->level == 1) return 0;
-  if ((d->flags & ~6) || (d->flags & 6) == 6) return 0;                   // bit 0 is reserved (ABI 4), bits 1 and 2 exclude each other, bits above 2 are unassigned
+  if ((d->flags & ~14) || (d->flags & 6) == 6) return 0;                  // bit 0 is reserved (ABI 4), bits 1 and 2 exclude each other, bits above 3 are unassigned
+  if ((d->flags & 8) && d->C == 0) return 0;                              // DiffPool regularisers: only where the level pools
   if (d->jk && (d->E != d->H || !cgc_jk_matrix_core(d->H))) return 0;   // (other channel counts: staged parameter gradients, per-operator path)
   return 1;
 }
@@ -789,11 +842,13 @@ extern "C" int64_t cgc_level_scratch_floats(const cgc_level_desc* d) {
   return (int64_t)high + 64;
 }
 
-extern "C" int cgc_level_fwd(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
-                             const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, float* saved, float* scratch,
-                             float* readout, float* x_out, float* A_out, const float** assign_out, int* assign_ld, cgc_stream_t stream) {
+extern "C" int cgc_level_fwd_reg(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
+                                 const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, float* saved, float* scratch,
+                                 float* readout, float* x_out, float* A_out, const float** assign_out, int* assign_ld, float* reg_out,
+                                 cgc_stream_t stream) {
   if (!cgc_level_supported(d) || saved == nullptr || scratch == nullptr) return CGC_EINVAL;
   if (!aligned16(saved) || !aligned16(scratch)) return CGC_EINVAL;
+  if ((d->flags & 8) && reg_out == nullptr) return CGC_EINVAL;
   Level L(*d);
   Arena sv(saved), sc(scratch);
   L.layout_saved(sv);
@@ -801,18 +856,25 @@ extern "C" int cgc_level_fwd(const cgc_level_desc* d, const cgc_block_params* em
   Ctx c{stream, false, &sc, nullptr, cgc_gemm_ws_floats()};
   c.gws = sc.f((size_t)c.gws_floats);
   c.gemm_mode = (d->flags & 2) ? CGC_GEMM_SPLIT_BF16 : (d->flags & 4) ? CGC_GEMM_SPLIT_F16 : CGC_GEMM_EXACT;
-  const int rc = level_fwd(c, L, emb, pool, jk, g, gptr, x_in, A_in, readout, x_out, A_out);
+  const int rc = level_fwd(c, L, emb, pool, jk, g, gptr, x_in, A_in, readout, x_out, A_out, reg_out);
   if (assign_out != nullptr) *assign_out = L.S;
   if (assign_ld != nullptr) *assign_ld = L.ldC;
   return rc;
 }
 
-extern "C" int cgc_level_bwd(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
-                             const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, const float* saved, float* scratch,
-                             const float* d_readout, const float* d_x_out, const float* d_A_out, float* grads, float* d_x_in, float* d_A_in,
-                             cgc_stream_t stream) {
+extern "C" int cgc_level_fwd(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
+                             const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, float* saved, float* scratch,
+                             float* readout, float* x_out, float* A_out, const float** assign_out, int* assign_ld, cgc_stream_t stream) {
+  return cgc_level_fwd_reg(d, emb, pool, jk, g, gptr, x_in, A_in, saved, scratch, readout, x_out, A_out, assign_out, assign_ld, nullptr, stream);
+}
+
+extern "C" int cgc_level_bwd_reg(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
+                                 const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, const float* saved, float* scratch,
+                                 const float* d_readout, const float* d_x_out, const float* d_A_out, const float* d_reg, float* grads,
+                                 float* d_x_in, float* d_A_in, cgc_stream_t stream) {
   if (!cgc_level_supported(d) || saved == nullptr || scratch == nullptr || grads == nullptr || d->eval) return CGC_EINVAL;
   if (!aligned16(saved) || !aligned16(scratch) || !aligned16(grads)) return CGC_EINVAL;
+  if ((d->flags & 8) && d_reg == nullptr) return CGC_EINVAL;
   Level L(*d);
   Arena sv(const_cast<float*>(saved)), sc(scratch);
   L.layout_saved(sv);
@@ -820,5 +882,13 @@ extern "C" int cgc_level_bwd(const cgc_level_desc* d, const cgc_block_params* em
   Ctx c{stream, false, &sc, nullptr, cgc_gemm_ws_floats()};
   c.gws = sc.f((size_t)c.gws_floats);
   c.gemm_mode = (d->flags & 2) ? CGC_GEMM_SPLIT_BF16 : (d->flags & 4) ? CGC_GEMM_SPLIT_F16 : CGC_GEMM_EXACT;
-  return level_bwd(c, L, emb, pool, jk, g, gptr, x_in, A_in, d_readout, d_x_out, d_A_out, grads, d_x_in, d_A_in);
+  return level_bwd(c, L, emb, pool, jk, g, gptr, x_in, A_in, d_readout, d_x_out, d_A_out, grads, d_x_in, d_A_in, d_reg);
+}
+
+extern "C" int cgc_level_bwd(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
+                             const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, const float* saved, float* scratch,
+                             const float* d_readout, const float* d_x_out, const float* d_A_out, float* grads, float* d_x_in, float* d_A_in,
+                             cgc_stream_t stream) {
+  return cgc_level_bwd_reg(d, emb, pool, jk, g, gptr, x_in, A_in, saved, scratch, d_readout, d_x_out, d_A_out, nullptr, grads, d_x_in, d_A_in,
+                           stream);
 }

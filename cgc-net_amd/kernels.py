@@ -228,6 +228,24 @@ class KernelSpec(object):
         """dAt = dense_rownorm_bwd(gAn) + gAt (gAt may be None); dA = dense_renorm_bwd(A, dAt) (dA = dAt when p is None)."""
         raise NotImplementedError
 
+    # ------------------------------------------------------------------ DiffPool regularisers (csrc/diffpool_reg.hip)
+    def diffpool_reg_fwd(self, S, n, C, lds, G, A_out, B, A, A_numel, rowptr, numel, rows, link_out, ent_out, keep_out):
+        """link = sqrt(||A||^2 - 2 sum_b tr(A_out_b) + ||G||^2) / numel, ent = sum -S log(S + 1e-15) / rows (0-dim outputs);
+        keep[0] = the square root.  A: dense [A_numel] (rowptr None) or the CSR values of rowptr (None: all ones)."""
+        raise NotImplementedError
+
+    def diffpool_reg_bwd_prep(self, d_reg, keep, numel, rows, d_ao, dao_out, G, Gs_out, B, C, coef_out):
+        """coef = [c_l, c_e] from the upstream gradients d_reg [2]; dao = d_ao (None: 0) - 2 c_l I per graph; Gs = 4 c_l G."""
+        raise NotImplementedError
+
+    def diffpool_reg_entropy_bwd(self, S, n, C, lds, coef, ds, ldd):
+        """ds[:, :C] += c_e (-log(S + 1e-15) - S / (S + 1e-15))."""
+        raise NotImplementedError
+
+    def diffpool_reg_adj_bwd(self, A, m, coef, gA, accumulate):
+        """gA (+)= 2 c_l A over m elements."""
+        raise NotImplementedError
+
 
 # ----------------------------------------------------------------------------------------------
 _LIB_NAME = 'libcgc_hip.so'
@@ -771,3 +789,26 @@ class HipKernels(KernelSpec):
         self._dev(A, An, invd, ge1, gAn, gAt, dA_out)
         self._chk(self.lib.cgc_adj_prep_bwd(_ptr(A), _ptr(An), _ptr(invd), _ptr(ge1), _ptr(gAn), _ptr(gAt), R, C,
                                             ctypes.c_float(-1.0 if p is None else p), _ptr(dA_out), self._stream()), 'cgc_adj_prep_bwd')
+
+    def diffpool_reg_fwd(self, S, n, C, lds, G, A_out, B, A, A_numel, rowptr, numel, rows, link_out, ent_out, keep_out):
+        self._dev(S, G, A_out, A, rowptr, link_out, ent_out, keep_out)
+        ws = torch.empty(int(self.lib.cgc_diffpool_reg_ws_floats()), dtype=torch.float32, device=S.device)
+        self._chk(self.lib.cgc_diffpool_reg_fwd(_ptr(S), n, C, lds, _ptr(G), _ptr(A_out), B, _ptr(A), A_numel, _ptr(rowptr),
+                                                float(numel), float(rows), _ptr(ws), _ptr(link_out), _ptr(ent_out), _ptr(keep_out),
+                                                self._stream()), 'cgc_diffpool_reg_fwd')
+
+    def diffpool_reg_bwd_prep(self, d_reg, keep, numel, rows, d_ao, dao_out, G, Gs_out, B, C, coef_out):
+        self._dev(d_reg, keep, d_ao, dao_out, G, Gs_out, coef_out)
+        self._chk(self.lib.cgc_diffpool_reg_bwd_prep(_ptr(d_reg), _ptr(keep), float(numel), float(rows), _ptr(d_ao), _ptr(dao_out),
+                                                     _ptr(G), _ptr(Gs_out), B, C, _ptr(coef_out), self._stream()),
+                  'cgc_diffpool_reg_bwd_prep')
+
+    def diffpool_reg_entropy_bwd(self, S, n, C, lds, coef, ds, ldd):
+        self._dev(S, coef, ds)
+        self._chk(self.lib.cgc_diffpool_reg_entropy_bwd(_ptr(S), n, C, lds, _ptr(coef), _ptr(ds), ldd, self._stream()),
+                  'cgc_diffpool_reg_entropy_bwd')
+
+    def diffpool_reg_adj_bwd(self, A, m, coef, gA, accumulate):
+        self._dev(A, coef, gA)
+        self._chk(self.lib.cgc_diffpool_reg_adj_bwd(_ptr(A), m, _ptr(coef), _ptr(gA), int(accumulate), self._stream()),
+                  'cgc_diffpool_reg_adj_bwd')

@@ -126,7 +126,7 @@ def prepared(enc, level, emb, pool, jk, fin):
                    for b in blocks if b.use_bn for k in (1, 2, 3))
     modes = (enc.training,) + tuple(m.training for b in blocks for m in _mode_modules(b))
     key = (tuple(id(t) for t in params), tuple(t.data_ptr() for t in params if t is not None), modes, enc.norm_adj, fin, bn_cfg,
-           emb.activation, int(getattr(enc, 'gemm_mode', 0)))
+           emb.activation, int(getattr(enc, 'gemm_mode', 0)), bool(getattr(enc, 'diffpool_loss', False)))
     cache = enc.__dict__.setdefault('_native_prepared', {})
     hit = cache.get(level)
     if hit is not None and hit[0] == key:
@@ -189,6 +189,8 @@ def describe(enc, level, emb, pool, jk, B, n, rows_per_graph, nmax, npad, fin, c
     d.renorm, d.renorm_p = int(enc.norm_adj), float(RENORM_P)
     d.eval = int(not enc.training)
     d.flags = {0: 0, 1: 2, 2: 4}[int(getattr(enc, 'gemm_mode', 0))]      # bit 1: six bf16 pairs, bit 2: three fp16 pairs (bit 0 is reserved: include/cgc_hip.h)
+    if pool is not None and getattr(enc, 'diffpool_loss', False):
+        d.flags |= REG_FLAG
     for b_i, blk in enumerate(blocks):
         if blk.use_bn:
             for k in range(3):
@@ -204,6 +206,11 @@ def describe(enc, level, emb, pool, jk, B, n, rows_per_graph, nmax, npad, fin, c
 
 
 RENORM_P = 0.4      # model/network.py:260,271,280
+REG_FLAG = 8        # cgc_level_desc.flags bit 3: the level also yields the DiffPool regularisers (link, entropy)
+
+
+def has_reg(d):
+    return bool(d.flags & REG_FLAG)
 
 
 _SIZES = {}
@@ -249,8 +256,9 @@ class _Level(Function):
             gs.val, gs.t_val, gs.inv_d, gs.gorder = _p(g.val), _p(g.t_val), _p(g.inv_d), _p(g.gorder)
             gs.spatial = int(bool(getattr(g, 'spatial', False)))
         s_ptr, s_ld = P(), I()
-        rc = lib.cgc_level_fwd(C.byref(d), C.byref(pe), C.byref(pp), C.byref(pj), C.byref(gs), _p(gptr), _p(x_in), _p(A_in), _p(saved),
-                               _p(scratch), _p(readout), _p(x_out), _p(A_out), C.byref(s_ptr), C.byref(s_ld), stream)
+        reg = torch.empty(2, dtype=torch.float32, device=dev) if has_reg(d) else None
+        rc = lib.cgc_level_fwd_reg(C.byref(d), C.byref(pe), C.byref(pp), C.byref(pj), C.byref(gs), _p(gptr), _p(x_in), _p(A_in), _p(saved),
+                                   _p(scratch), _p(readout), _p(x_out), _p(A_out), C.byref(s_ptr), C.byref(s_ld), _p(reg), stream)
         if rc != 0:
             raise RuntimeError('cgc_level_fwd failed with code %d' % rc)
         if cfg.get('assign') is not None and d.C:
@@ -260,12 +268,14 @@ class _Level(Function):
         ctx.save_for_backward(x_in, A_in, saved, *[p for p in params if p is not None])
         ctx.mask = [p is not None for p in params]
         ctx.shapes = [tuple(p.shape) if p is not None else None for p in params]
+        if reg is not None:          # (link, ent): 0-dim outputs of their own
+            return readout, x_out, A_out, reg[0].clone(), reg[1].clone()
         if d.C:
             return readout, x_out, A_out
         return readout
 
     @staticmethod
-    def backward(ctx, d_readout, d_x_out=None, d_A_out=None):
+    def backward(ctx, d_readout, d_x_out=None, d_A_out=None, d_link=None, d_ent=None):
         lib = _lib()
         cfg = ctx.cfg
         d, g, gptr = cfg['desc'], cfg['graph'], cfg['gptr']
@@ -284,8 +294,12 @@ class _Level(Function):
         dense = d.level >= 2
         d_x_in = torch.empty_like(x_in) if dense else None
         d_A_in = torch.empty_like(A_in) if dense else None
-        rc = lib.cgc_level_bwd(C.byref(d), C.byref(pe), C.byref(pp), C.byref(pj), C.byref(gs), _p(gptr), _p(x_in), _p(A_in), _p(saved),
-                               _p(scratch), _p(d_readout), _p(d_x_out), _p(d_A_out), _p(grads), _p(d_x_in), _p(d_A_in), stream)
+        d_reg = None
+        if has_reg(d):               # a loss that does not reach the objective has gradient zero
+            zero = torch.zeros((), dtype=torch.float32, device=dev)
+            d_reg = torch.stack([zero if d_link is None else d_link.float(), zero if d_ent is None else d_ent.float()])
+        rc = lib.cgc_level_bwd_reg(C.byref(d), C.byref(pe), C.byref(pp), C.byref(pj), C.byref(gs), _p(gptr), _p(x_in), _p(A_in), _p(saved),
+                                   _p(scratch), _p(d_readout), _p(d_x_out), _p(d_A_out), _p(d_reg), _p(grads), _p(d_x_in), _p(d_A_in), stream)
         if rc != 0:
             raise RuntimeError('cgc_level_bwd failed with code %d' % rc)
         owner = cfg.get('owner')
@@ -327,7 +341,8 @@ def _param_offsets(d, lay):
 
 
 def level(enc, desc, emb, pool, jk, g, gptr, x_in, A_in, assign=None, prep=None):
-    """Run one level through the sequencer.  Returns (readout, x_out, A_out) (x_out / A_out None at the last level)."""
+    """Run one level through the sequencer.  Returns (readout, x_out, A_out) (x_out / A_out None at the last level), and the 0-dim
+    (link, ent) after them when desc has the regulariser bit (REG_FLAG)."""
     cfg = dict(desc=desc, emb=emb, pool=pool, jk=jk, graph=g, gptr=gptr, assign=assign, structs=prep['structs'] if prep else None,
                owner=enc)
     params = prep['params'] if prep else (_block_tensors(emb) + (_block_tensors(pool) if pool is not None else []) +
@@ -341,7 +356,7 @@ def level(enc, desc, emb, pool, jk, g, gptr, x_in, A_in, assign=None, prep=None)
 
 def level_eval(enc, desc, emb, pool, jk, g, gptr, x_in, A_in, assign=None, prep=None):
     """Inference forward of one level through the sequencer (desc.eval = 1: BatchNorm on its running statistics, nothing kept): no
-    autograd node, two arenas that die with the call.  Returns (readout, x_out, A_out).  evaluate() (train.py:21-91) runs on this."""
+    autograd node, two arenas that die with the call.  Returns (readout, x_out, A_out) (+ (link, ent) as level()).  evaluate() (train.py:21-91) runs on this."""
     lib = _lib()
     K = kernels.get()
     d = desc
@@ -361,13 +376,16 @@ def level_eval(enc, desc, emb, pool, jk, g, gptr, x_in, A_in, assign=None, prep=
         gs.val, gs.t_val, gs.inv_d, gs.gorder = _p(g.val), _p(g.t_val), _p(g.inv_d), _p(g.gorder)
         gs.spatial = int(bool(getattr(g, 'spatial', False)))
     s_ptr, s_ld = P(), I()
-    rc = lib.cgc_level_fwd(C.byref(d), C.byref(pe), C.byref(pp), C.byref(pj), C.byref(gs), _p(gptr), _p(x_in), _p(A_in), _p(saved),
-                           _p(scratch), _p(readout), _p(x_out), _p(A_out), C.byref(s_ptr), C.byref(s_ld), K._stream())
+    reg = torch.empty(2, dtype=torch.float32, device=dev) if has_reg(d) else None
+    rc = lib.cgc_level_fwd_reg(C.byref(d), C.byref(pe), C.byref(pp), C.byref(pj), C.byref(gs), _p(gptr), _p(x_in), _p(A_in), _p(saved),
+                               _p(scratch), _p(readout), _p(x_out), _p(A_out), C.byref(s_ptr), C.byref(s_ld), _p(reg), K._stream())
     if rc != 0:
         raise RuntimeError('cgc_level_fwd (inference) failed with code %d' % rc)
     if assign is not None and d.C:
         off = (s_ptr.value - saved.data_ptr()) // 4
         assign.append(torch.as_strided(saved, (d.n, d.C), (s_ld.value, 1), off).clone())
+    if reg is not None:
+        return readout, x_out, A_out, reg[0], reg[1]
     return readout, x_out, A_out
 
 

@@ -306,13 +306,20 @@ def _pairable(emb, pool):
 class SoftPoolingGcnEncoder(nn.Module):
     """model/network.py:127-291.  ``forward(data)`` takes a Batch-like object (``.x .edge_index .batch .y``)
     when ``load_data_sparse`` else the tuple ``(x[B,N,F], adj[B,N,N], num_nodes[B][, label])``; returns
-    ``(logits, loss)`` in training mode and ``logits`` in eval mode."""
+    ``(logits, loss)`` in training mode and ``logits`` in eval mode.
+
+    ``diffpool_loss`` (not in the reference; a plain attribute that may be switched at any time): every forward also fills
+    ``link_loss`` and ``ent_loss``, lists [level 1, level 2] of 0-dim tensors -- the link-prediction and entropy regularisers of
+    PyG's ``dense_diff_pool`` for the two pooling stages, connected to autograd when grad is enabled.  Typical use:
+    ``loss = cls_loss + sum(model.link_loss) + sum(model.ent_loss)``.  Off: both lists stay empty."""
 
     def __init__(self, max_num_nodes, input_dim, hidden_dim, embedding_dim, bias, bn, assign_hidden_dim, label_dim,
                  assign_ratio=0.25, pred_hidden_dims=[50], concat=True, gcn_name='SAGE',
                  collect_assign=False, load_data_sparse=False, norm_adj=False,
-                 activation='relu', drop_out=0., jk=False):
+                 activation='relu', drop_out=0., jk=False, diffpool_loss=False):
         super().__init__()
+        self.diffpool_loss = bool(diffpool_loss)
+        self.link_loss, self.ent_loss = [], []
         self.jk, self.drop_out, self.norm_adj = jk, drop_out, norm_adj
         self.load_data_sparse, self.collect_assign = load_data_sparse, collect_assign
         self.assign_matrix = []
@@ -360,6 +367,7 @@ class SoftPoolingGcnEncoder(nn.Module):
         for k in native.TRANSIENT + ('last_graph',):
             state.pop(k, None)
         state['last_graph'] = None
+        state['link_loss'], state['ent_loss'] = [], []        # (one forward's autograd-connected values)
         return state
 
     def build_readout_module(self, pred_input_dim, pred_hidden_dims, label_dim, activation):
@@ -442,6 +450,9 @@ class SoftPoolingGcnEncoder(nn.Module):
             out = native.level(self, desc, emb, pool, jk, g, gptr, x.contiguous(), adj, assign, prep)
         else:
             out = native.level_eval(self, desc, emb, pool, jk, g, gptr, x.contiguous(), adj, assign, prep)
+        if native.has_reg(desc):
+            self._add_reg(*out[3:])
+            out = out[:3]
         if assign:
             s = assign[0]
             self.assign_matrix.append(self._pad_assign(s, g) if level == 1 else s.view(desc.B, desc.rows_per_graph, -1))
@@ -505,7 +516,13 @@ class SoftPoolingGcnEncoder(nn.Module):
         if self.collect_assign:
             self.assign_matrix.append(self._pad_assign(s.detach(), g))
         xn, an = ops.diff_pool_sparse(embed, s, g)
+        if getattr(self, 'diffpool_loss', False):
+            self._add_reg(*ops.diffpool_reg_sparse(s, an, g))
         return readout, xn, an
+
+    def _add_reg(self, link, ent):
+        self.link_loss.append(link)
+        self.ent_loss.append(ent)
 
     def _pad_assign(self, s, g):
         """[Ntot, C] -> the reference's [B, Nmax, C]; its padded rows hold softmax(0) = 1/C.  Rows return to the caller's node order."""
@@ -530,12 +547,16 @@ class SoftPoolingGcnEncoder(nn.Module):
                 adj = ops.renorm_dense(adj, RENORM_P)
             a = adj
         shared = ops.SharedGrad() if (torch.is_grad_enabled() and a.requires_grad) else None   # one d(adjacency) buffer per level
+        pool_blk = getattr(self, 'GCN_pool_%d' % level) if level < 3 else None
+        if pool_blk is not None and getattr(self, 'diffpool_loss', False) and not _pairable(emb_blk, pool_blk):
+            # the regularisers alone reach only the assignment block's aggregations, and SharedGrad's deferred product waits for every
+            # registered one: separately aggregating blocks (GIN) report their adjacency gradients one by one instead
+            shared = None
 
         def aggregate(h):
             return ops.bmatmul(a, h.view(B, C, -1), shared=shared).view(B * C, -1)
         xf = x.reshape(B * C, -1)
         agg0 = aggregate(xf)
-        pool_blk = getattr(self, 'GCN_pool_%d' % level) if level < 3 else None
         outs_p = None
         if pool_blk is not None and _pairable(emb_blk, pool_blk):
             outs_e, outs_p = run_blocks_paired(emb_blk, pool_blk, xf, aggregate, B * C, agg0)
@@ -551,6 +572,8 @@ class SoftPoolingGcnEncoder(nn.Module):
         if self.collect_assign:
             self.assign_matrix.append(s.detach().view(B, C, -1))
         xn, an = ops.diff_pool_dense(embed.view(B, C, -1), adj, s.view(B, C, -1))
+        if getattr(self, 'diffpool_loss', False):
+            self._add_reg(*ops.diffpool_reg_dense(s, an, adj))
         return readout, xn, an
 
     def _dense_levels(self, x, adj):
@@ -573,6 +596,7 @@ class SoftPoolingGcnEncoder(nn.Module):
 
     def _forward(self, data):
         self.assign_matrix = []
+        self.link_loss, self.ent_loss = [], []
         if self.load_data_sparse:
             label = data.y
         else:

@@ -785,6 +785,75 @@ def diff_pool_dense(embed, adj, s):
 
 
 # ----------------------------------------------------------------------------------------------
+# DiffPool regularisers: PyG dense_diff_pool's link and entropy losses of one pooling stage (csrc/diffpool_reg.hip)
+# ----------------------------------------------------------------------------------------------
+class _DiffPoolReg(Function):
+    """(link, ent) from the stage's assignment S [n, C], its pooled adjacency A' = S^T A S [B, C, C] and its adjacency A: the CSR of
+    ``g`` at level 1 (``adj`` None), the dense A~ [B, R, R] after.  link = sqrt(||A||^2 - 2 tr A' + ||S^T S||^2) / numel.
+    Backward: dS = 4 c_l S G + c_e (-log(S + eps) - S / (S + eps)), dA' = -2 c_l I per graph (the diff_pool node turns it into
+    -2 c_l (A + A^T) S and, at a dense level, -2 c_l S S^T for A~), dA~ = 2 c_l A~."""
+
+    @staticmethod
+    def forward(ctx, s, ao, adj, g, B, R, numel, rows):
+        s, ld = _rows_ld(s)
+        n, c = s.shape
+        dev = s.device
+        ao = _f32c(ao)
+        G = torch.empty(B, c, c, dtype=torch.float32, device=dev)
+        link = torch.empty((), dtype=torch.float32, device=dev)
+        ent = torch.empty((), dtype=torch.float32, device=dev)
+        keep = torch.empty(4, dtype=torch.float32, device=dev)
+        if g is not None:       # G = S^T S: the call shape of A' = S^T (A S) (diff_pool_sparse)
+            K().gemm(s, s, G, c, c, 0, True, False, ld, ld, c, 1.0, 0.0, None, g.B, 0, 0, c * c, g.gptr, 2, g.nmax, n)
+            K().diffpool_reg_fwd(s, n, c, ld, G, ao, B, g.val, 0, g.rowptr, numel, rows, link, ent, keep)
+        else:
+            adj = _f32c(adj)
+            s3 = s.as_strided((B, R, c), (R * ld, ld, 1))
+            _bgemm(s3, s3, G, True, False)
+            K().diffpool_reg_fwd(s, n, c, ld, G, ao, B, adj, adj.numel(), None, numel, rows, link, ent, keep)
+        ctx.save_for_backward(s, G, keep, adj)
+        ctx.g, ctx.dims = g, (B, R, ld, numel, rows)
+        return link, ent
+
+    @staticmethod
+    def backward(ctx, d_link, d_ent):
+        s, G, keep, adj = ctx.saved_tensors
+        g = ctx.g
+        B, R, ld, numel, rows = ctx.dims
+        n, c = s.shape
+        dev = s.device
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        d_reg = torch.stack([zero if d_link is None else d_link.float(), zero if d_ent is None else d_ent.float()])
+        dao = torch.empty(B, c, c, dtype=torch.float32, device=dev)
+        Gs = torch.empty_like(G)
+        coef = torch.empty(4, dtype=torch.float32, device=dev)
+        K().diffpool_reg_bwd_prep(d_reg, keep, numel, rows, None, dao, G, Gs, B, c, coef)
+        ds = torch.empty(n, c, dtype=torch.float32, device=dev) if ld == c else _window(torch.empty(n, ld, dtype=torch.float32, device=dev), 0, c)
+        if g is not None:       # 4 c_l S G: the call shape of dP = S dA'
+            K().gemm(s, Gs, ds, 0, c, c, False, False, ld, c, ld, 1.0, 0.0, None, g.B, 0, c * c, 0, g.gptr, 1, g.nmax, n)
+        else:
+            _bgemm(s.as_strided((B, R, c), (R * ld, ld, 1)), Gs, ds.as_strided((B, R, c), (R * ld, ld, 1)), False, False)
+        K().diffpool_reg_entropy_bwd(s, n, c, ld, coef, ds, ld)
+        dadj = None
+        if adj is not None and ctx.needs_input_grad[2]:
+            dadj = torch.empty_like(adj)
+            K().diffpool_reg_adj_bwd(adj, adj.numel(), coef, dadj, 0)
+        return ds, dao, dadj, None, None, None, None, None
+
+
+def diffpool_reg_sparse(s, ao, g):
+    """(link, ent) of the level-1 pooling: S [Ntot, C], A' [B, C, C], the CSR of ``g`` (values g.val; None = ones); the dense padding
+    is g.npad (numel = B npad^2, rows = B npad: the padded rows have s = 0 and only count)."""
+    return _DiffPoolReg.apply(s, ao, None, g, g.B, g.npad, float(g.B) * g.npad * g.npad, float(g.padded_rows))
+
+
+def diffpool_reg_dense(s, ao, adj):
+    """(link, ent) of a dense level's pooling: S [B R, C], A' [B, C, C], A~ [B, R, R]."""
+    B, R, _ = adj.shape
+    return _DiffPoolReg.apply(s, ao, adj, None, B, R, float(B) * R * R, float(B) * R)
+
+
+# ----------------------------------------------------------------------------------------------
 # dense adjacency transforms with gradient (levels 2-3)
 # ----------------------------------------------------------------------------------------------
 class _RowNormClamp(Function):

@@ -49,6 +49,8 @@ def main():
     ap.add_argument('--plain', action='store_true', help='without --jk --norm_adj --drop 0.2')
     ap.add_argument('--optim', choices=['adam', 'sgd', 'rmsprop'], default=None,
                     help="the reference's --optim through cgc_net_amd.optim.init_optim (one-launch update); default: torch.optim.Adam")
+    ap.add_argument('--diffpool-loss', action='store_true',
+                    help="add PyG dense_diff_pool's link-prediction and entropy regularisers of both pooling stages to the loss")
     args = ap.parse_args()
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -67,7 +69,7 @@ def main():
     torch.manual_seed(0)
     flags = dict() if args.plain else dict(norm_adj=True, jk=True, drop_out=0.2)
     model = network.SoftPoolingGcnEncoder(args.max_num_nodes, 16, 20, 20, True, True, 20, 3, 0.1, [50], concat=True,
-                                          gcn_name='SAGE', load_data_sparse=True, **flags)
+                                          gcn_name='SAGE', load_data_sparse=True, diffpool_loss=args.diffpool_loss, **flags)
     model = DataParallel(model.to(device))
     if args.optim is None:
         optimizer = torch.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-4)
@@ -82,6 +84,8 @@ def main():
         for batch_idx, data in enumerate(train_loader):
             _, cls_loss = model(data)
             loss = torch.mean(cls_loss)
+            if args.diffpool_loss:                 # this rank's module holds its own lists (no cross-rank averaging of the values)
+                loss = loss + sum(model.module.link_loss) + sum(model.module.ent_loss)
             optimizer.zero_grad()
             loss.backward()
             optimizer.step()

@@ -46,8 +46,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *      adjacency gradient; a descriptor with bit 0 set is refused.  Added: cgc_graph_build_local, cgc_graph_local_max_nodes)
  *   5: round 6 (mode CGC_GEMM_SPLIT_F16 of cgc_gemm_f32_ws / cgc_gemm_f32_cat_ws; cgc_level_desc.flags bit 2; cgc_gemm_half_count, cgc_gemm_half_ws_floats, cgc_gemm_half_min_work;
  *      cgc_gemm_ws_floats() grew by the mode's scale slots: workspaces sized by an older library are too small for the tail split)
- *   6: added cgc_sgd_step, cgc_rmsprop_step (one-launch SGD and RMSprop on the tables of cgc_adam_step) */
-#define CGC_ABI_VERSION 6
+ *   6: added cgc_sgd_step, cgc_rmsprop_step (one-launch SGD and RMSprop on the tables of cgc_adam_step)
+ *   7: DiffPool regularisers: cgc_level_desc.flags bit 3, cgc_level_fwd_reg, cgc_level_bwd_reg, cgc_diffpool_reg_ws_floats,
+ *      cgc_diffpool_reg_fwd, cgc_diffpool_reg_bwd_prep, cgc_diffpool_reg_entropy_bwd, cgc_diffpool_reg_adj_bwd */
+#define CGC_ABI_VERSION 7
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -409,7 +411,11 @@ typedef struct {
   int flags;              /* bit 0: reserved, must be 0 (rounds 4-5: an opt-in thin-operand form of the dense levels' adjacency gradient;
                            * it missed the 1e-4 gradient bar on two reference fixtures and was removed with ABI 4 -- DESIGN.md section 8);
                            * bit 1: the level's products run with mode CGC_GEMM_SPLIT_BF16 (cgc_gemm_f32_ws): those on the 128 x 128
-                           * route as six bf16 MFMA pairs per fp32 product.  Off by default */
+                           * route as six bf16 MFMA pairs per fp32 product.  Off by default;
+                           * bit 2: the same with mode CGC_GEMM_SPLIT_F16 (three fp16 pairs); bits 1 and 2 exclude each other;
+                           * bit 3: DiffPool regularisers (link and entropy losses of the level's pooling: cgc_diffpool_reg_fwd below).
+                           * Only on a level with an assignment block; needs cgc_level_fwd_reg / cgc_level_bwd_reg (the plain calls
+                           * refuse it).  Bits above 3 are unassigned and refused */
 } cgc_level_desc;
 
 typedef struct {          /* one GNN_Module's parameters (DEVICE pointers; unused ones NULL) */
@@ -461,6 +467,35 @@ int cgc_level_bwd(const cgc_level_desc* d, const cgc_block_params* emb, const cg
                   const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, const float* saved, float* scratch,
                   const float* d_readout, const float* d_x_out, const float* d_A_out, float* grads, float* d_x_in, float* d_A_in,
                   cgc_stream_t stream);
+
+/* DiffPool regularisers of one level (flags bit 3).  reg_out [2] (device): link, entropy loss as PyG's dense_diff_pool defines them
+ * (cgc_diffpool_reg_fwd).  d_reg [2] (device): their upstream gradients (zeros when a loss does not reach the objective).  Otherwise
+ * the arguments of cgc_level_fwd / cgc_level_bwd; without bit 3 these are those calls. */
+int cgc_level_fwd_reg(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
+                      const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, float* saved, float* scratch,
+                      float* readout, float* x_out, float* A_out, const float** assign_out, int* assign_ld, float* reg_out,
+                      cgc_stream_t stream);
+int cgc_level_bwd_reg(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
+                      const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, const float* saved, float* scratch,
+                      const float* d_readout, const float* d_x_out, const float* d_A_out, const float* d_reg, float* grads,
+                      float* d_x_in, float* d_A_in, cgc_stream_t stream);
+
+/* ==== DiffPool regularisers (csrc/diffpool_reg.hip), the passes around the products G = S^T S and S G.  For one pooling stage with
+ * assignment S [n, C] (row stride lds), the stage's adjacency A, dense padding N, numel = B N N, rows = B N:
+ *   link = ||A - S S^T||_F / numel = sqrt(||A||^2 - 2 sum_b tr(A'_b) + sum_b ||G_b||^2) / numel,   A' = S^T A S (A_out of _diff_pool)
+ *   ent  = sum_rows sum_j -S log(S + 1e-15) / rows
+ * All sums in double over fixed grids, combined in a fixed order (deterministic).  ws: cgc_diffpool_reg_ws_floats() floats, 16-byte
+ * aligned.  fwd: G, A_out [B, C, C] contiguous; A = dense adjacency of A_numel floats (rowptr NULL), or rowptr = the CSR's row
+ * pointer over n rows with A its values (NULL: all ones).  Writes link, ent (device scalars) and keep[0] = sqrt(T) for the backward.
+ * bwd_prep: c_l = d_reg[0] / (2 numel keep[0]), c_e = d_reg[1] / rows -> coef [2]; dao = d_ao - 2 c_l I per graph (d_ao NULL: 0),
+ * Gs = 4 c_l G.  entropy_bwd: ds[:, :C] (row stride ldd) += c_e (-log(S + 1e-15) - S / (S + 1e-15)).  adj_bwd: gA (+)= 2 c_l A. */
+int64_t cgc_diffpool_reg_ws_floats(void);
+int cgc_diffpool_reg_fwd(const float* S, int n, int C, int lds, const float* G, const float* A_out, int B, const float* A, int64_t A_numel,
+                         const int* rowptr, double numel, double rows, float* ws, float* link, float* ent, float* keep, cgc_stream_t stream);
+int cgc_diffpool_reg_bwd_prep(const float* d_reg, const float* keep, double numel, double rows, const float* d_ao, float* dao,
+                              const float* G, float* Gs, int B, int C, float* coef, cgc_stream_t stream);
+int cgc_diffpool_reg_entropy_bwd(const float* S, int n, int C, int lds, const float* coef, float* ds, int ldd, cgc_stream_t stream);
+int cgc_diffpool_reg_adj_bwd(const float* A, int64_t m, const float* coef, float* gA, int accumulate, cgc_stream_t stream);
 
 /* ==== A10: classification head + loss (model/network.py:220-234, 286-289): logits = Linear2(dropout(act(Linear1(cat(readouts))))),
  * loss = mean cross-entropy(logits, y), one kernel; the backward another.  x: HOST array of nseg (<= 3) device pointers [B, D] (the
