@@ -3,7 +3,7 @@ import ctypes as C
 
 P, I, F, D, L = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_int64
 
-ABI_VERSION = 7      # = CGC_ABI_VERSION of include/cgc_hip.h these prototypes were written against (tests compare the two)
+ABI_VERSION = 8      # = CGC_ABI_VERSION of include/cgc_hip.h these prototypes were written against (tests compare the two)
 
 PROTOTYPES = {
     'cgc_abi_version': [],
@@ -22,17 +22,13 @@ PROTOTYPES = {
     'cgc_graph_build_local': [P, L, I, P, P, I, I, I, F, P, P, P, P, P, P, P, P, P, P, P],
     'cgc_graph_local_max_nodes': [],
     'cgc_spmm': [P, P, P, P, P, P, P, P, I, I, P],
-    'cgc_spmm_graphs': [P, P, P, P, P, P, P, P, I, I, I, P, I, I, I, P],
-    'cgc_spmm_graphs_ordered': [P, P, P, P, P, P, P, P, I, I, I, P, I, I, I, P, P],
-    'cgc_gemm_f32': [I, I, I, I, I, F, P, I, P, I, F, P, I, P, I, L, L, L, P, I, I, P],
-    'cgc_gemm_f32_cat': [I, I, I, I, I, F, P, I, P, I, F, P, I, P, I, L, L, L, P, I, I, I, P, P, P, P, P, P, P, P],
+    'cgc_spmm_graphs': [P, P, P, P, P, P, P, P, I, I, I, P, I, I, I, P, P],
+    'cgc_gemm_f32': [I, I, I, I, I, F, P, I, P, I, F, P, I, P, I, L, L, L, P, I, I, I, P, P, P, P, P, P, P, P, L, I, P],
     'cgc_gemm_ws_floats': [],
     'cgc_gemm_split_count': [],
     'cgc_gemm_half_count': [],
     'cgc_gemm_half_ws_floats': [],
     'cgc_gemm_half_min_work': [L],
-    'cgc_gemm_f32_ws': [I, I, I, I, I, F, P, I, P, I, F, P, I, P, I, L, L, L, P, I, I, P, L, I, P],
-    'cgc_gemm_f32_cat_ws': [I, I, I, I, I, F, P, I, P, I, F, P, I, P, I, L, L, L, P, I, I, I, P, P, P, P, P, P, P, P, L, I, P],
     'cgc_gemm_tuning': [I],
     'cgc_reduce_batch_sum': [P, P, I, L, F, P],
     'cgc_reduce_batched': [P, P, I, I, I, F, P],
@@ -43,14 +39,12 @@ PROTOTYPES = {
     'cgc_l2norm_act_bn': [P, I, I, I, I, P, P, P, D, F, F, P, P, P, P, P, P],
     'cgc_sage_wide_fwd': [P, I, P, P, I, I, I, I, I, P, I, P, I, P, D, F, F, P, P, P, P, P, P],
     'cgc_bn_running_stats': [P, P, I, F, P, P, P],
-    'cgc_bn_act_apply': [P, I, I, I, P, P, P, P, P, I, P],
-    'cgc_bn_act_apply2': [P, I, I, I, P, P, P, P, P, I, P, I, P],
+    'cgc_bn_act_apply': [P, I, I, I, P, P, P, P, P, I, P, I, P],
     'cgc_bn_bwd_reduce': [P, I, P, I, I, I, P, P, P, P, P],
     'cgc_bn_act_l2_bwd': [P, I, P, P, I, I, I, I, I, P, P, P, P, D, P, P, P, P],
     'cgc_sage_narrow_fwd': [P, I, P, P, I, I, I, I, I, P, P, I, P, D, F, F, P, P, P, P, P, P],
     'cgc_sage_narrow_ws_floats': [I, I, I],
-    'cgc_sage_narrow_bwd': [P, I, P, P, I, I, I, I, I, P, P, P, P, D, P, I, I, P, P, P, P, P],
-    'cgc_sage_narrow_bwd_ld': [P, I, P, P, I, I, I, I, I, P, P, P, P, D, P, I, I, P, P, I, P, P, P],
+    'cgc_sage_narrow_bwd': [P, I, P, P, I, I, I, I, I, P, P, P, P, D, P, I, I, P, P, I, P, P, P],
     'cgc_colsum': [P, I, I, I, P, P, P],
     'cgc_softmax_fwd': [P, I, I, I, P, P],
     'cgc_softmax_bwd': [P, P, I, I, I, P, P, P, P],
@@ -89,10 +83,8 @@ PROTOTYPES = {
     'cgc_level_saved_floats': [P],
     'cgc_level_scratch_floats': [P],
     'cgc_level_grad_layout_of': [P, P],
-    'cgc_level_fwd': [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
-    'cgc_level_bwd': [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
-    'cgc_level_fwd_reg': [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
-    'cgc_level_bwd_reg': [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
+    'cgc_level_fwd': [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
+    'cgc_level_bwd': [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
     # DiffPool regularisers (csrc/diffpool_reg.hip)
     'cgc_diffpool_reg_ws_floats': [],
     'cgc_diffpool_reg_fwd': [P, I, I, I, P, P, I, P, L, P, D, D, P, P, P, P, P],

@@ -136,24 +136,23 @@ inline int up(int v, int m) { return (v + m - 1) / m * m; }
 inline int wide_ld(int F) { return (F >= 256 && F % 32 != 0) ? up(F, 32) : (F > 32 && F % 4 != 0) ? up(F, 4) : F; }
 inline int pad4_ld(int c) { return (c > 32 && c % 4 != 0) ? up(c, 4) : c; }
 
+// cgc_gemm_f32 with the level's workspace and mode, alpha = 1; nx extra K segments as that call takes them
 int gemm(const Ctx& c, int tA, int tB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float beta, float* C, int ldc,
          const float* bias = nullptr, int batch = 1, int64_t sA = 0, int64_t sB = 0, int64_t sC = 0, const int* gptr = nullptr,
-         int ragged = 0, int max_ragged = 0) {
+         int ragged = 0, int max_ragged = 0, int nx = 0, const float* const* xA = nullptr, const int* xlda = nullptr,
+         const int64_t* xsA = nullptr, const float* const* xB = nullptr, const int* xldb = nullptr, const int64_t* xsB = nullptr,
+         const int* xK = nullptr) {
   if (c.dry) return 0;
-  return cgc_gemm_f32_ws(tA, tB, M, N, K, 1.f, A, lda, B, ldb, beta, C, ldc, bias, batch, sA, sB, sC, gptr, ragged, max_ragged, c.gws,
-                         c.gws_floats, c.gemm_mode, c.s);
+  return cgc_gemm_f32(tA, tB, M, N, K, 1.f, A, lda, B, ldb, beta, C, ldc, bias, batch, sA, sB, sC, gptr, ragged, max_ragged, nx, xA, xlda,
+                      xsA, xB, xldb, xsB, xK, c.gws, c.gws_floats, c.gemm_mode, c.s);
 }
 
+// gemm with one extra K segment
 int gemm_x1(const Ctx& c, int tA, int tB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float beta, float* C, int ldc,
             const float* bias, int batch, int64_t sA, int64_t sB, int64_t sC, const int* gptr, int ragged, int max_ragged, const float* xA,
             int xlda, int64_t xsA, const float* xB, int xldb, int64_t xsB, int xK) {
-  if (c.dry) return 0;
-  const float* pa[1] = {xA};
-  const float* pb[1] = {xB};
-  const int la[1] = {xlda}, lb[1] = {xldb}, kk[1] = {xK};
-  const int64_t s1[1] = {xsA}, s2[1] = {xsB};
-  return cgc_gemm_f32_cat_ws(tA, tB, M, N, K, 1.f, A, lda, B, ldb, beta, C, ldc, bias, batch, sA, sB, sC, gptr, ragged, max_ragged, 1, pa, la,
-                             s1, pb, lb, s2, kk, c.gws, c.gws_floats, c.gemm_mode, c.s);
+  return gemm(c, tA, tB, M, N, K, A, lda, B, ldb, beta, C, ldc, bias, batch, sA, sB, sC, gptr, ragged, max_ragged, 1, &xA, &xlda, &xsA,
+              &xB, &xldb, &xsB, &xK);
 }
 
 // how many row slices the tall-skinny "weight gradient" contraction out[Fa,Fb] = A[n,Fa]^T B[n,Fb] is cut into (ops._split_parts):
@@ -293,7 +292,7 @@ int layer_fwd(const Ctx& c, const cgc_level_desc& d, const LayerP& p, const Laye
       CALL(cgc_l2norm_act_stats(s.hn, n, F, 1, d.act, s.hn, s.rinv, nullptr, nullptr, c.s));
   }
   if (d.has_bn && d.eval) CALL(cgc_bn_running_stats(p.rm, p.rv, F, p.eps, s.mean, s.istd, c.s));
-  CALL(cgc_bn_act_apply2(s.hn, n, F, d.act, d.has_bn ? s.mean : nullptr, s.istd, p.gamma, p.beta, y, ldy, y2, ldy2, c.s));
+  CALL(cgc_bn_act_apply(s.hn, n, F, d.act, d.has_bn ? s.mean : nullptr, s.istd, p.gamma, p.beta, y, ldy, y2, ldy2, c.s));
   c.scratch->release(m);
   return 0;
 }
@@ -312,8 +311,8 @@ int layer_bwd(const Ctx& c, const cgc_level_desc& d, const LayerP& p, const Laye
   float* db = d.has_bias ? dwdb + (size_t)fin * F : nullptr;
   if (F <= 32 && fin <= 32) {
     float* ws = c.scratch->f((size_t)cgc_sage_narrow_ws_floats(n, fin, F));
-    CALL(cgc_sage_narrow_bwd_ld(dy, ldy, s.hn, s.rinv, n, F, d.act, 1, mode, s.mean, s.istd, p.gamma, d.has_bn ? sums : nullptr, d.count, agg,
-                                lda, fin, p.W, dagg, ldd, dwdb, ws, c.s));
+    CALL(cgc_sage_narrow_bwd(dy, ldy, s.hn, s.rinv, n, F, d.act, 1, mode, s.mean, s.istd, p.gamma, d.has_bn ? sums : nullptr, d.count, agg,
+                             lda, fin, p.W, dagg, ldd, dwdb, ws, c.s));
   } else {
     float* dh = c.scratch->f((size_t)n * F);
     float* ws = db ? c.scratch->f(slot_floats) : nullptr;
@@ -500,15 +499,14 @@ struct Level {
 // neighbour aggregation of a level and its transpose: level 1 on the CSR (ops._Aggregate), levels 2-3 A_norm @ h (ops._BMatmul)
 int aggregate(const Ctx& c, const Level& L, const cgc_graph* g, const int* gptr, const float* h, int ldh, int w, float* out) {
   if (!L.dense) {
-    CALL(cgc_spmm_graphs_ordered(g->rowptr, g->col, nullptr, g->val, nullptr, g->inv_d, h, out, L.n, w, w, gptr, L.B, L.d.nmax, 0, nullptr, c.s));
+    CALL(cgc_spmm_graphs(g->rowptr, g->col, nullptr, g->val, nullptr, g->inv_d, h, out, L.n, w, w, gptr, L.B, L.d.nmax, 0, nullptr, c.s));
     return 0;
   }
   return bgemm(c, T3{L.An, L.B, L.R, L.R, L.R}, T3{const_cast<float*>(h), L.B, L.R, w, ldh}, T3{out, L.B, L.R, w, w}, 0, 0);
 }
 int aggregate_t(const Ctx& c, const Level& L, const cgc_graph* g, const int* gptr, const float* dy, int ldy, int w, float* dx) {
   if (!L.dense) {
-    CALL(cgc_spmm_graphs_ordered(g->t_rowptr, g->t_col, nullptr, g->t_val, g->inv_d, nullptr, dy, dx, L.n, w, w, gptr, L.B, L.d.nmax, 0, nullptr,
-                                 c.s));
+    CALL(cgc_spmm_graphs(g->t_rowptr, g->t_col, nullptr, g->t_val, g->inv_d, nullptr, dy, dx, L.n, w, w, gptr, L.B, L.d.nmax, 0, nullptr, c.s));
     return 0;
   }
   return bgemm(c, T3{L.An, L.B, L.R, L.R, L.R}, T3{const_cast<float*>(dy), L.B, L.R, w, ldy}, T3{dx, L.B, L.R, w, w}, 1, 0);
@@ -607,7 +605,7 @@ int level_fwd(const Ctx& c, Level& L, const cgc_block_params* emb, const cgc_blo
   CALL(cgc_softmax_fwd(L.S, n, C, L.ldC, L.S, c.s));
   // _diff_pool (model/network.py:194-208): X' = S^T X, A' = S^T (A S)
   if (!L.dense) {
-    CALL(cgc_spmm_graphs_ordered(g->rowptr, g->col, nullptr, g->val, nullptr, nullptr, L.S, L.P, n, C, L.ldC, gptr, L.B, d.nmax, 1 | (g->spatial ? 4 : 0), g->gorder, c.s));
+    CALL(cgc_spmm_graphs(g->rowptr, g->col, nullptr, g->val, nullptr, nullptr, L.S, L.P, n, C, L.ldC, gptr, L.B, d.nmax, 1 | (g->spatial ? 4 : 0), g->gorder, c.s));
     TRY(gemm(c, 1, 0, C, L.D, 0, L.S, L.ldC, L.embed(), L.D, 0.f, x_out, L.D, nullptr, L.B, 0, 0, (int64_t)C * L.D, gptr, 2, d.nmax));
     TRY(gemm(c, 1, 0, C, C, 0, L.S, L.ldC, L.P, L.ldC, 0.f, A_out, C, nullptr, L.B, 0, 0, (int64_t)C * C, gptr, 2, d.nmax));
   } else {
@@ -728,8 +726,8 @@ int level_bwd(const Ctx& c, Level& L, const cgc_block_params* emb, const cgc_blo
     if (!L.dense) {
       float* dp = sc.f((size_t)n * L.ldC);
       TRY(gemm(c, 0, 0, 0, C, C, L.S, L.ldC, d_ao, C, 0.f, dp, L.ldC, nullptr, B, 0, (int64_t)C * C, 0, gptr, 1, d.nmax));      // dP = S dA'
-      CALL(cgc_spmm_graphs_ordered(g->t_rowptr, g->t_col, nullptr, g->t_val, nullptr, nullptr, dp, ds, n, C, L.ldC, gptr, B, d.nmax, 2 | (g->spatial ? 4 : 0), g->gorder,
-                                   c.s));                                                                                          // dS = A^T dP
+      CALL(cgc_spmm_graphs(g->t_rowptr, g->t_col, nullptr, g->t_val, nullptr, nullptr, dp, ds, n, C, L.ldC, gptr, B, d.nmax, 2 | (g->spatial ? 4 : 0), g->gorder,
+                           c.s));                                                                                                  // dS = A^T dP
       TRY(gemm_x1(c, 0, 1, 0, C, C, L.P, L.ldC, d_ao, C, 1.f, ds, L.ldC, nullptr, B, 0, (int64_t)C * C, 0, gptr, 1, d.nmax, L.embed(), D, 0, d_xo,
                   D, (int64_t)C * D, D));                                                                  // + P dA'^T + X dX'^T
       if (L.reg) TRY(gemm(c, 0, 0, 0, C, C, L.S, L.ldC, Gs, C, 1.f, ds, L.ldC, nullptr, B, 0, (int64_t)C * C, 0, gptr, 1, d.nmax));   // + 4 c_l S G
@@ -783,6 +781,20 @@ int level_bwd(const Ctx& c, Level& L, const cgc_block_params* emb, const cgc_blo
     return level_bwd_blocks(c, L, emb, pl, jk, g, gptr, x_in, A_in, d_embed, dx12, dagg1, gAt, grads, d_x_in, d_A_in);
   }
   return level_bwd_blocks(c, L, emb, pl, jk, g, gptr, x_in, A_in, d_embed, nullptr, nullptr, nullptr, grads, d_x_in, d_A_in);
+}
+
+// What cgc_level_fwd and cgc_level_bwd share: the level's layouts in its two arenas (the GEMM workspace first in scratch) and the
+// launch context with the GEMM mode of flags bits 1 / 2; then body(c, L)
+template <class Body>
+int run_level(const cgc_level_desc* d, float* saved, float* scratch, cgc_stream_t stream, Body&& body) {
+  Level L(*d);
+  Arena sv(saved), sc(scratch);
+  L.layout_saved(sv);
+  L.layout_grads();
+  Ctx c{stream, false, &sc, nullptr, cgc_gemm_ws_floats()};
+  c.gws = sc.f((size_t)c.gws_floats);
+  c.gemm_mode = (d->flags & 2) ? CGC_GEMM_SPLIT_BF16 : (d->flags & 4) ? CGC_GEMM_SPLIT_F16 : CGC_GEMM_EXACT;
+  return body(c, L);
 }
 
 }  // namespace
@@ -842,53 +854,29 @@ extern "C" int64_t cgc_level_scratch_floats(const cgc_level_desc* d) {
   return (int64_t)high + 64;
 }
 
-extern "C" int cgc_level_fwd_reg(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
-                                 const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, float* saved, float* scratch,
-                                 float* readout, float* x_out, float* A_out, const float** assign_out, int* assign_ld, float* reg_out,
-                                 cgc_stream_t stream) {
+extern "C" int cgc_level_fwd(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
+                             const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, float* saved, float* scratch,
+                             float* readout, float* x_out, float* A_out, const float** assign_out, int* assign_ld, float* reg_out,
+                             cgc_stream_t stream) {
   if (!cgc_level_supported(d) || saved == nullptr || scratch == nullptr) return CGC_EINVAL;
   if (!aligned16(saved) || !aligned16(scratch)) return CGC_EINVAL;
   if ((d->flags & 8) && reg_out == nullptr) return CGC_EINVAL;
-  Level L(*d);
-  Arena sv(saved), sc(scratch);
-  L.layout_saved(sv);
-  L.layout_grads();
-  Ctx c{stream, false, &sc, nullptr, cgc_gemm_ws_floats()};
-  c.gws = sc.f((size_t)c.gws_floats);
-  c.gemm_mode = (d->flags & 2) ? CGC_GEMM_SPLIT_BF16 : (d->flags & 4) ? CGC_GEMM_SPLIT_F16 : CGC_GEMM_EXACT;
-  const int rc = level_fwd(c, L, emb, pool, jk, g, gptr, x_in, A_in, readout, x_out, A_out, reg_out);
-  if (assign_out != nullptr) *assign_out = L.S;
-  if (assign_ld != nullptr) *assign_ld = L.ldC;
-  return rc;
-}
-
-extern "C" int cgc_level_fwd(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
-                             const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, float* saved, float* scratch,
-                             float* readout, float* x_out, float* A_out, const float** assign_out, int* assign_ld, cgc_stream_t stream) {
-  return cgc_level_fwd_reg(d, emb, pool, jk, g, gptr, x_in, A_in, saved, scratch, readout, x_out, A_out, assign_out, assign_ld, nullptr, stream);
-}
-
-extern "C" int cgc_level_bwd_reg(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
-                                 const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, const float* saved, float* scratch,
-                                 const float* d_readout, const float* d_x_out, const float* d_A_out, const float* d_reg, float* grads,
-                                 float* d_x_in, float* d_A_in, cgc_stream_t stream) {
-  if (!cgc_level_supported(d) || saved == nullptr || scratch == nullptr || grads == nullptr || d->eval) return CGC_EINVAL;
-  if (!aligned16(saved) || !aligned16(scratch) || !aligned16(grads)) return CGC_EINVAL;
-  if ((d->flags & 8) && d_reg == nullptr) return CGC_EINVAL;
-  Level L(*d);
-  Arena sv(const_cast<float*>(saved)), sc(scratch);
-  L.layout_saved(sv);
-  L.layout_grads();
-  Ctx c{stream, false, &sc, nullptr, cgc_gemm_ws_floats()};
-  c.gws = sc.f((size_t)c.gws_floats);
-  c.gemm_mode = (d->flags & 2) ? CGC_GEMM_SPLIT_BF16 : (d->flags & 4) ? CGC_GEMM_SPLIT_F16 : CGC_GEMM_EXACT;
-  return level_bwd(c, L, emb, pool, jk, g, gptr, x_in, A_in, d_readout, d_x_out, d_A_out, grads, d_x_in, d_A_in, d_reg);
+  return run_level(d, saved, scratch, stream, [&](const Ctx& c, Level& L) {
+    const int rc = level_fwd(c, L, emb, pool, jk, g, gptr, x_in, A_in, readout, x_out, A_out, reg_out);
+    if (assign_out != nullptr) *assign_out = L.S;
+    if (assign_ld != nullptr) *assign_ld = L.ldC;
+    return rc;
+  });
 }
 
 extern "C" int cgc_level_bwd(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
                              const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, const float* saved, float* scratch,
-                             const float* d_readout, const float* d_x_out, const float* d_A_out, float* grads, float* d_x_in, float* d_A_in,
-                             cgc_stream_t stream) {
-  return cgc_level_bwd_reg(d, emb, pool, jk, g, gptr, x_in, A_in, saved, scratch, d_readout, d_x_out, d_A_out, nullptr, grads, d_x_in, d_A_in,
-                           stream);
+                             const float* d_readout, const float* d_x_out, const float* d_A_out, const float* d_reg, float* grads,
+                             float* d_x_in, float* d_A_in, cgc_stream_t stream) {
+  if (!cgc_level_supported(d) || saved == nullptr || scratch == nullptr || grads == nullptr || d->eval) return CGC_EINVAL;
+  if (!aligned16(saved) || !aligned16(scratch) || !aligned16(grads)) return CGC_EINVAL;
+  if ((d->flags & 8) && d_reg == nullptr) return CGC_EINVAL;
+  return run_level(d, const_cast<float*>(saved), scratch, stream, [&](const Ctx& c, Level& L) {
+    return level_bwd(c, L, emb, pool, jk, g, gptr, x_in, A_in, d_readout, d_x_out, d_A_out, grads, d_x_in, d_A_in, d_reg);
+  });
 }

@@ -731,45 +731,20 @@ static int gemm_dispatch(GemmArgs& a, int transA, int transB, int batch, int max
   return big_route(sk, ws);                        // 128 x 128
 }
 
-static void gemm_fill(GemmArgs& a, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb, float beta,
-                      float* C, int ldc, const float* bias, int64_t strideA, int64_t strideB, int64_t strideC, const int* gptr,
-                      int ragged) {
+extern "C" int cgc_gemm_f32(int transA, int transB, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb,
+                            float beta, float* C, int ldc, const float* bias, int batch, int64_t strideA, int64_t strideB,
+                            int64_t strideC, const int* gptr, int ragged, int max_ragged, int nx, const float* const* xA,
+                            const int* xlda, const int64_t* xstrideA, const float* const* xB, const int* xldb,
+                            const int64_t* xstrideB, const int* xK, float* ws, int64_t ws_floats, int mode, cgc_stream_t stream_) {
+  if (nx < 0 || nx > 2) return CGC_EINVAL;
+  if (mode != CGC_GEMM_EXACT && mode != CGC_GEMM_SPLIT_BF16 && mode != CGC_GEMM_SPLIT_F16) return CGC_EINVAL;
+  GemmArgs a;
   a.A = A; a.B = B; a.C = C; a.bias = bias; a.gptr = gptr;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
   a.strideA = strideA; a.strideB = strideB; a.strideC = strideC;
   a.alpha = alpha; a.beta = beta; a.ragged = ragged; a.tiles_n = 0;
   a.per_batch = a.nb = 0; a.ws = nullptr; a.resident = 0; a.s_max = 1; a.chunk = 0; a.scale = nullptr;
-  a.nx = 0;
   for (int i = 0; i < 2; ++i) { a.xA[i] = a.xB[i] = nullptr; a.xlda[i] = a.xldb[i] = a.xK[i] = 0; a.xsA[i] = a.xsB[i] = 0; }
-}
-
-extern "C" int cgc_gemm_f32_ws(int transA, int transB, int M, int N, int K, float alpha, const float* A, int lda, const float* B,
-                               int ldb, float beta, float* C, int ldc, const float* bias, int batch, int64_t strideA, int64_t strideB,
-                               int64_t strideC, const int* gptr, int ragged, int max_ragged, float* ws, int64_t ws_floats, int mode,
-                               cgc_stream_t stream_) {
-  if (mode != CGC_GEMM_EXACT && mode != CGC_GEMM_SPLIT_BF16 && mode != CGC_GEMM_SPLIT_F16) return CGC_EINVAL;
-  GemmArgs a;
-  gemm_fill(a, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, strideA, strideB, strideC, gptr, ragged);
-  return gemm_dispatch(a, transA, transB, batch, max_ragged, ws, ws_floats, mode, as_stream(stream_));
-}
-
-extern "C" int cgc_gemm_f32(int transA, int transB, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb,
-                            float beta, float* C, int ldc, const float* bias, int batch, int64_t strideA, int64_t strideB,
-                            int64_t strideC, const int* gptr, int ragged, int max_ragged, cgc_stream_t stream_) {
-  return cgc_gemm_f32_ws(transA, transB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, batch, strideA, strideB, strideC, gptr,
-                         ragged, max_ragged, nullptr, 0, CGC_GEMM_EXACT, stream_);
-}
-
-extern "C" int cgc_gemm_f32_cat_ws(int transA, int transB, int M, int N, int K, float alpha, const float* A, int lda, const float* B,
-                                   int ldb, float beta, float* C, int ldc, const float* bias, int batch, int64_t strideA,
-                                   int64_t strideB, int64_t strideC, const int* gptr, int ragged, int max_ragged, int nx,
-                                   const float* const* xA, const int* xlda, const int64_t* xstrideA, const float* const* xB,
-                                   const int* xldb, const int64_t* xstrideB, const int* xK, float* ws, int64_t ws_floats, int mode,
-                                   cgc_stream_t stream_) {
-  if (nx < 0 || nx > 2) return CGC_EINVAL;
-  if (mode != CGC_GEMM_EXACT && mode != CGC_GEMM_SPLIT_BF16 && mode != CGC_GEMM_SPLIT_F16) return CGC_EINVAL;
-  GemmArgs a;
-  gemm_fill(a, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, strideA, strideB, strideC, gptr, ragged);
   int kept = 0;
   for (int i = 0; i < nx; ++i) {
     if (xK[i] <= 0) continue;
@@ -779,15 +754,6 @@ extern "C" int cgc_gemm_f32_cat_ws(int transA, int transB, int M, int N, int K, 
   }
   a.nx = kept;
   return gemm_dispatch(a, transA, transB, batch, max_ragged, ws, ws_floats, mode, as_stream(stream_));
-}
-
-extern "C" int cgc_gemm_f32_cat(int transA, int transB, int M, int N, int K, float alpha, const float* A, int lda, const float* B,
-                                int ldb, float beta, float* C, int ldc, const float* bias, int batch, int64_t strideA,
-                                int64_t strideB, int64_t strideC, const int* gptr, int ragged, int max_ragged, int nx,
-                                const float* const* xA, const int* xlda, const int64_t* xstrideA, const float* const* xB,
-                                const int* xldb, const int64_t* xstrideB, const int* xK, cgc_stream_t stream_) {
-  return cgc_gemm_f32_cat_ws(transA, transB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, batch, strideA, strideB, strideC,
-                             gptr, ragged, max_ragged, nx, xA, xlda, xstrideA, xB, xldb, xstrideB, xK, nullptr, 0, CGC_GEMM_EXACT, stream_);
 }
 
 // ---- deterministic split-K combine

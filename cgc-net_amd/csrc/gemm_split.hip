@@ -7,7 +7,7 @@
 // v_mfma_f32_32x32x16_bf16 issues in 32 cycles per SIMD where the eight v_mfma_f32_32x32x2_f32 of the same k range take 512: six
 // pairs are 192 matrix-pipe cycles per 32 x 32 x 16 block against 512.
 //
-// This is an opt-in MODE of the same entry points (cgc_gemm_f32_ws / cgc_gemm_f32_cat_ws, mode = CGC_GEMM_SPLIT_BF16; the step
+// This is an opt-in MODE of the same entry point (cgc_gemm_f32, mode = CGC_GEMM_SPLIT_BF16; the step
 // sequencer: cgc_level_desc.flags bit 1) for the products that take the 128 x 128 route of gemm.hip -- the assignment Linear
 // (model/network.py:121-122), S^T (A S), P dA'^T, S dA' of _diff_pool and its backward (:206-207) -- in all their forms: NN / NT / TN,
 // ragged M, ragged K, uniform K chunks, extra K segments, beta = 1, tail split.  Everything else stays on the exact kernel.

@@ -24,7 +24,7 @@ struct StatsFinPtrs {        // slots in, BatchNorm vectors out
   long long* nbt;
   float eps, momentum;
 };
-struct BnApplyPtrs {         // cgc_bn_act_apply2
+struct BnApplyPtrs {         // cgc_bn_act_apply
   const float *hn, *mean, *istd, *gamma, *beta;
   float *y, *y2;
   int ldy2;

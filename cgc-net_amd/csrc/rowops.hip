@@ -536,11 +536,6 @@ __global__ __launch_bounds__(256) void k_bn_act_apply(const BnApplyPtrs p0, cons
   }
 }
 
-extern "C" int cgc_bn_act_apply(const float* hn, int n, int F, int act, const float* mean, const float* istd,
-                                const float* gamma, const float* beta, float* y, int ldy, cgc_stream_t stream) {
-  return cgc_bn_act_apply2(hn, n, F, act, mean, istd, gamma, beta, y, ldy, nullptr, 0, stream);
-}
-
 // the same result written to a second destination as well (y2 [n, F], row stride ldy2; NULL: none): a layer's output goes into the
 // buffer the next aggregation reads AND into its slot of the block's concatenation (model/network.py:118)
 int bn_act_apply_groups(const BnApplyPtrs* g, int ng, int n, int F, int act, int ldy, hipStream_t stream) {
@@ -557,8 +552,8 @@ int bn_act_apply_groups(const BnApplyPtrs* g, int ng, int n, int F, int act, int
   CGC_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
-extern "C" int cgc_bn_act_apply2(const float* hn, int n, int F, int act, const float* mean, const float* istd, const float* gamma,
-                                 const float* beta, float* y, int ldy, float* y2, int ldy2, cgc_stream_t stream) {
+extern "C" int cgc_bn_act_apply(const float* hn, int n, int F, int act, const float* mean, const float* istd, const float* gamma,
+                                const float* beta, float* y, int ldy, float* y2, int ldy2, cgc_stream_t stream) {
   const BnApplyPtrs g{hn, mean, istd, gamma, beta, y, y2, ldy2};
   return bn_act_apply_groups(&g, 1, n, F, act, ldy, as_stream(stream));
 }

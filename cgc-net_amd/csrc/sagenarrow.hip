@@ -172,18 +172,6 @@ static int sn_grid(int n) {
 
 extern "C" int64_t cgc_sage_narrow_ws_floats(int n, int fin, int F) { return (int64_t)sn_grid(n > 0 ? n : 1) * (fin * F + F); }
 
-// dy [n,F] (row stride ldy), hn [n,F], rinv [n], BatchNorm vectors and sums [2,F] exactly as cgc_bn_act_l2_bwd (mode 0 / 1 / 2);
-// agg [n,fin] (row stride lda), W [fin,F].  Out: dagg [n,fin] (NULL: not needed), dwdb [fin*F + F] = d W row-major followed by d b.
-// ws: cgc_sage_narrow_ws_floats(n, fin, F) floats.  Envelope fin <= 32, F <= 32; otherwise CGC_EINVAL, nothing launched.
-extern "C" int cgc_sage_narrow_bwd(const float* dy, int ldy, const float* hn, const float* rinv, int n, int F, int act, int normalize,
-                                   int mode, const float* mean, const float* istd, const float* gamma, const float* sums, double count,
-                                   const float* agg, int lda, int fin, const float* W, float* dagg, float* dwdb, float* ws,
-                                   cgc_stream_t stream_) {
-  return cgc_sage_narrow_bwd_ld(dy, ldy, hn, rinv, n, F, act, normalize, mode, mean, istd, gamma, sums, count, agg, lda, fin, W, dagg, fin,
-                                dwdb, ws, stream_);
-}
-
-// the same with a row stride for dagg (>= fin): the two blocks of a level write their halves of one [n, fin_e + fin_p] gradient
 // One launch for up to two layers of equal shape (the embedding and the assignment block of a level run in lockstep): sets g[0..ng)
 int sage_narrow_bwd_groups(const SnBwdPtrs* g, float* const* dwdb, int ng, int ldy, int n, int F, int act, int normalize, int mode, double count,
                            int lda, int fin, int ldd, hipStream_t st) {
@@ -217,10 +205,14 @@ int sage_narrow_bwd_groups(const SnBwdPtrs* g, float* const* dwdb, int ng, int l
   return launch_reduce_slots_f32_pair(g[0].ws, dwdb[0], g1.ws, dwdb[ng - 1], ng, grid, width, st);
 }
 
-extern "C" int cgc_sage_narrow_bwd_ld(const float* dy, int ldy, const float* hn, const float* rinv, int n, int F, int act, int normalize,
-                                      int mode, const float* mean, const float* istd, const float* gamma, const float* sums, double count,
-                                      const float* agg, int lda, int fin, const float* W, float* dagg, int ldd, float* dwdb, float* ws,
-                                      cgc_stream_t stream_) {
+// dy [n,F] (row stride ldy), hn [n,F], rinv [n], BatchNorm vectors and sums [2,F] exactly as cgc_bn_act_l2_bwd (mode 0 / 1 / 2);
+// agg [n,fin] (row stride lda), W [fin,F].  Out: dagg [n,fin] (row stride ldd >= fin: the two blocks of a level write their halves of
+// one [n, fin_e + fin_p] gradient; NULL: not needed), dwdb [fin*F + F] = d W row-major followed by d b.
+// ws: cgc_sage_narrow_ws_floats(n, fin, F) floats.  Envelope fin <= 32, F <= 32; otherwise CGC_EINVAL, nothing launched.
+extern "C" int cgc_sage_narrow_bwd(const float* dy, int ldy, const float* hn, const float* rinv, int n, int F, int act, int normalize,
+                                   int mode, const float* mean, const float* istd, const float* gamma, const float* sums, double count,
+                                   const float* agg, int lda, int fin, const float* W, float* dagg, int ldd, float* dwdb, float* ws,
+                                   cgc_stream_t stream_) {
   const SnBwdPtrs g{dy, hn, rinv, mean, istd, gamma, sums, agg, W, dagg, ws};
   float* const out[1] = {dwdb};
   return sage_narrow_bwd_groups(&g, out, 1, ldy, n, F, act, normalize, mode, count, lda, fin, ldd, as_stream(stream_));

@@ -287,19 +287,13 @@ extern "C" int cgc_spmm(const int* rowptr, const int* col, const int* perm, cons
 // nmax = largest graph.  visit bits 0-1: the visiting-order hint of k_spmm_wide; the other bits are not read.
 // gorder (optional, B ints, a permutation of the graphs): the sequence in which the graphs are visited; the eight XCDs take
 // consecutive eighths of it.  Scheduling only -- the result does not depend on it.
-extern "C" int cgc_spmm_graphs_ordered(const int* rowptr, const int* col, const int* perm, const float* val, const float* pre,
-                                       const float* post, const float* x, float* out, int n, int width, int ld, const int* gptr, int B,
-                                       int nmax, int visit, const int* gorder, cgc_stream_t stream) {
+extern "C" int cgc_spmm_graphs(const int* rowptr, const int* col, const int* perm, const float* val, const float* pre,
+                               const float* post, const float* x, float* out, int n, int width, int ld, const int* gptr, int B,
+                               int nmax, int visit, const int* gorder, cgc_stream_t stream) {
   if (n <= 0 || width <= 0) return 0;
   if (ld < width) return CGC_EINVAL;
   const int trec = width > 64 ? cgc_timing_begin(CGC_TAG_SPMM_WIDE, n, width, ld, val != nullptr, 0, 0, 0, as_stream(stream)) : -1;
   const int rc = launch_gather(rowptr, col, perm, val, pre, post, x, out, n, width, ld, gptr, B, nmax, visit & 3, as_stream(stream), gorder);
   cgc_timing_end(trec, as_stream(stream));
   return rc;
-}
-
-extern "C" int cgc_spmm_graphs(const int* rowptr, const int* col, const int* perm, const float* val, const float* pre,
-                               const float* post, const float* x, float* out, int n, int width, int ld, const int* gptr, int B,
-                               int nmax, int visit, cgc_stream_t stream) {
-  return cgc_spmm_graphs_ordered(rowptr, col, perm, val, pre, post, x, out, n, width, ld, gptr, B, nmax, visit, nullptr, stream);
 }

@@ -376,8 +376,8 @@ _NO_WS = _NoWorkspace()
 
 
 class HipKernels(KernelSpec):
-    tail_split = True   # hand cgc_gemm_f32_ws its slab workspace (False: every output tile is computed whole; tests / A-B timing)
-    # cgc_gemm_f32_ws's `mode` for the products issued through this table (the per-operator path): GEMM_EXACT (default),
+    tail_split = True   # hand cgc_gemm_f32 its slab workspace (False: every output tile is computed whole; tests / A-B timing)
+    # cgc_gemm_f32's `mode` for the products issued through this table (the per-operator path): GEMM_EXACT (default),
     # GEMM_SPLIT_BF16 -- the big products as six bf16 MFMA pairs per fp32 product (csrc/gemm_split.hip) -- or GEMM_SPLIT_F16 -- as
     # three fp16 pairs of operands scaled per batch item (csrc/gemm_half.hip).  The encoder sets it from its own ``gemm_mode`` at
     # the top of forward(); the sequencer gets the same choice through cgc_level_desc.flags bits 1 / 2.
@@ -542,16 +542,16 @@ class HipKernels(KernelSpec):
         self._dev(rowptr, col, perm, val, pre, post, x, out, gptr)
         assert (x.is_contiguous() and out.is_contiguous()) if ld is None else (gptr is not None and x.stride(1) == 1 and out.stride(1) == 1)
         if gptr is not None:
-            self._chk(self.lib.cgc_spmm_graphs_ordered(_ptr(rowptr), _ptr(col), _ptr(perm), _ptr(val), _ptr(pre), _ptr(post),
-                                                       _ptr(x), _ptr(out), n, width, width if ld is None else ld, _ptr(gptr),
-                                                       num_graphs, nmax, int(visit), _ptr(gorder), self._stream()), 'cgc_spmm_graphs')
+            self._chk(self.lib.cgc_spmm_graphs(_ptr(rowptr), _ptr(col), _ptr(perm), _ptr(val), _ptr(pre), _ptr(post),
+                                               _ptr(x), _ptr(out), n, width, width if ld is None else ld, _ptr(gptr),
+                                               num_graphs, nmax, int(visit), _ptr(gorder), self._stream()), 'cgc_spmm_graphs')
         else:
             self._chk(self.lib.cgc_spmm(_ptr(rowptr), _ptr(col), _ptr(perm), _ptr(val), _ptr(pre), _ptr(post),
                                         _ptr(x), _ptr(out), n, width, self._stream()), 'cgc_spmm')
 
     # -- dense contractions
     def _gemm_ws(self, device, stream):
-        """The workspace of cgc_gemm_f32_ws (include/cgc_hip.h): the slabs of the tail split and, at its end, the scale slots of mode
+        """The workspace of cgc_gemm_f32 (include/cgc_hip.h): the slabs of the tail split and, at its end, the scale slots of mode
         GEMM_SPLIT_F16; one per (device, stream): products queued on one stream run one after the other and may share it; two
         streams must not.  tail_split = False: no slabs -- mode GEMM_SPLIT_F16 still gets its scale slots (a workspace too small for
         a slab)."""
@@ -568,23 +568,18 @@ class HipKernels(KernelSpec):
         self._dev(A, B, C, bias, gptr)
         stream = self._stream()
         ws = self._gemm_ws(C.device, stream)
-        if extra:
-            nx = len(extra)
+        nx = len(extra)
+        segs = (None,) * 7                     # no extra K segments: NULL arrays
+        if nx:
             self._dev(*[e[0] for e in extra], *[e[1] for e in extra])
             PA, IA, LA = ctypes.c_void_p * nx, ctypes.c_int * nx, ctypes.c_int64 * nx
-            rc = self.lib.cgc_gemm_f32_cat_ws(int(transA), int(transB), M, N, K, ctypes.c_float(alpha), _ptr(A), lda,
-                                              _ptr(B), ldb, ctypes.c_float(beta), _ptr(C), ldc, _ptr(bias), batch,
-                                              ctypes.c_int64(strideA), ctypes.c_int64(strideB), ctypes.c_int64(strideC),
-                                              _ptr(gptr), ragged, max_ragged, nx,
-                                              PA(*[e[0].data_ptr() for e in extra]), IA(*[e[2] for e in extra]),
-                                              LA(*[e[5] for e in extra]), PA(*[e[1].data_ptr() for e in extra]),
-                                              IA(*[e[3] for e in extra]), LA(*[e[6] for e in extra]),
-                                              IA(*[e[4] for e in extra]), ws.data_ptr(), ws.numel(), int(self.gemm_mode), stream)
-        else:
-            rc = self.lib.cgc_gemm_f32_ws(int(transA), int(transB), M, N, K, ctypes.c_float(alpha), _ptr(A), lda,
-                                          _ptr(B), ldb, ctypes.c_float(beta), _ptr(C), ldc, _ptr(bias), batch,
-                                          ctypes.c_int64(strideA), ctypes.c_int64(strideB), ctypes.c_int64(strideC),
-                                          _ptr(gptr), ragged, max_ragged, ws.data_ptr(), ws.numel(), int(self.gemm_mode), stream)
+            segs = (PA(*[e[0].data_ptr() for e in extra]), IA(*[e[2] for e in extra]), LA(*[e[5] for e in extra]),
+                    PA(*[e[1].data_ptr() for e in extra]), IA(*[e[3] for e in extra]), LA(*[e[6] for e in extra]),
+                    IA(*[e[4] for e in extra]))
+        rc = self.lib.cgc_gemm_f32(int(transA), int(transB), M, N, K, ctypes.c_float(alpha), _ptr(A), lda,
+                                   _ptr(B), ldb, ctypes.c_float(beta), _ptr(C), ldc, _ptr(bias), batch,
+                                   ctypes.c_int64(strideA), ctypes.c_int64(strideB), ctypes.c_int64(strideC),
+                                   _ptr(gptr), ragged, max_ragged, nx, *segs, ws.data_ptr(), ws.numel(), int(self.gemm_mode), stream)
         self._chk(rc, 'cgc_gemm_f32')
 
     def reduce_batch_sum(self, ws, out, parts, numel, beta=0.0):
@@ -633,7 +628,7 @@ class HipKernels(KernelSpec):
     def bn_act_apply(self, hn, n, F, act, mean, istd, gamma, beta, y_out, ldy):
         self._dev(hn, mean, istd, gamma, beta, y_out)
         self._chk(self.lib.cgc_bn_act_apply(_ptr(hn), n, F, act, _ptr(mean), _ptr(istd), _ptr(gamma), _ptr(beta),
-                                            _ptr(y_out), ldy, self._stream()), 'cgc_bn_act_apply')
+                                            _ptr(y_out), ldy, None, 0, self._stream()), 'cgc_bn_act_apply')
 
     def l2norm_act_bn(self, h, n, F, normalize, act, hn_out, rinv_out, count, eps, momentum, running_mean, running_var,
                       num_batches_tracked, mean_out, istd_out):
@@ -673,7 +668,7 @@ class HipKernels(KernelSpec):
         ws = torch.empty(int(self.lib.cgc_sage_narrow_ws_floats(n, fin, F)), dtype=torch.float32, device=hn.device)
         self._chk(self.lib.cgc_sage_narrow_bwd(_ptr(dy), ldy, _ptr(hn), _ptr(rinv), n, F, act, int(normalize), mode, _ptr(mean),
                                                _ptr(istd), _ptr(gamma), _ptr(sums), ctypes.c_double(count), _ptr(agg), lda, fin,
-                                               _ptr(weight), _ptr(dagg_out), _ptr(dwdb_out), _ptr(ws), self._stream()),
+                                               _ptr(weight), _ptr(dagg_out), fin, _ptr(dwdb_out), _ptr(ws), self._stream()),
                   'cgc_sage_narrow_bwd')
         return True
 

@@ -15,7 +15,6 @@ import torch
 from torch.autograd import Function
 
 from . import kernels
-from .graph import uniform_ptr
 from .kernels import ACT_CODES
 
 P, I, F_, D_, L = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_int64
@@ -232,39 +231,47 @@ def _sizes(d):
     return hit
 
 
+def _level_fwd(d, emb, pool, jk, g, gptr, x_in, A_in, structs=None, assign=None):
+    """One cgc_level_fwd call on fresh arenas and outputs; a copy of the assignment matrix is appended to ``assign`` (a list) when
+    given.  Returns (saved, (pe, pp, pj, gs), readout, x_out, A_out, reg): x_out / A_out are None without an assignment block, reg
+    (the [link, ent] pair) is None without REG_FLAG.  gs: the cgc_graph of a level-1 BatchGraph, all NULL at the dense levels."""
+    K = kernels.get()
+    dev = x_in.device
+    K._dev(x_in, A_in, gptr)
+    n_saved, n_scratch, _ = _sizes(d)
+    saved = torch.empty(n_saved, dtype=torch.float32, device=dev)
+    scratch = torch.empty(n_scratch, dtype=torch.float32, device=dev)
+    D = d.H if d.jk else 2 * d.H + d.E
+    readout = torch.empty(d.B, D, dtype=torch.float32, device=dev)
+    x_out = torch.empty(d.B, d.C, D, dtype=torch.float32, device=dev) if d.C else None
+    A_out = torch.empty(d.B, d.C, d.C, dtype=torch.float32, device=dev) if d.C else None
+    pe, pp, pj = structs if structs is not None else (_block_params(emb), _block_params(pool), _jk_params(jk))
+    gs = Graph()
+    if g is not None:
+        gs.rowptr, gs.col, gs.t_rowptr, gs.t_col = _p(g.rowptr), _p(g.col), _p(g.t_rowptr), _p(g.t_col)
+        gs.val, gs.t_val, gs.inv_d, gs.gorder = _p(g.val), _p(g.t_val), _p(g.inv_d), _p(g.gorder)
+        gs.spatial = int(bool(getattr(g, 'spatial', False)))
+    s_ptr, s_ld = P(), I()
+    reg = torch.empty(2, dtype=torch.float32, device=dev) if has_reg(d) else None
+    rc = K.lib.cgc_level_fwd(C.byref(d), C.byref(pe), C.byref(pp), C.byref(pj), C.byref(gs), _p(gptr), _p(x_in), _p(A_in), _p(saved),
+                             _p(scratch), _p(readout), _p(x_out), _p(A_out), C.byref(s_ptr), C.byref(s_ld), _p(reg), K._stream())
+    if rc != 0:
+        raise RuntimeError('cgc_level_fwd%s failed with code %d' % (' (inference)' if d.eval else '', rc))
+    if assign is not None and d.C:
+        off = (s_ptr.value - saved.data_ptr()) // 4
+        assign.append(torch.as_strided(saved, (d.n, d.C), (s_ld.value, 1), off).clone())
+    return saved, (pe, pp, pj, gs), readout, x_out, A_out, reg
+
+
 class _Level(Function):
     """(readout, x_out, A_out) = one level; ``cfg`` carries the non-tensor arguments."""
 
     @staticmethod
     def forward(ctx, cfg, x_in, A_in, *params):
-        lib = _lib()
-        d, emb, pool, jk, g, gptr = cfg['desc'], cfg['emb'], cfg['pool'], cfg['jk'], cfg['graph'], cfg['gptr']
-        dev = x_in.device
-        kernels.get()._dev(x_in, A_in, gptr)
-        stream = kernels.get()._stream()
-        n_saved, n_scratch, _ = _sizes(d)
-        saved = torch.empty(n_saved, dtype=torch.float32, device=dev)
-        scratch = torch.empty(n_scratch, dtype=torch.float32, device=dev)
-        D = d.H if d.jk else 2 * d.H + d.E
-        readout = torch.empty(d.B, D, dtype=torch.float32, device=dev)
-        x_out = torch.empty(d.B, d.C, D, dtype=torch.float32, device=dev) if d.C else None
-        A_out = torch.empty(d.B, d.C, d.C, dtype=torch.float32, device=dev) if d.C else None
-        pe, pp, pj = cfg['structs'] if cfg.get('structs') is not None else (_block_params(emb), _block_params(pool), _jk_params(jk))
-        gs = Graph()
-        if g is not None:
-            gs.rowptr, gs.col, gs.t_rowptr, gs.t_col = _p(g.rowptr), _p(g.col), _p(g.t_rowptr), _p(g.t_col)
-            gs.val, gs.t_val, gs.inv_d, gs.gorder = _p(g.val), _p(g.t_val), _p(g.inv_d), _p(g.gorder)
-            gs.spatial = int(bool(getattr(g, 'spatial', False)))
-        s_ptr, s_ld = P(), I()
-        reg = torch.empty(2, dtype=torch.float32, device=dev) if has_reg(d) else None
-        rc = lib.cgc_level_fwd_reg(C.byref(d), C.byref(pe), C.byref(pp), C.byref(pj), C.byref(gs), _p(gptr), _p(x_in), _p(A_in), _p(saved),
-                                   _p(scratch), _p(readout), _p(x_out), _p(A_out), C.byref(s_ptr), C.byref(s_ld), _p(reg), stream)
-        if rc != 0:
-            raise RuntimeError('cgc_level_fwd failed with code %d' % rc)
-        if cfg.get('assign') is not None and d.C:
-            off = (s_ptr.value - saved.data_ptr()) // 4
-            cfg['assign'].append(torch.as_strided(saved, (d.n, d.C), (s_ld.value, 1), off).detach().clone())
-        ctx.cfg, ctx.structs = cfg, (pe, pp, pj, gs)
+        d = cfg['desc']
+        saved, ctx.structs, readout, x_out, A_out, reg = _level_fwd(d, cfg['emb'], cfg['pool'], cfg['jk'], cfg['graph'], cfg['gptr'], x_in,
+                                                                    A_in, cfg.get('structs'), cfg.get('assign'))
+        ctx.cfg = cfg
         ctx.save_for_backward(x_in, A_in, saved, *[p for p in params if p is not None])
         ctx.mask = [p is not None for p in params]
         ctx.shapes = [tuple(p.shape) if p is not None else None for p in params]
@@ -298,8 +305,8 @@ class _Level(Function):
         if has_reg(d):               # a loss that does not reach the objective has gradient zero
             zero = torch.zeros((), dtype=torch.float32, device=dev)
             d_reg = torch.stack([zero if d_link is None else d_link.float(), zero if d_ent is None else d_ent.float()])
-        rc = lib.cgc_level_bwd_reg(C.byref(d), C.byref(pe), C.byref(pp), C.byref(pj), C.byref(gs), _p(gptr), _p(x_in), _p(A_in), _p(saved),
-                                   _p(scratch), _p(d_readout), _p(d_x_out), _p(d_A_out), _p(d_reg), _p(grads), _p(d_x_in), _p(d_A_in), stream)
+        rc = lib.cgc_level_bwd(C.byref(d), C.byref(pe), C.byref(pp), C.byref(pj), C.byref(gs), _p(gptr), _p(x_in), _p(A_in), _p(saved),
+                               _p(scratch), _p(d_readout), _p(d_x_out), _p(d_A_out), _p(d_reg), _p(grads), _p(d_x_in), _p(d_A_in), stream)
         if rc != 0:
             raise RuntimeError('cgc_level_bwd failed with code %d' % rc)
         owner = cfg.get('owner')
@@ -357,33 +364,8 @@ def level(enc, desc, emb, pool, jk, g, gptr, x_in, A_in, assign=None, prep=None)
 def level_eval(enc, desc, emb, pool, jk, g, gptr, x_in, A_in, assign=None, prep=None):
     """Inference forward of one level through the sequencer (desc.eval = 1: BatchNorm on its running statistics, nothing kept): no
     autograd node, two arenas that die with the call.  Returns (readout, x_out, A_out) (+ (link, ent) as level()).  evaluate() (train.py:21-91) runs on this."""
-    lib = _lib()
-    K = kernels.get()
-    d = desc
-    dev = x_in.device
-    K._dev(x_in, A_in, gptr)
-    n_saved, n_scratch, _ = _sizes(d)
-    saved = torch.empty(n_saved, dtype=torch.float32, device=dev)
-    scratch = torch.empty(n_scratch, dtype=torch.float32, device=dev)
-    D = d.H if d.jk else 2 * d.H + d.E
-    readout = torch.empty(d.B, D, dtype=torch.float32, device=dev)
-    x_out = torch.empty(d.B, d.C, D, dtype=torch.float32, device=dev) if d.C else None
-    A_out = torch.empty(d.B, d.C, d.C, dtype=torch.float32, device=dev) if d.C else None
-    pe, pp, pj = prep['structs'] if prep else (_block_params(emb), _block_params(pool), _jk_params(jk))
-    gs = Graph()
-    if g is not None:
-        gs.rowptr, gs.col, gs.t_rowptr, gs.t_col = _p(g.rowptr), _p(g.col), _p(g.t_rowptr), _p(g.t_col)
-        gs.val, gs.t_val, gs.inv_d, gs.gorder = _p(g.val), _p(g.t_val), _p(g.inv_d), _p(g.gorder)
-        gs.spatial = int(bool(getattr(g, 'spatial', False)))
-    s_ptr, s_ld = P(), I()
-    reg = torch.empty(2, dtype=torch.float32, device=dev) if has_reg(d) else None
-    rc = lib.cgc_level_fwd_reg(C.byref(d), C.byref(pe), C.byref(pp), C.byref(pj), C.byref(gs), _p(gptr), _p(x_in), _p(A_in), _p(saved),
-                               _p(scratch), _p(readout), _p(x_out), _p(A_out), C.byref(s_ptr), C.byref(s_ld), _p(reg), K._stream())
-    if rc != 0:
-        raise RuntimeError('cgc_level_fwd (inference) failed with code %d' % rc)
-    if assign is not None and d.C:
-        off = (s_ptr.value - saved.data_ptr()) // 4
-        assign.append(torch.as_strided(saved, (d.n, d.C), (s_ld.value, 1), off).clone())
+    structs = prep['structs'] if prep else None
+    _, _, readout, x_out, A_out, reg = _level_fwd(desc, emb, pool, jk, g, gptr, x_in, A_in, structs, assign)
     if reg is not None:
         return readout, x_out, A_out, reg[0], reg[1]
     return readout, x_out, A_out
@@ -419,6 +401,13 @@ def _register_flat(enc, slot, params, offsets, total=None):
     enc._flat_sizes[slot] = int(total())
 
 
+def _register_head(owner, l1, l2):
+    """The head's flat-gradient layout (slot 0): dW1 | db1 | dW2 | db2, as cgc_head_bwd writes it."""
+    H1, Kin, L_ = l1.out_features, l1.in_features, l2.out_features
+    _register_flat(owner, 0, [l1.weight, l1.bias, l2.weight, l2.bias], lambda: [0, H1 * Kin, H1 * Kin + H1, H1 * Kin + H1 + L_ * H1],
+                   lambda: H1 * Kin + H1 + L_ * H1 + L_)
+
+
 def static_flat(enc):
     """Register the flat gradient layout of a model WITHOUT running it (it depends on widths only) and return the number of floats
     of the per-pass gradient buffer (native._grad_buffer), or None when the step sequencer does not cover the model as configured.
@@ -442,10 +431,7 @@ def static_flat(enc):
     layers = list(enc.pred_model) if isinstance(enc.pred_model, nn.Sequential) else [enc.pred_model]
     if len(layers) not in (3, 4) or not isinstance(layers[0], nn.Linear) or not isinstance(layers[-1], nn.Linear):
         return None
-    l1, l2 = layers[0], layers[-1]
-    H1, Kin, L_ = l1.out_features, l1.in_features, l2.out_features
-    _register_flat(enc, 0, [l1.weight, l1.bias, l2.weight, l2.bias], lambda: [0, H1 * Kin, H1 * Kin + H1, H1 * Kin + H1 + L_ * H1],
-                   lambda: H1 * Kin + H1 + L_ * H1 + L_)
+    _register_head(enc, layers[0], layers[-1])
     if len(enc._flat_sizes) != 4:
         return None
     return sum(-(-enc._flat_sizes[s_] // 64) * 64 for s_ in range(4))
@@ -454,10 +440,6 @@ def static_flat(enc):
 def flat_slot_offset(enc, slot):
     """First float of a slot inside the per-pass gradient buffer."""
     return sum(-(-enc._flat_sizes[s_] // 64) * 64 for s_ in range(slot))
-
-
-def dense_gptr(B, Cn, device):
-    return uniform_ptr(B, Cn, device)
 
 
 # ---- classification head + loss as one kernel each way (csrc/head.hip) ---------------------------------------------------------
@@ -560,7 +542,5 @@ def head(pred_model, readouts, labels, training, owner=None):
     # the mask is a function of (seed, element): the seed comes from torch's CPU generator (no device work; torch.manual_seed governs it)
     seed = int(torch.empty((), dtype=torch.int64).random_().item()) if drop_p > 0.0 else 0
     cfg = dict(act=ACT_CODES[act], drop_p=drop_p, seed=seed, labels=labels.view(-1).contiguous(), owner=owner)
-    H1, Kin, L_ = l1.out_features, l1.in_features, l2.out_features
-    _register_flat(owner, 0, [l1.weight, l1.bias, l2.weight, l2.bias], lambda: [0, H1 * Kin, H1 * Kin + H1, H1 * Kin + H1 + L_ * H1],
-                   lambda: H1 * Kin + H1 + L_ * H1 + L_)
+    _register_head(owner, l1, l2)
     return _Head.apply(cfg, l1.weight, l1.bias, l2.weight, l2.bias, *readouts)

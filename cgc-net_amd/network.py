@@ -349,7 +349,7 @@ class SoftPoolingGcnEncoder(nn.Module):
         self.native_head = os.environ.get('CGC_NATIVE_HEAD', '1') != '0'     # classification head + loss as one kernel each way
         self.reorder_large = os.environ.get('CGC_REORDER', '1') != '0'       # see _spatially_ordered
         # How the products on the 128 x 128 route -- from ~450 output tiles up: the six dominant products of a step (assignment Linear,
-        # S^T(AS), their backward: model/network.py:121-122, 206-207) -- are computed (include/cgc_hip.h: cgc_gemm_f32_ws):
+        # S^T(AS), their backward: model/network.py:121-122, 206-207) -- are computed (include/cgc_hip.h: cgc_gemm_f32):
         #   2 = kernels.GEMM_SPLIT_F16 (the module's default): three fp16 MFMA pairs of operands scaled per output tile
         #       (csrc/gemm_half.hip); those products 1.75x faster than exact, the step 1.37x;
         #   1 = kernels.GEMM_SPLIT_BF16: six bf16 MFMA pairs (csrc/gemm_split.hip; no scaling, no range caveat); 1.4x / 1.2x;

@@ -48,8 +48,13 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *      cgc_gemm_ws_floats() grew by the mode's scale slots: workspaces sized by an older library are too small for the tail split)
  *   6: added cgc_sgd_step, cgc_rmsprop_step (one-launch SGD and RMSprop on the tables of cgc_adam_step)
  *   7: DiffPool regularisers: cgc_level_desc.flags bit 3, cgc_level_fwd_reg, cgc_level_bwd_reg, cgc_diffpool_reg_ws_floats,
- *      cgc_diffpool_reg_fwd, cgc_diffpool_reg_bwd_prep, cgc_diffpool_reg_entropy_bwd, cgc_diffpool_reg_adj_bwd */
-#define CGC_ABI_VERSION 7
+ *      cgc_diffpool_reg_fwd, cgc_diffpool_reg_bwd_prep, cgc_diffpool_reg_entropy_bwd, cgc_diffpool_reg_adj_bwd
+ *   8: one entry point per operation.  Removed: cgc_gemm_f32_ws, cgc_gemm_f32_cat, cgc_gemm_f32_cat_ws, cgc_spmm_graphs_ordered,
+ *      cgc_bn_act_apply2, cgc_sage_narrow_bwd_ld, cgc_level_fwd_reg, cgc_level_bwd_reg.  The survivors take the signature of their
+ *      widest former sibling: cgc_gemm_f32 (of cgc_gemm_f32_cat_ws), cgc_spmm_graphs (of cgc_spmm_graphs_ordered), cgc_bn_act_apply
+ *      (of cgc_bn_act_apply2), cgc_sage_narrow_bwd (of cgc_sage_narrow_bwd_ld), cgc_level_fwd (of cgc_level_fwd_reg), cgc_level_bwd
+ *      (of cgc_level_bwd_reg) */
+#define CGC_ABI_VERSION 8
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -143,19 +148,16 @@ int cgc_spmm(const int* rowptr, const int* col, const int* perm, const float* va
  * of x the previous kernel left in the Infinity Cache -- bits 0-1: 0 unknown / ascending, 1 x was written in ascending row order,
  * 2 x was written by cgc_gemm_f32 as a ragged batch.  Bit 2 (+4, round 5): a NOTE that the nodes of every graph are listed grid cell
  * by grid cell (neighbours in space are neighbours in memory: data.spatial_order).  The gather kernel does not read the bit -- it is
- * the node order itself that makes its re-reads hit nearer caches (+3 % at C3, +30 % at C5).  Higher bits are ignored. */
+ * the node order itself that makes its re-reads hit nearer caches (+3 % at C3, +30 % at C5).  Higher bits are ignored.
+ * gorder[B] (NULL: ascending) lists the graphs in the order in which they are swept, the eight XCDs taking consecutive eighths.  For
+ * a few LARGE graphs of unequal size (the stress configuration: 32 graphs of 6400..9600 nodes, 4 per XCD) the host deals the graphs
+ * to the XCDs by size (graph.BatchGraph.gorder) so that every XCD gets the same number of rows.  The result does not depend on the
+ * sequence. */
 int cgc_spmm_graphs(const int* rowptr, const int* col, const int* perm, const float* val, const float* pre,
                     const float* post, const float* x, float* out, int n, int width, int ld /* row stride of x and out
                     (>= width): wide rows are kept at a multiple of 32 floats so that a 128-byte line never holds parts
-                    of two rows */, const int* gptr, int B, int nmax, int visit,
+                    of two rows */, const int* gptr, int B, int nmax, int visit, const int* gorder,
                     cgc_stream_t stream);
-/* The same with a caller-supplied visiting sequence: gorder[B] (NULL = as above) lists the graphs in the order in which they are
- * swept, the eight XCDs taking consecutive eighths.  For a few LARGE graphs of unequal size (the stress configuration: 32 graphs of
- * 6400..9600 nodes, 4 per XCD) the host deals the graphs to the XCDs by size (graph.BatchGraph.gorder) so that every XCD gets
- * the same number of rows.  The result does not depend on the sequence. */
-int cgc_spmm_graphs_ordered(const int* rowptr, const int* col, const int* perm, const float* val, const float* pre,
-                            const float* post, const float* x, float* out, int n, int width, int ld, const int* gptr, int B,
-                            int nmax, int visit, const int* gorder, cgc_stream_t stream);
 
 /* ---- A4/A5/A8: dense contractions on fp32 MFMA (v_mfma_f32_32x32x2_f32).  Replaces torch.matmul / nn.Linear at
  * model/network.py:122 (assignment Linear), :206-207 (S^T X, S^T A S), and the level-2/3 adj@x.
@@ -166,30 +168,22 @@ int cgc_spmm_graphs_ordered(const int* rowptr, const int* col, const int* perm, 
  * ragged=3 (uniform row chunks: split-K without an offset array): batch = outer * parts items, parts = ceil(K / max_ragged); item
  * (o, p) reduces over rows [o*K + p*max_ragged, o*K + min((p+1)*max_ragged, K)) of A (transA = 1) and B (transB = 0), the
  * flattened [outer*K, .] row blocks (strideA / strideB ignored), and writes C + (o*parts + p)*strideC: partial products for
- * cgc_reduce_batch_sum / cgc_reduce_batched. */
-int cgc_gemm_f32(int transA, int transB, int M, int N, int K, float alpha, const float* A, int lda,
-                 const float* B, int ldb, float beta, float* C, int ldc, const float* bias, int batch,
-                 int64_t strideA, int64_t strideB, int64_t strideC, const int* gptr, int ragged, int max_ragged,
-                 cgc_stream_t stream);
-
-/* Same, with up to two EXTRA operand pairs that continue the reduction: C_b = alpha*( op(A_b)op(B_b) + sum_s op(xA[s]_b)op(xB[s]_b) )
- * + beta*C_b (+bias), i.e. the product of column-concatenated A's with row-concatenated B's without materialising either
- * (assignment Linear over cat[x1,x2,x3], model/network.py:118-122; dS = P dA'^T + X dX'^T in _diff_pool's backward).
- * Extra pairs share op(), M, N, the batch and (ragged = 1) the row offsets of the main pair; xK[s] = their reduction length.
- * Host arrays of length nx (<= 2).  ragged = 2 is not supported here. */
-int cgc_gemm_f32_cat(int transA, int transB, int M, int N, int K, float alpha, const float* A, int lda,
-                     const float* B, int ldb, float beta, float* C, int ldc, const float* bias, int batch,
-                     int64_t strideA, int64_t strideB, int64_t strideC, const int* gptr, int ragged, int max_ragged,
-                     int nx, const float* const* xA, const int* xlda, const int64_t* xstrideA,
-                     const float* const* xB, const int* xldb, const int64_t* xstrideB, const int* xK, cgc_stream_t stream);
-/* The same two products with a SLAB WORKSPACE for the tail split of the 128 x 128 pipelined kernel (round 3): T output tiles on the
- * 512 workgroups the chip holds run in ceil(T / 512) rounds, and the last round lasts as long as a full one however few tiles it
- * holds (4140 tiles = 8.09 -> 9 rounds for the step's big products at 32 graphs, 522 tiles = 1.02 -> 2 rounds at 4 graphs per GPU).
- * With ws != NULL the T mod 512 tiles of the last round (all tiles when T < 512) are cut along K into up to 12 pieces each, every
- * piece parks its raw fp32 accumulators in a slab of ws, and a second kernel adds a tile's slabs IN PIECE ORDER and applies
- * alpha / beta / bias: deterministic (no atomics, no arrival order), no flags, no spinning.  ws: ws_floats >= cgc_gemm_ws_floats()
- * floats, contents irrelevant before and after; products on one stream may share it.  ws = NULL (or too small, or a product the
- * split does not apply to: short reductions, other tile shapes) behaves exactly as the plain entry points.
+ * cgc_reduce_batch_sum / cgc_reduce_batched.
+ *
+ * nx (<= 2) EXTRA operand pairs continue the reduction: C_b = alpha*( op(A_b)op(B_b) + sum_s op(xA[s]_b)op(xB[s]_b) ) + beta*C_b
+ * (+bias), i.e. the product of column-concatenated A's with row-concatenated B's without materialising either (assignment Linear
+ * over cat[x1,x2,x3], model/network.py:118-122; dS = P dA'^T + X dX'^T in _diff_pool's backward).  Extra pairs share op(), M, N, the
+ * batch and (ragged = 1) the row offsets of the main pair; xK[s] = their reduction length.  Host arrays of length nx; nx = 0: none
+ * (the arrays may be NULL).  ragged = 2 is not supported with extra pairs.
+ *
+ * ws: a SLAB WORKSPACE for the tail split of the 128 x 128 pipelined kernel (round 3): T output tiles on the 512 workgroups the chip
+ * holds run in ceil(T / 512) rounds, and the last round lasts as long as a full one however few tiles it holds (4140 tiles = 8.09 -> 9
+ * rounds for the step's big products at 32 graphs, 522 tiles = 1.02 -> 2 rounds at 4 graphs per GPU).  With ws != NULL the T mod 512
+ * tiles of the last round (all tiles when T < 512) are cut along K into up to 12 pieces each, every piece parks its raw fp32
+ * accumulators in a slab of ws, and a second kernel adds a tile's slabs IN PIECE ORDER and applies alpha / beta / bias: deterministic
+ * (no atomics, no arrival order), no flags, no spinning.  ws: ws_floats >= cgc_gemm_ws_floats() floats, contents irrelevant before
+ * and after; products on one stream may share it.  ws = NULL, ws_floats = 0 (or too small, or a product the split does not apply to:
+ * short reductions, other tile shapes): every output tile is computed whole.
  *
  * mode (round 5):  CGC_GEMM_EXACT -- the fp32 matrix-core chain (v_mfma_f32_32x32x2_f32: bitwise an fmaf chain), the default of every
  * caller;  CGC_GEMM_SPLIT_BF16 -- products that take the 128 x 128 route (both output extents > 128, reduction > 160, operands fit
@@ -197,7 +191,7 @@ int cgc_gemm_f32_cat(int transA, int transB, int M, int N, int K, float alpha, c
  * the six pairs above 2^-24 multiplied exactly and summed in fp32 (csrc/gemm_split.hip).  Same forms (NN / NT / TN, ragged 1 / 2 / 3,
  * extra K segments, beta, bias, tail split), same determinism; max and rms error against float64 within 1.25 x the exact kernel's
  * (tests/test_kernels_gpu.py::test_split_gemm_*).  Inputs must be finite; magnitudes below ~2^-108 lose the low planes.  Products the
- * mode does not apply to run on the exact kernel.  The plain entry points above are always exact.
+ * mode does not apply to run on the exact kernel.
  * CGC_GEMM_SPLIT_F16 (round 6, csrc/gemm_half.hip) -- the same products on the fp16 matrix cores in THREE passes: a first launch
  * takes max |x| over every output tile's operand panels (256 rows of op(A), 128 columns of op(B), all of K); every element, scaled
  * by the power of two that puts its panel's maximum in [2^14, 2^15), is split into two fp16 values h + l, the pairs l h, h l, h h
@@ -207,10 +201,16 @@ int cgc_gemm_f32_cat(int transA, int transB, int M, int N, int K, float alpha, c
  * that the element's ABSOLUTE error stops shrinking at 2^-40 of the panel's maximum (bound and measurements:
  * tests/test_half_gemm_gpu.py, tools/operand_range.py for the step's own operands).  Inputs must be finite (an infinite element
  * makes the tiles of its panel NaN).  1.25 x faster than CGC_GEMM_SPLIT_BF16 on the step's six products, operand pass included; products
- * too small for that (cgc_gemm_half_min_work) run as CGC_GEMM_SPLIT_BF16. */
+ * too small for that (cgc_gemm_half_min_work) run as CGC_GEMM_SPLIT_BF16.  Any other mode, or nx outside [0, 2]: CGC_EINVAL. */
 #define CGC_GEMM_EXACT 0
 #define CGC_GEMM_SPLIT_BF16 1
 #define CGC_GEMM_SPLIT_F16 2
+int cgc_gemm_f32(int transA, int transB, int M, int N, int K, float alpha, const float* A, int lda,
+                 const float* B, int ldb, float beta, float* C, int ldc, const float* bias, int batch,
+                 int64_t strideA, int64_t strideB, int64_t strideC, const int* gptr, int ragged, int max_ragged,
+                 int nx, const float* const* xA, const int* xlda, const int64_t* xstrideA,
+                 const float* const* xB, const int* xldb, const int64_t* xstrideB, const int* xK,
+                 float* ws, int64_t ws_floats, int mode, cgc_stream_t stream);
 int64_t cgc_gemm_split_count(void);   /* products this process has sent to the split kernel so far (diagnostic: did the mode apply?) */
 int64_t cgc_gemm_half_count(void);    /* ... and to the fp16 kernel of mode CGC_GEMM_SPLIT_F16 */
 int64_t cgc_gemm_half_ws_floats(void); /* the part of cgc_gemm_ws_floats() that mode CGC_GEMM_SPLIT_F16 needs by itself (scale slots, at the end) */
@@ -220,16 +220,6 @@ int64_t cgc_gemm_half_ws_floats(void); /* the part of cgc_gemm_ws_floats() that 
  * cgc_gemm_tuning: process-wide, not meant to be changed while products are in flight. */
 int64_t cgc_gemm_half_min_work(int64_t v);
 int64_t cgc_gemm_ws_floats(void);
-int cgc_gemm_f32_ws(int transA, int transB, int M, int N, int K, float alpha, const float* A, int lda,
-                    const float* B, int ldb, float beta, float* C, int ldc, const float* bias, int batch,
-                    int64_t strideA, int64_t strideB, int64_t strideC, const int* gptr, int ragged, int max_ragged,
-                    float* ws, int64_t ws_floats, int mode, cgc_stream_t stream);
-int cgc_gemm_f32_cat_ws(int transA, int transB, int M, int N, int K, float alpha, const float* A, int lda,
-                        const float* B, int ldb, float beta, float* C, int ldc, const float* bias, int batch,
-                        int64_t strideA, int64_t strideB, int64_t strideC, const int* gptr, int ragged, int max_ragged,
-                        int nx, const float* const* xA, const int* xlda, const int64_t* xstrideA,
-                        const float* const* xB, const int* xldb, const int64_t* xstrideB, const int* xK,
-                        float* ws, int64_t ws_floats, int mode, cgc_stream_t stream);
 /* Tuning hook for experiments (tools/gemm_cfg_sweep.py): cfg 1..6 forces the tile shape 128x128, 128x64, 64x128, 64x64, 128x32,
  * 32x128 for every following product of this process, +10 the pipelined kernel, +20 the short-K kernel; 0 restores the automatic
  * selection.  Returns the previous value.  Results do not depend on it (same arithmetic per output element up to tile-edge order). */
@@ -262,11 +252,9 @@ int cgc_l2norm_act_bn(const float* h, int n, int F, int normalize, int act, floa
  * (IEEE division and square root), for cgc_bn_act_apply. */
 int cgc_bn_running_stats(const float* running_mean, const float* running_var, int F, float eps, float* mean, float* istd,
                          cgc_stream_t stream);
+/* y [n, F] (row stride ldy) and, unless y2 is NULL, a second destination y2 [n, F] (row stride ldy2) receive the same values */
 int cgc_bn_act_apply(const float* hn, int n, int F, int act, const float* mean /*NULL: no BN*/, const float* istd,
-                     const float* gamma, const float* beta, float* y, int ldy, cgc_stream_t stream);
-/* cgc_bn_act_apply writing the same values to a second destination y2 [n, F] (row stride ldy2) as well (NULL: none) */
-int cgc_bn_act_apply2(const float* hn, int n, int F, int act, const float* mean, const float* istd, const float* gamma,
-                      const float* beta, float* y, int ldy, float* y2, int ldy2, cgc_stream_t stream);
+                     const float* gamma, const float* beta, float* y, int ldy, float* y2, int ldy2, cgc_stream_t stream);
 int cgc_bn_bwd_reduce(const float* dy, int ldy, const float* hn, int n, int F, int act, const float* mean,
                       const float* istd, float* sums /*[2,F]*/, float* ws, cgc_stream_t stream);
 /* mode: 2 batch statistics, 1 running statistics, 0 no BN */
@@ -344,20 +332,15 @@ int cgc_sage_narrow_fwd(const float* agg, int lda, const float* W, const float* 
 
 /* ---- backward of a NARROW SAGE projection y = BN(act(l2norm(agg W + b))) (the 13 hidden-width layers of a step,
  * model/network.py:109-125) in one kernel + one slot reduction: dy [n,F] (row stride ldy), hn, rinv, mode / mean / istd / gamma /
- * sums / count exactly as cgc_bn_act_l2_bwd; agg [n,fin] (row stride lda), W [fin,F].  Out: dagg [n,fin] = dh W^T (NULL: skipped),
- * dwdb [fin*F + F] = dW (= agg^T dh, row-major [fin,F]) followed by db (= column sums of dh); dh itself is never written.
+ * sums / count exactly as cgc_bn_act_l2_bwd; agg [n,fin] (row stride lda), W [fin,F].  Out: dagg [n,fin] = dh W^T (row stride
+ * ldd >= fin; NULL: skipped), dwdb [fin*F + F] = dW (= agg^T dh, row-major [fin,F]) followed by db (= column sums of dh); dh itself
+ * is never written.
  * ws: cgc_sage_narrow_ws_floats(n, fin, F) floats.  Envelope fin <= 32, F <= 32 -- otherwise CGC_EINVAL, nothing launched. */
 int64_t cgc_sage_narrow_ws_floats(int n, int fin, int F);
 int cgc_sage_narrow_bwd(const float* dy, int ldy, const float* hn, const float* rinv, int n, int F, int act, int normalize,
                         int mode, const float* mean, const float* istd, const float* gamma, const float* sums, double count,
-                        const float* agg, int lda, int fin, const float* W, float* dagg, float* dwdb, float* ws,
+                        const float* agg, int lda, int fin, const float* W, float* dagg, int ldd, float* dwdb, float* ws,
                         cgc_stream_t stream);
-
-/* cgc_sage_narrow_bwd with a row stride ldd (>= fin) for dagg */
-int cgc_sage_narrow_bwd_ld(const float* dy, int ldy, const float* hn, const float* rinv, int n, int F, int act, int normalize,
-                           int mode, const float* mean, const float* istd, const float* gamma, const float* sums, double count,
-                           const float* agg, int lda, int fin, const float* W, float* dagg, int ldd, float* dwdb, float* ws,
-                           cgc_stream_t stream);
 
 /* ---- A4/A6 at levels 2-3 (dense, real-valued adjacency that carries gradient) */
 int cgc_dense_rownorm_fwd(const float* A, int R, int C, float* out, float* invd, float* ge1, cgc_stream_t stream);
@@ -410,12 +393,12 @@ typedef struct {
                            * cgc_level_bwd refuses such a descriptor */
   int flags;              /* bit 0: reserved, must be 0 (rounds 4-5: an opt-in thin-operand form of the dense levels' adjacency gradient;
                            * it missed the 1e-4 gradient bar on two reference fixtures and was removed with ABI 4 -- DESIGN.md section 8);
-                           * bit 1: the level's products run with mode CGC_GEMM_SPLIT_BF16 (cgc_gemm_f32_ws): those on the 128 x 128
+                           * bit 1: the level's products run with mode CGC_GEMM_SPLIT_BF16 (cgc_gemm_f32): those on the 128 x 128
                            * route as six bf16 MFMA pairs per fp32 product.  Off by default;
                            * bit 2: the same with mode CGC_GEMM_SPLIT_F16 (three fp16 pairs); bits 1 and 2 exclude each other;
                            * bit 3: DiffPool regularisers (link and entropy losses of the level's pooling: cgc_diffpool_reg_fwd below).
-                           * Only on a level with an assignment block; needs cgc_level_fwd_reg / cgc_level_bwd_reg (the plain calls
-                           * refuse it).  Bits above 3 are unassigned and refused */
+                           * Only on a level with an assignment block; needs reg_out / d_reg of cgc_level_fwd / cgc_level_bwd
+                           * (NULL: the call is refused).  Bits above 3 are unassigned and refused */
 } cgc_level_desc;
 
 typedef struct {          /* one GNN_Module's parameters (DEVICE pointers; unused ones NULL) */
@@ -440,7 +423,7 @@ typedef struct {          /* level 1: what graph.BatchGraph holds */
   const int* rowptr; const int* col; const int* t_rowptr; const int* t_col;
   const float* val; const float* t_val;   /* NULL without _re_norm_adj */
   const float* inv_d;
-  const int* gorder;      /* NULL or the visiting sequence of cgc_spmm_graphs_ordered */
+  const int* gorder;      /* NULL or the visiting sequence of cgc_spmm_graphs */
   int spatial;            /* 1: every graph's nodes are listed grid cell by grid cell (cgc_spmm_graphs: visit bit 2) */
 } cgc_graph;
 
@@ -457,28 +440,21 @@ int64_t cgc_level_scratch_floats(const cgc_level_desc* d);             /* arena 
 int cgc_level_grad_layout_of(const cgc_level_desc* d, cgc_level_grad_layout* out);
 /* x_in [n, fin]; A_in [B, C, C] (levels 2-3; NULL at level 1); gptr [B+1] first row of every graph.
  * Out: readout [B, D] (D = H with jk, else 2H + E); x_out [B, C, D] and A_out [B, C, C] (levels 1-2); assign_out (optional, may be
- * NULL): receives the address of the assignment matrix S [n, C] inside `saved` and *assign_ld its row stride. */
+ * NULL): receives the address of the assignment matrix S [n, C] inside `saved` and *assign_ld its row stride.  reg_out [2] (device):
+ * with flags bit 3, the DiffPool regularisers of the level -- link, entropy loss as PyG's dense_diff_pool defines them
+ * (cgc_diffpool_reg_fwd); not read without bit 3 (may be NULL). */
 int cgc_level_fwd(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
                   const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, float* saved, float* scratch,
-                  float* readout, float* x_out, float* A_out, const float** assign_out, int* assign_ld, cgc_stream_t stream);
-/* d_readout [B, D]; d_x_out / d_A_out: gradients of x_out / A_out (NULL at level 3).  Out: grads (cgc_level_grad_layout_of),
- * d_x_in [n, fin] and d_A_in [B, C, C] (levels 2-3; NULL at level 1: the input features carry no gradient). */
+                  float* readout, float* x_out, float* A_out, const float** assign_out, int* assign_ld, float* reg_out,
+                  cgc_stream_t stream);
+/* d_readout [B, D]; d_x_out / d_A_out: gradients of x_out / A_out (NULL at level 3); d_reg [2] (device): with flags bit 3, the
+ * upstream gradients of reg_out (zeros when a loss does not reach the objective); not read without bit 3 (may be NULL).
+ * Out: grads (cgc_level_grad_layout_of), d_x_in [n, fin] and d_A_in [B, C, C] (levels 2-3; NULL at level 1: the input features
+ * carry no gradient). */
 int cgc_level_bwd(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
                   const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, const float* saved, float* scratch,
-                  const float* d_readout, const float* d_x_out, const float* d_A_out, float* grads, float* d_x_in, float* d_A_in,
-                  cgc_stream_t stream);
-
-/* DiffPool regularisers of one level (flags bit 3).  reg_out [2] (device): link, entropy loss as PyG's dense_diff_pool defines them
- * (cgc_diffpool_reg_fwd).  d_reg [2] (device): their upstream gradients (zeros when a loss does not reach the objective).  Otherwise
- * the arguments of cgc_level_fwd / cgc_level_bwd; without bit 3 these are those calls. */
-int cgc_level_fwd_reg(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
-                      const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, float* saved, float* scratch,
-                      float* readout, float* x_out, float* A_out, const float** assign_out, int* assign_ld, float* reg_out,
-                      cgc_stream_t stream);
-int cgc_level_bwd_reg(const cgc_level_desc* d, const cgc_block_params* emb, const cgc_block_params* pool, const cgc_jk_params* jk,
-                      const cgc_graph* g, const int* gptr, const float* x_in, const float* A_in, const float* saved, float* scratch,
-                      const float* d_readout, const float* d_x_out, const float* d_A_out, const float* d_reg, float* grads,
-                      float* d_x_in, float* d_A_in, cgc_stream_t stream);
+                  const float* d_readout, const float* d_x_out, const float* d_A_out, const float* d_reg, float* grads,
+                  float* d_x_in, float* d_A_in, cgc_stream_t stream);
 
 /* ==== DiffPool regularisers (csrc/diffpool_reg.hip), the passes around the products G = S^T S and S G.  For one pooling stage with
  * assignment S [n, C] (row stride lds), the stage's adjacency A, dense padding N, numel = B N N, rows = B N:

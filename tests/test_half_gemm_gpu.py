@@ -1,4 +1,4 @@
-"""GPU: mode CGC_GEMM_SPLIT_F16 of cgc_gemm_f32_ws / cgc_gemm_f32_cat_ws (csrc/gemm_half.hip: an fp32 product as three fp16 MFMA pairs
+"""GPU: mode CGC_GEMM_SPLIT_F16 of cgc_gemm_f32 (csrc/gemm_half.hip: an fp32 product as three fp16 MFMA pairs
 of operands scaled per batch item) in every form the step's dominant products take (model/network.py:121-122, 206-207), against
 float64, NEXT TO the exact fp32 kernel on the same inputs.  Yardstick as in test_split_gemm_gpu.py: error of an output element relative
 to sum_k |a_ik| |b_kj|.
@@ -383,9 +383,9 @@ def test_half_gemm_non_finite_input_stays_in_its_panels():
     assert float(((out[rows].double() - want).abs() / mag).max()) < 5e-7
 
 
-def test_half_mode_without_a_workspace_runs_the_exact_kernel():
-    """cgc_gemm_f32_ws with ws = NULL in mode CGC_GEMM_SPLIT_F16: no room for the scale slots -- the product runs on another kernel
-    (the bf16 one needs no workspace) instead of failing; the plain entry point cgc_gemm_f32 is always exact."""
+def test_gemm_f32_half_mode_without_a_workspace_runs_the_exact_kernel():
+    """cgc_gemm_f32 with ws = NULL in mode CGC_GEMM_SPLIT_F16: no room for the scale slots -- the product runs on another kernel
+    (the bf16 one needs no workspace) instead of failing."""
     import ctypes
     k = hip()
     M, N, K = 700, 300, 400
@@ -393,12 +393,13 @@ def test_half_mode_without_a_workspace_runs_the_exact_kernel():
     want, mag = A.double() @ B.double(), A.double().abs() @ B.double().abs()
     out = torch.empty(M, N, device=DEV)
     h0 = int(k.lib.cgc_gemm_half_count())
-    rc = k.lib.cgc_gemm_f32_ws(0, 0, M, N, K, ctypes.c_float(1.0), A.data_ptr(), K, B.data_ptr(), N, ctypes.c_float(0.0), out.data_ptr(), N, None, 1,
-                               ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), None, 0, 0, None, ctypes.c_int64(0), int(HALF),
-                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    no_x = (0,) + (None,) * 7                         # nx = 0: no extra K segments, NULL arrays
+    rc = k.lib.cgc_gemm_f32(0, 0, M, N, K, ctypes.c_float(1.0), A.data_ptr(), K, B.data_ptr(), N, ctypes.c_float(0.0), out.data_ptr(), N, None, 1,
+                            ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), None, 0, 0, *no_x, None, ctypes.c_int64(0), int(HALF),
+                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     assert rc == 0 and int(k.lib.cgc_gemm_half_count()) == h0
     assert float(((out.double() - want).abs() / mag).max()) < 5e-7
-    assert k.lib.cgc_gemm_f32_ws(0, 0, M, N, K, ctypes.c_float(1.0), A.data_ptr(), K, B.data_ptr(), N, ctypes.c_float(0.0), out.data_ptr(), N, None, 1,
-                                 ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), None, 0, 0, None, ctypes.c_int64(0), 3,
-                                 ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) != 0          # an unknown mode is refused
+    assert k.lib.cgc_gemm_f32(0, 0, M, N, K, ctypes.c_float(1.0), A.data_ptr(), K, B.data_ptr(), N, ctypes.c_float(0.0), out.data_ptr(), N, None, 1,
+                              ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), None, 0, 0, *no_x, None, ctypes.c_int64(0), 3,
+                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) != 0          # an unknown mode is refused

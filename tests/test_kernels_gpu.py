@@ -309,7 +309,7 @@ def test_spmm_forward_and_transpose(width, weighted):
 
 @pytest.mark.parametrize('visit', [0, 1, 2])
 def test_wide_spmm_visiting_sequences(visit):
-    """Order hints and a caller-supplied visiting sequence (cgc_spmm_graphs_ordered) are scheduling only: the same bits."""
+    """Order hints and a caller-supplied visiting sequence (cgc_spmm_graphs: gorder) are scheduling only: the same bits."""
     from cgc_net_amd.graph import BatchGraph
     rng = np.random.RandomState(visit)
     counts = [int(c) for c in rng.randint(20, 140, size=16)]
@@ -583,7 +583,7 @@ TAIL_CASES = [
 
 @pytest.mark.parametrize('rows,N,K,tA,tB,batch,ragged', TAIL_CASES)
 def test_gemm_tail_split(rows, N, K, tA, tB, batch, ragged):
-    """The tail split of the 128 x 128 kernel (include/cgc_hip.h: cgc_gemm_f32_ws): tiles of the last partial round cut along K
+    """The tail split of the 128 x 128 kernel (include/cgc_hip.h: cgc_gemm_f32): tiles of the last partial round cut along K
     into pieces + slab fix-up.  Against fp64, against the unsplit launch (same arithmetic per element up to the order of the
     K pieces), and bitwise repeatable; alpha / beta / bias / an extra K segment go through the fix-up's epilogue."""
     k = hip()

@@ -1,4 +1,4 @@
-"""GPU: mode CGC_GEMM_SPLIT_BF16 of cgc_gemm_f32_ws / cgc_gemm_f32_cat_ws (csrc/gemm_split.hip: an fp32 product as six bf16 MFMA
+"""GPU: mode CGC_GEMM_SPLIT_BF16 of cgc_gemm_f32 (csrc/gemm_split.hip: an fp32 product as six bf16 MFMA
 pairs) in every form the step's dominant products take -- the assignment Linear and _diff_pool's contractions with their backward
 (model/network.py:121-122, 206-207) -- against float64, NEXT TO the exact fp32 kernel on the same inputs.
 

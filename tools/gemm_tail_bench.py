@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """The six dominant contractions of a step (C1 = 1140) at 4 / 8 / 16 / 32 graphs per GPU, with and without the tail split of the
-128 x 128 kernel (cgc_gemm_f32_ws): time per launch and TFLOP/s.  usage: tools/gemm_tail_bench.py [B ...]"""
+128 x 128 kernel (cgc_gemm_f32): time per launch and TFLOP/s.  usage: tools/gemm_tail_bench.py [B ...]"""
 import os
 import sys
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The six dominant products of a 32-graph step (profiles/r04_gemm_calls_by_shape.txt), stand-alone, in both modes of cgc_gemm_f32_ws:
+"""The six dominant products of a 32-graph step (profiles/r04_gemm_calls_by_shape.txt), stand-alone, in both modes of cgc_gemm_f32:
 exact (fp32 MFMA chain), split (six bf16 MFMA pairs, csrc/gemm_split.hip) and half (three fp16 pairs of scaled operands, csrc/gemm_half.hip;
 its time includes the operand-maximum pass).  Operands on the row strides the step uses.  Per product:
 time of a launch (mean over `reps` back-to-back launches after a long warm-up: the clock ramps over milliseconds), fp32-equivalent
