@@ -21,13 +21,19 @@ each, cluster counts fixed by the reference's ``setting.max_num_nodes`` = 11404 
 (setting.py:15, train.py:254), model flags as shipped in parallel_train.sh (--jk --norm_adj --drop 0.2; ``--flags plain``
 turns the three off).  ``--maxn 1800`` gives the "clusters proportional to the graph" variant (C1 = 180).
 
+A plain run does only what the headline needs: set up, W warm-up + K timed steps, ``--dump-outputs`` if given, the line.
+``--full`` adds what takes runs of its own, after the headline leg: at N=1 the split-bf16 and fp16 legs (``value_split``,
+``value_half`` and their rooflines; ``--no-split-leg`` drops them) and the CPU baseline (``--no-cpu-baseline`` drops it).  The
+headline leg, its timed steps and what it dumps are the same with or without ``--full``; N>1 runs the legs ``--scaling`` names
+either way.
+
 Extra objects on the line:
   roofline            dominant kernel = the 128x128 pipelined fp32-MFMA GEMM k_gemm_f32<2,2,2,2,*> (bound "mfma", peak
                       157.3 TFLOP/s): algorithmic flops 2MNK of every launch of it / HIP-event duration of that launch,
                       measured inside the timed region (rocprofv3 --stats: average over its three instantiations)
   roofline_aggregation  the wide neighbour-aggregation SpMM A*S ("K4", bound "hbm", peak 8000 GB/s): algorithmic
                       bytes 4(n+1) + 4 nnz (+4 nnz weighted) + 8 n W per launch / HIP-event duration
-  cpu_baseline        the dense CPU oracle (the reference's algorithm incl. densification; oracle/dense_ref.py)
+  cpu_baseline        ``--full`` only: the dense CPU oracle (the reference's algorithm incl. densification; oracle/dense_ref.py)
                       timed on the host cores, rank 0, N=1 only, on a bounded sample of the same workload
   dump_outputs        with ``--dump-outputs DIR`` only: where the outputs of the headline leg's last timed step were written
                       (inputs and initial weights are seeded: the same arguments give the same inputs in every run, so two builds
@@ -73,13 +79,17 @@ def parse():
     p.add_argument('--spatial', action='store_true',
                    help='list the nuclei of every graph grid cell by grid cell (data.spatial_order) instead of in draw order')
     p.add_argument('--pool', type=int, default=4, help='distinct resident batches cycled through')
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--full', action='store_true',
+                   help='N=1: after the headline leg, also run the split-bf16 and fp16 legs and the CPU baseline (each can be dropped '
+                        'with its --no-* option); without it the run does only what the headline needs')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     p.add_argument('--cpu-warmup', type=int, default=3, help='CPU baseline: untimed warm-up steps')
     p.add_argument('--cpu-steps', type=int, default=5, help='CPU baseline: timed steps')
     p.add_argument('--no-kernel-timing', action='store_true', help='do not record per-launch HIP events')
     p.add_argument('--no-split-leg', action='store_true',
-                   help='N=1: skip the second leg that runs the same W + K steps with the six dominant products in mode CGC_GEMM_SPLIT_BF16 '
-                        '(reported beside the headline as value_split / roofline_split; the headline is always the exact fp32 kernel)')
+                   help='--full, N=1: skip the legs that run the same W + K steps with the six dominant products in modes CGC_GEMM_SPLIT_BF16 '
+                        'and CGC_GEMM_SPLIT_F16 (reported beside the headline as value_split / roofline_split, value_half / roofline_half; '
+                        'the headline is always the exact fp32 kernel)')
     p.add_argument('--gemm-mode', type=int, default=0, help='experiments: mode of the HEADLINE leg (0 exact, 1 split bf16, 2 three fp16 pairs); the JSON says so')
     p.add_argument('--no-gc', action='store_true',
                    help="experiment: Python's cyclic garbage collector off during the timed steps (gc.disable() after a gc.collect()): does "
@@ -278,7 +288,7 @@ def main():
     # ---- synthetic workload: `pool` distinct batches, resident in HBM.  weak: per rank, seeded by rank; strong: the SAME
     # global batches on every rank, each rank keeping its chunk of the cumulative-node-count split (data.partition_by_nodes)
     from cgc_net_amd.data import partition_by_nodes
-    legs = (['single'] + ([] if args.no_split_leg else ['split', 'half'])) if world == 1 else (['strong', 'weak'] if args.scaling == 'both' else [args.scaling])
+    legs = (['single'] + (['split', 'half'] if args.full and not args.no_split_leg else [])) if world == 1 else (['strong', 'weak'] if args.scaling == 'both' else [args.scaling])
 
     def make_batches(leg):
         strong_ = leg == 'strong'
@@ -551,7 +561,7 @@ def main():
                                                             'mfma_busy x sustained clock / 2.4 GHz)' % fname)
                         else:
                             out[obj]['mfma_busy_stale'] = True
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args, cpu_batches)
         if args.dump_outputs is not None:
             out['dump_outputs'] = write_outputs(args.dump_outputs, head['outputs'])

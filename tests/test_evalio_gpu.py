@@ -247,6 +247,33 @@ def test_bench_dump_outputs_are_the_same_run_after_run(tmp_path):
     for n, (a, b) in arrays.items():
         assert a.dtype == np.float32 and np.array_equal(a, b), n
 
+
+def test_bench_full_adds_the_extra_legs_and_cpu_baseline():
+    """A plain ``--gpus 1`` run measures the headline leg alone; ``--full`` adds the split-bf16 and fp16 legs (each with its own W + K
+    steps) and the CPU baseline beside it, in the same one JSON line."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    extra = ('value_split', 'ms_per_step_split', 'value_half', 'ms_per_step_half', 'cpu_baseline')
+    recs = {}
+    for mode in ('plain', 'full'):
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '4', '--nodes', '300',
+               '--maxn', '600', '--pool', '2', '--cpu-warmup', '1', '--cpu-steps', '1'] + (['--full'] if mode == 'full' else [])
+        out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        recs[mode] = json.loads(lines[0])
+    for rec in recs.values():
+        assert rec['steps'] == 2 and rec['value'] > 0 and rec['ms_per_step'] > 0 and rec['dtype'] == 'f32' and rec['higher_is_better']
+    assert not any(k in recs['plain'] for k in extra)
+    full = recs['full']
+    assert all(k in full for k in extra)
+    assert full['value_split'] > 0 and full['value_half'] > 0 and full['cpu_baseline']['value'] > 0
+
+
 def test_one_epoch_example_runs_the_reference_training_loop():
     """BASELINE.json configs[0]/[1] plumbing: examples/train_synthetic.py = the reference's loop (train.py:174-184: model(data) ->
     torch.mean(cls_loss) -> zero_grad / backward / step, StepLR, evaluate) over 200 synthetic graphs of ~300 nodes, shipped flags
