@@ -3,7 +3,7 @@ import ctypes as C
 
 P, I, F, D, L = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_int64
 
-ABI_VERSION = 8      # = CGC_ABI_VERSION of include/cgc_hip.h these prototypes were written against (tests compare the two)
+ABI_VERSION = 9      # = CGC_ABI_VERSION of include/cgc_hip.h these prototypes were written against (tests compare the two)
 
 PROTOTYPES = {
     'cgc_abi_version': [],
@@ -15,6 +15,12 @@ PROTOTYPES = {
     'cgc_radius_knn_ws_ints': [I, I],
     'cgc_radius_knn': [P, P, I, I, F, I, I, P, P, P, P, P],
     'cgc_knn_emit_edges': [P, P, I, I, L, P, P],
+    'cgc_nuclei_lds_max_pixels': [],
+    'cgc_nuclei_ws_bytes': [I],
+    'cgc_nuclei_label_pass': [P, I, I, I, I, P, P, P, P],
+    'cgc_nuclei_big_ws_bytes': [I, L],
+    'cgc_nuclei_features': [P, P, I, I, I, I, P, P, I, I, L, P, P, P, P, P],
+    'cgc_bgr_to_gray': [P, L, P, P],
     'cgc_edge_renorm': [P, P, I, F, P, P],
     'cgc_csr_transpose_vals': [P, P, P, I, P, P],
     'cgc_csr_invdeg': [P, P, I, P, P],
@@ -108,4 +114,4 @@ def declare(lib):
         if name == 'cgc_timing_create':
             fn.restype = P          # a handle, not a status
             continue
-        fn.restype = C.c_int64 if name.endswith(('_ws_ints', '_ws_floats', '_offset', '_grad_floats', '_saved_floats', '_scratch_floats', '_split_count', '_half_count', '_min_work')) else C.c_int
+        fn.restype = C.c_int64 if name.endswith(('_ws_ints', '_ws_floats', '_offset', '_grad_floats', '_saved_floats', '_scratch_floats', '_split_count', '_half_count', '_min_work', '_ws_bytes')) else C.c_int

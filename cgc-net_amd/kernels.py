@@ -56,6 +56,45 @@ class KernelSpec(object):
         distance, ties by index) with global node ids."""
         raise NotImplementedError
 
+    def nucleus_features(self, labels, gray, max_label, min_size, with_info=False):
+        """Nucleus feature rows and centroids of one instance mask (F4: dataflow/construct_feature_graph.py:50-123 +
+        common/nuc_feature.py).  labels int32 [H, W] (0 = background, values in [0, max_label]), gray uint8 [H, W], H * W < 2^31.
+        Returns (features f32 [n, 16], centroids f32 [n, 2], kept_labels int32 [n], info int32 [n, 4] or None); reads n on the host.
+
+        1.  remove_small_objects(mask, min_size) of skimage 0.15 on a label image: labels with fewer than min_size pixels in the whole
+            image become background; no relabelling, the connectivity is irrelevant.
+        2.  One row per surviving label, ascending; a label of several pieces is one row.  centroid = (mean row, mean column) of its
+            pixels; bbox = (r0, c0, r1 + 1, c1 + 1).
+        3.  Crop (quirk): rows r0 .. r1 + 1, columns c0 .. c1 + 1, clipped at the image edge; crop mask = pixels of ANY surviving
+            label (neighbours' pixels count as foreground in everything below).
+        4.  mean_im_out = sum fg / (n_fg + 1e-8); diff = |mean_im_out - sum bg / (n_bg + 1e-8)|; var_im = population variance of fg;
+            skew_im = m3 / m2^1.5 (biased), 0 when m2 = 0 -- over gray in the crop.
+        5.  mean_ent = mean over the crop mask of skimage.filters.rank.entropy(gray, disk(3)): per pixel the histogram of the <= 29
+            in-image values with dy^2 + dx^2 <= 9, -sum p log2 p.
+        6.  GLCM of gray * mask with offset (0, +1), 256 levels, not symmetric: row and column 0 dropped, normalised by the remaining
+            total (0 -> 1); dissimilarity sum P |i - j|, homogeneity sum P / (1 + (i - j)^2), ASM sum P^2, energy sqrt(ASM).
+        7.  Contour (quirk, cv2.findContours(RETR_TREE)[0][0]): among the 8-connected components of the crop mask that are top-level
+            -- the background pixel left of the raster-first pixel is 4-connected to the outside (the crop is padded by background) --
+            the one whose raster-first pixel comes last.  It may be a fragment of a neighbour.
+        8.  Suzuki 8-connected border following from that pixel, CHAIN_APPROX_SIMPLE vertices (direction changes; the start kept).
+        9.  area = |shoelace| (0 below 3 vertices); hull_area of the vertices (0 -> 1); solidity = area / hull_area; perimeter = closed
+            polygon length with float32 edge lengths summed in double; with more than 4 vertices fitEllipse gives major = max, minor =
+            min of the box sizes and orientation = the box angle, otherwise 1, 1, 0; eccentricity = sqrt(1 - (minor / major)^2).
+        10. fitEllipse = OpenCV 4.1 fitEllipseNoDirect: least squares [-x^2, -y^2, -xy, x, y] g = const on centred points (min-norm),
+            centre from [[2 g0, g2], [g2, 2 g1]] c = (g3, g4), refit [(x-cx)^2, (y-cy)^2, (x-cx)(y-cy)] h = 1, theta = -atan2(h2,
+            h1 - h0) / 2, t = h2 / sin(-2 theta) (h1 - h0 when |h2| <= 1e-8), radii sqrt(2 / |h0 + h1 -+ t|) (when > 1e-8), box (2 r2, 2 r3),
+            swapped with angle 90 + theta in degrees when the width exceeds the height, else angle 0.  Directions whose singular value
+            is below 1e-6 of the largest are dropped (OpenCV perturbs such point sets instead: not pinned).
+        11. Columns: mean_im_out, diff, var_im, skew_im, mean_ent, glcm_dissimilarity, glcm_homogeneity, glcm_energy, glcm_ASM,
+            eccentricity, area, majoraxis_length, minoraxis_length, perimeter, solidity, orientation.
+        info (with_info): start row, start column of the contour in the crop, its vertex count, path (0 LDS, 1 global workspace).
+        Pixels with a label outside [0, max_label] raise ValueError (the reference raises for negative labels)."""
+        raise NotImplementedError
+
+    def bgr_to_gray(self, bgr):
+        """cv2.cvtColor(img, COLOR_BGR2GRAY) on uint8 [H, W, 3]: (1868 B + 9617 G + 4899 R + 8192) >> 14 -> uint8 [H, W]."""
+        raise NotImplementedError
+
     def edge_renorm(self, rowptr, col, n, p, val_out):
         """Level-1 ``_re_norm_adj`` (model/network.py:183-191) on a 0/1 CSR that holds its diagonal:
         val[k] = p if col[k]==row else (1/(c+1e-15))*(1-p), c = number of off-diagonal entries of the row."""
@@ -523,6 +562,37 @@ class HipKernels(KernelSpec):
         self._chk(self.lib.cgc_knn_emit_edges(_ptr(nbr), _ptr(rowptr), n, k, ctypes.c_int64(nnz), _ptr(ei), self._stream()),
                   'cgc_knn_emit_edges')
         return ei
+
+    def nucleus_features(self, labels, gray, max_label, min_size, with_info=False):
+        self._dev(labels, gray)
+        assert labels.dtype == torch.int32 and gray.dtype == torch.uint8 and labels.dim() == 2 and labels.shape == gray.shape
+        labels, gray = labels.contiguous(), gray.contiguous()
+        H, W = labels.shape
+        dev = labels.device
+        u8, i32, f32 = (dict(dtype=d, device=dev) for d in (torch.uint8, torch.int32, torch.float32))
+        ws = torch.empty(int(self.lib.cgc_nuclei_ws_bytes(max_label)), **u8)
+        kept = torch.empty(max(max_label, 1), **i32)
+        meta = torch.empty(4, **i32)
+        self._chk(self.lib.cgc_nuclei_label_pass(_ptr(labels), H, W, max_label, int(min_size), _ptr(ws), _ptr(kept), _ptr(meta),
+                                                 self._stream()), 'cgc_nuclei_label_pass')
+        n, nbig, big_px, refused = meta.tolist()        # the host sync of this stage: the row count
+        if refused:
+            raise ValueError('%d pixels carry a label outside [0, %d]' % (refused, max_label))
+        feats, cen = torch.empty(n, 16, **f32), torch.empty(n, 2, **f32)
+        info = torch.empty(n, 4, **i32) if with_info else None
+        big_ws = torch.empty(int(self.lib.cgc_nuclei_big_ws_bytes(nbig, ctypes.c_int64(big_px))), **u8) if nbig else None
+        self._chk(self.lib.cgc_nuclei_features(_ptr(labels), _ptr(gray), H, W, max_label, int(min_size), _ptr(ws), _ptr(kept), n, nbig,
+                                               ctypes.c_int64(big_px), _ptr(big_ws), _ptr(feats), _ptr(cen), _ptr(info), self._stream()),
+                  'cgc_nuclei_features')
+        return feats, cen, kept[:n], info
+
+    def bgr_to_gray(self, bgr):
+        self._dev(bgr)
+        assert bgr.dtype == torch.uint8 and bgr.dim() == 3 and bgr.shape[2] == 3
+        bgr = bgr.contiguous()
+        out = torch.empty(bgr.shape[0], bgr.shape[1], dtype=torch.uint8, device=bgr.device)
+        self._chk(self.lib.cgc_bgr_to_gray(_ptr(bgr), ctypes.c_int64(out.numel()), _ptr(out), self._stream()), 'cgc_bgr_to_gray')
+        return out
 
     def edge_renorm(self, rowptr, col, n, p, val_out):
         self._dev(rowptr, col, val_out)

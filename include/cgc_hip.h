@@ -53,8 +53,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *      cgc_bn_act_apply2, cgc_sage_narrow_bwd_ld, cgc_level_fwd_reg, cgc_level_bwd_reg.  The survivors take the signature of their
  *      widest former sibling: cgc_gemm_f32 (of cgc_gemm_f32_cat_ws), cgc_spmm_graphs (of cgc_spmm_graphs_ordered), cgc_bn_act_apply
  *      (of cgc_bn_act_apply2), cgc_sage_narrow_bwd (of cgc_sage_narrow_bwd_ld), cgc_level_fwd (of cgc_level_fwd_reg), cgc_level_bwd
- *      (of cgc_level_bwd_reg) */
-#define CGC_ABI_VERSION 8
+ *      (of cgc_level_bwd_reg)
+ *   9: nucleus features from instance masks: cgc_nuclei_lds_max_pixels, cgc_nuclei_ws_bytes, cgc_nuclei_label_pass,
+ *      cgc_nuclei_big_ws_bytes, cgc_nuclei_features, cgc_bgr_to_gray */
+#define CGC_ABI_VERSION 9
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -104,6 +106,32 @@ int cgc_radius_knn(const float* pos, const int* gptr, int B, int n, float r, int
 /* ELL rows of cgc_radius_knn -> edge_index [2, nnz] int64 (row = centre, ascending; col = neighbour), the layout
  * Batch.from_data_list / cgc_csr_build consume (dataflow/data.py:347-353). */
 int cgc_knn_emit_edges(const int* nbr, const int* rowptr, int n, int k, int64_t nnz, int64_t* edge_index, cgc_stream_t stream);
+
+/* ---- F4 (the first front-end step): nucleus features and centroids from an instance mask (csrc/nuclei.hip).  Replaces
+ * dataflow/construct_feature_graph.py:50-123 + common/nuc_feature.py (remove_small_objects, regionprops, the per-nucleus crop statistics,
+ * rank entropy, GLCM, findContours / contourArea / convexHull / arcLength / fitEllipse); the arithmetic item by item:
+ * cgc-net_amd/kernels.py KernelSpec.nucleus_features.  labels int32 [H, W] (0 = background), gray uint8 [H, W]; H * W < 2^31.
+ * Two calls around ONE host read of meta:
+ *   cgc_nuclei_label_pass: ws = cgc_nuclei_ws_bytes(max_label) bytes (tables indexed by label value: max_label >= the largest label);
+ *     kept_labels int32 [max_label] receives the surviving labels (count >= min_size) in ascending order; meta int32 [4] (device) =
+ *     {n rows, nbig crops above the LDS path, pixels of the largest such crop, refused pixels}.  A pixel whose label is negative or above
+ *     max_label is counted in meta[3] and ignored (the reference raises ValueError for a negative label).
+ *   cgc_nuclei_features: the same labels / ws / kept_labels, n, nbig and max_big_px = meta[0..2] read on the host; big_ws =
+ *     cgc_nuclei_big_ws_bytes(nbig, max_big_px) bytes (NULL when nbig = 0).  Out: features f32 [n, 16] (the reference's column order),
+ *     centroids f32 [n, 2] (mean row, mean column), info int32 [n, 4] or NULL: start row / column of the traced contour in the crop,
+ *     its vertex count (negative: the trace overran its workspace -- never expected), path (0 LDS, 1 global workspace).
+ * A crop of at most cgc_nuclei_lds_max_pixels() (2048) pixels is processed in LDS, a larger one on a slot of big_ws.
+ * cgc_bgr_to_gray: cv2.cvtColor(BGR2GRAY) on 8-bit data, gray[i] = (1868 B + 9617 G + 4899 R + 8192) >> 14 for npix pixels of
+ * bgr uint8 [npix, 3]; no workspace. */
+int cgc_nuclei_lds_max_pixels(void);
+int64_t cgc_nuclei_ws_bytes(int max_label);
+int cgc_nuclei_label_pass(const int* labels, int H, int W, int max_label, int min_size, void* ws, int* kept_labels, int* meta,
+                          cgc_stream_t stream);
+int64_t cgc_nuclei_big_ws_bytes(int nbig, int64_t max_big_px);
+int cgc_nuclei_features(const int* labels, const uint8_t* gray, int H, int W, int max_label, int min_size, const void* ws,
+                        const int* kept_labels, int n, int nbig, int64_t max_big_px, void* big_ws, float* features, float* centroids,
+                        int* info, cgc_stream_t stream);
+int cgc_bgr_to_gray(const uint8_t* bgr, int64_t npix, uint8_t* gray, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
