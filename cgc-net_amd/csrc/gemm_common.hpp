@@ -1,5 +1,6 @@
-// Shared pieces of the matrix-core GEMM kernels (gemm.hip: exact fp32 MFMA; gemm_split.hip: fp32 products as six bf16 MFMA pairs):
-// argument block, tile map with tail split, per-item operand bases, the epilogue through LDS, the fix-up kernel of the tail split.
+// Shared pieces of the matrix-core GEMM kernels (gemm.hip: exact fp32 MFMA; gemm_split.hip: fp32 products as six bf16 MFMA pairs;
+// gemm_half.hip: as three fp16 MFMA pairs): argument block, operand-segment table, tile map with tail split, per-item operand bases,
+// the epilogue through LDS, the fix-up kernel of the tail split.
 #pragma once
 #include <type_traits>
 
@@ -25,7 +26,8 @@ struct GemmArgs {
   int resident;   // workgroups the chip holds at once = the quantum of a "round"
   int chunk;      // ragged 3: rows per part
   int s_max;      // most pieces a tail tile is cut into
-  const unsigned* scale;   // gemm_half.hip only: bits of max |A|, max |B| per batch item (2 per item); nullptr elsewhere
+  const unsigned* scale;   // gemm_half.hip only: bits of max |A| per (batch item, 256-row tile) and of max |B| per (batch item, 128-column
+                           // tile), i.e. per output tile's operand panels (slot layout: k_gemm_absmax); nullptr elsewhere
   // optional extra K segments: C += alpha * A_x[s] * B_x[s] (same op() orientation, M, N as the main pair), i.e. the
   // product of the column-concatenated [A | A_x0 | A_x1] with the row-concatenated [B ; B_x0 ; B_x1] without ever
   // materialising the concatenation (Linear over cat[x1,x2,x3]; dS = P dA'^T + X dX'^T)
@@ -46,28 +48,39 @@ __device__ __forceinline__ const float* sgpr_ptr(const float* p) {     // a wave
   return reinterpret_cast<const float*>(((uintptr_t)hi << 32) | lo);
 }
 
-// Branch-free fetch of ANY k-tile -- a full or partial tile of the main operand pair or of an extra K segment -- for the
-// prologue and the tail of the k loop of k_gemm_f32<FAST>: the segment (base pointers, row strides, reduction length) is picked
-// with scalar selects and both operands take the masked unguarded loads.  A free function over a table of VALUES: as a lambda
-// capturing by reference inside the phase lambda its closure (a struct of pointers to locals) survived into the generated code
-// and put the locals it referred to in scratch memory.
+// Which k-tile (of KT) of which operand segment: the main pair, then the extra K segments (GemmArgs::nx).  The segment (base pointers,
+// row strides, reduction length) is picked with scalar selects: ANY k-tile -- full or partial, main pair or extra segment -- is fetched
+// without a branch (the prologue and the tail of the k loops of k_gemm_f32<FAST>, gemm_split_common.hpp).  Free functions over a
+// table of VALUES: as a lambda capturing by reference inside the phase lambda its closure (a struct of pointers to locals) survived
+// into the generated code and put the locals it referred to in scratch memory.
 struct SegTable {
   const float *A0, *A1, *A2, *B0, *B1, *B2;
   int lda0, lda1, lda2, ldb0, ldb1, ldb2, K0, K1, K2;
   int nk_main, nkx0;
 };
-template <class LoaderA, class LoaderB>
-__device__ __forceinline__ void fetch_seg(LoaderA& la, LoaderB& lb, const SegTable t, int kt, int m0, int a_last, int n0, int b_last) {
+struct SegTile {
+  const float* A;
+  const float* B;
+  int lda, ldb, klim, k0;
+};
+template <int KT>
+__device__ __forceinline__ SegTile seg_tile(const SegTable t, int kt) {
   const int kx = kt - t.nk_main;
   const bool in_main = kx < 0, in_x0 = kx < t.nkx0;
-  const float* Ap = in_main ? t.A0 : in_x0 ? t.A1 : t.A2;
-  const float* Bp = in_main ? t.B0 : in_x0 ? t.B1 : t.B2;
-  const int lda = in_main ? t.lda0 : in_x0 ? t.lda1 : t.lda2;
-  const int ldb = in_main ? t.ldb0 : in_x0 ? t.ldb1 : t.ldb2;
-  const int Ks = in_main ? t.K0 : in_x0 ? t.K1 : t.K2;
-  const int k0 = (in_main ? kt : in_x0 ? kx : kx - t.nkx0) * BK;
-  la.load_fast_masked(Ap, lda, m0, a_last, k0, Ks);
-  lb.load_fast_masked(Bp, ldb, n0, b_last, k0, Ks);
+  SegTile r;
+  r.A = in_main ? t.A0 : in_x0 ? t.A1 : t.A2;
+  r.B = in_main ? t.B0 : in_x0 ? t.B1 : t.B2;
+  r.lda = in_main ? t.lda0 : in_x0 ? t.lda1 : t.lda2;
+  r.ldb = in_main ? t.ldb0 : in_x0 ? t.ldb1 : t.ldb2;
+  r.klim = in_main ? t.K0 : in_x0 ? t.K1 : t.K2;
+  r.k0 = (in_main ? kt : in_x0 ? kx : kx - t.nkx0) * KT;
+  return r;
+}
+template <class LoaderA, class LoaderB>
+__device__ __forceinline__ void fetch_seg(LoaderA& la, LoaderB& lb, const SegTable t, int kt, int m0, int a_last, int n0, int b_last) {
+  const SegTile s = seg_tile<BK>(t, kt);         // both operands take the masked unguarded loads
+  la.load_fast_masked(s.A, s.lda, m0, a_last, s.k0, s.klim);
+  lb.load_fast_masked(s.B, s.ldb, n0, b_last, s.k0, s.klim);
 }
 
 // Which (batch, tile) a workgroup computes.  Speed only -- every tile is computed exactly once whatever the hardware's dispatch

@@ -28,7 +28,6 @@
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-constexpr int H_PLA = S_BM * SROW, H_PLB = S_BN * SROW, H_STAGE = 2 * H_PLA + 2 * H_PLB, H_LDS = 2 * H_STAGE;   // 73728 bytes
 // scale slots at the end of the caller's workspace (floats reserved: cgc_gemm_ws_floats() counts them): max |A| per (batch item, 256-row
 // tile), max |B| per (batch item, 128-column tile)
 constexpr int H_SCALE_FLOATS = 65536;
@@ -64,274 +63,108 @@ __device__ __forceinline__ void half_scale(unsigned maxbits, float& s, float& in
   inv = __builtin_bit_cast(float, (unsigned)(254 - ex) << 23);
 }
 
-// ---- the split of one group of four values in four micro-steps (sidx = 4 * group + step; groups 0-3: operand A, 4-5: operand B)
-struct HalfGroup {
-  float x[4], r[4];
-  unsigned hp[2], lp[2];
-};
-template <class LoaderA, class LoaderB, bool MASKED>
-__device__ __forceinline__ void half_micro(int sidx, HalfGroup (&gs)[6], const float4 (&ra)[LoaderA::NF], const float4 (&rb)[LoaderB::NF],
-                                           unsigned char* wa, unsigned char* wb, int k0, int klim, float sa, float sb) {
-  const int u = sidx >> 2, st = sidx & 3;
-  HalfGroup& s = gs[u];
-  if (st == 0) {
-    if (u < 4) LoaderA::get(ra, u, s.x); else LoaderB::get(rb, u - 4, s.x);
-    const float sc = u < 4 ? sa : sb;
+// What the pipeline of gemm_split_common.hpp (split_gemm_body; gemm_split.hip's header has its reasons) does in this number format:
+// two planes, 24 MFMAs per k-tile
+struct F16x2 : SplitPlanes<2> {                       // LDS: 73728 bytes
+  // the scales of the tile's two operand panels and their reciprocals
+  struct Scale {
+    float sa, sb, isa, isb;
+    __device__ __forceinline__ Scale(const GemmArgs& a, int b, int tile_m, int tile_n) {
+      const int ta = a.per_batch / a.tiles_n;                    // row tiles of the largest item: the slot layout of k_gemm_absmax
+      const unsigned* sc = a.scale + (size_t)b * (ta + a.tiles_n);
+      half_scale(sc[tile_m], sa, isa);
+      half_scale(sc[ta + tile_n], sb, isb);
+    }
+    // two multiplications (1 / (sa sb) alone may leave the normal range)
+    __device__ __forceinline__ floatx16 descale(floatx16 v) const {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      s.x[e] *= sc;
-      if (MASKED) {
-        const int ke = k0 + (u < 4 ? LoaderA::kof(u, e) : LoaderB::kof(u - 4, e));
-        s.x[e] = ke < klim ? s.x[e] : 0.f;
+      for (int r = 0; r < 16; ++r) v[r] = (v[r] * isa) * isb;
+      return v;
+    }
+  };
+  // ---- the split of one group of four values in four micro-steps (sidx = 4 * group + step; groups 0-3: operand A, 4-5: operand B)
+  static constexpr int STEPS = 4;
+  struct Group {
+    float x[4], r[4];
+    unsigned hp[2], lp[2];
+  };
+  template <class LoaderA, class LoaderB, bool MASKED>
+  static __device__ __forceinline__ void micro(int sidx, Group (&gs)[6], const float4 (&ra)[LoaderA::NF], const float4 (&rb)[LoaderB::NF],
+                                               unsigned char* wa, unsigned char* wb, int k0, int klim, const Scale& sc) {
+    const int u = sidx >> 2, st = sidx & 3;
+    Group& s = gs[u];
+    if (st == 0) {
+      if (u < 4) LoaderA::get(ra, u, s.x); else LoaderB::get(rb, u - 4, s.x);
+      const float scl = u < 4 ? sc.sa : sc.sb;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        s.x[e] *= scl;
+        if (MASKED) {
+          const int ke = k0 + (u < 4 ? LoaderA::kof(u, e) : LoaderB::kof(u - 4, e));
+          s.x[e] = ke < klim ? s.x[e] : 0.f;
+        }
       }
-    }
-    s.hp[0] = pack_f16(s.x[0], s.x[1]);
-    s.hp[1] = pack_f16(s.x[2], s.x[3]);
-  } else if (st == 1) {
+      s.hp[0] = pack_f16(s.x[0], s.x[1]);
+      s.hp[1] = pack_f16(s.x[2], s.x[3]);
+    } else if (st == 1) {
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      s.r[2 * h] = resid_lo(s.hp[h], s.x[2 * h]);
-      s.r[2 * h + 1] = resid_hi(s.hp[h], s.x[2 * h + 1]);
-    }
-    asm volatile("" : "+v"(s.r[0]), "+v"(s.r[1]), "+v"(s.r[2]), "+v"(s.r[3]));
-  } else if (st == 2) {
-    s.lp[0] = pack_f16(s.r[0], s.r[1]);
-    s.lp[1] = pack_f16(s.r[2], s.r[3]);
-  } else {
-    if (u < 4) {
-      LoaderA::put(wa, u, 0, s.hp[0], s.hp[1]);
-      LoaderA::put(wa, u, H_PLA, s.lp[0], s.lp[1]);
+      for (int h = 0; h < 2; ++h) {
+        s.r[2 * h] = resid_lo(s.hp[h], s.x[2 * h]);
+        s.r[2 * h + 1] = resid_hi(s.hp[h], s.x[2 * h + 1]);
+      }
+      asm volatile("" : "+v"(s.r[0]), "+v"(s.r[1]), "+v"(s.r[2]), "+v"(s.r[3]));
+    } else if (st == 2) {
+      s.lp[0] = pack_f16(s.r[0], s.r[1]);
+      s.lp[1] = pack_f16(s.r[2], s.r[3]);
     } else {
-      LoaderB::put(wb, u - 4, 0, s.hp[0], s.hp[1]);
-      LoaderB::put(wb, u - 4, H_PLB, s.lp[0], s.lp[1]);
-    }
-  }
-}
-
-// One tile (HALF: a whole tile of <= 128 valid rows: 64 x 64 per wave) or one K piece of a tail tile; see gemm_split.hip's split_body
-// for the pipeline, which this follows step by step with two planes and 24 MFMAs per k-tile.
-template <bool TA, bool TB, bool HALF>
-__device__ __forceinline__ void half_body(const GemmArgs& a, const int b, const int tile_id, const int piece, const int S, const unsigned tj,
-                                          unsigned char* const slds) {
-  constexpr int TM = 4, TN = 2, WGN = 2, NA = HALF ? 2 : 4;
-  const TileBase tb(a, b);
-  const int M = tb.M, K = tb.K, N = a.N;
-  const float* A = tb.A;
-  const float* B = tb.B;
-  float* C = tb.C;
-  const int tile_m = tile_id / a.tiles_n, tile_n = tile_id - tile_m * a.tiles_n;
-  const int m0 = tile_m * S_BM, n0 = tile_n * S_BN;
-  if (m0 >= M) return;
-
-  float sa, sb, isa, isb;
-  {
-    const int ta = a.per_batch / a.tiles_n;                    // row tiles of the largest item: the slot layout of k_gemm_absmax
-    const unsigned* sc = a.scale + (size_t)b * (ta + a.tiles_n);
-    half_scale(sc[tile_m], sa, isa);
-    half_scale(sc[ta + tile_n], sb, isb);
-  }
-
-  typedef typename std::conditional<TA, SplitLoaderMN<S_BM, SROW>, SplitLoaderK<S_BM, SROW>>::type LoaderA;
-  typedef typename std::conditional<TB, SplitLoaderK<S_BN, SROW>, SplitLoaderMN<S_BN, SROW>>::type LoaderB;
-  static_assert(LoaderA::NG == 4 && LoaderB::NG == 2, "six groups of four values per thread and k-tile");
-  constexpr int NFA = LoaderA::NF, NFB = LoaderB::NF;
-  float4 ra[2][NFA], rb[2][NFB];            // two register sets: tile t lives in set t % 2 from its request until its split
-
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wm = wave / WGN, wn = wave - wm * WGN;
-  const int l31 = lane & 31, lhi = lane >> 5;
-
-  floatx16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int nk_main = (K + SBK - 1) / SBK, nk_full = K / SBK;
-  SplitSegs seg;
-  seg.A0 = A; seg.B0 = B; seg.lda0 = a.lda; seg.ldb0 = a.ldb; seg.K0 = K;
-  seg.A1 = seg.A2 = A; seg.B1 = seg.B2 = B; seg.lda1 = seg.lda2 = a.lda; seg.ldb1 = seg.ldb2 = a.ldb; seg.K1 = seg.K2 = K;
-  seg.nk_main = nk_main;
-  seg.nkx0 = 0;
-  int nkx1 = 0;
-  if (a.nx > 0) {
-    const size_t roff = a.ragged == 1 ? (size_t)a.gptr[b] : 0;
-    seg.A1 = a.xA[0] + (size_t)b * a.xsA[0] + roff * a.xlda[0];
-    seg.B1 = a.xB[0] + (size_t)b * a.xsB[0];
-    seg.lda1 = a.xlda[0]; seg.ldb1 = a.xldb[0]; seg.K1 = a.xK[0];
-    seg.nkx0 = (a.xK[0] + SBK - 1) / SBK;
-    if (a.nx > 1) {
-      seg.A2 = a.xA[1] + (size_t)b * a.xsA[1] + roff * a.xlda[1];
-      seg.B2 = a.xB[1] + (size_t)b * a.xsB[1];
-      seg.lda2 = a.xlda[1]; seg.ldb2 = a.xldb[1]; seg.K2 = a.xK[1];
-      nkx1 = (a.xK[1] + SBK - 1) / SBK;
-    }
-  }
-  const int nk = nk_main + seg.nkx0 + nkx1;
-  const int kbeg = S > 1 ? (int)(((long long)nk * piece) / S) : 0;
-  const int kend = S > 1 ? (int)(((long long)nk * (piece + 1)) / S) : nk;
-  const int n = kend - kbeg;
-  const int a_last = TA ? ((M - 1) & ~3) : M - 1, b_last = TB ? N - 1 : ((N - 1) & ~3);
-
-  unsigned offA[NFA], offB[NFB];
-  LoaderA::offsets(offA, a.lda, m0, a_last);
-  LoaderB::offsets(offB, a.ldb, n0, b_last);
-  const __amdgpu_buffer_rsrc_t rsrcA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, 0xffffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrcB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(B), 0, 0xffffffff, 0x00020000);
-
-  const unsigned fa_off = (unsigned)((HALF ? wm * 64 : wm * 128) + l31) * SROW + lhi * 16, fb_off = 2 * H_PLA + (unsigned)(wn * 64 + l31) * SROW + lhi * 16;
-  const unsigned wa_off = LoaderA::wbase(), wb_off = 2 * H_PLA + LoaderB::wbase();
-
-  uint4v fa[2][4][2], fb[2][2][2];          // [set = tile parity][sub-tile][plane h, l]
-  // ---- prologue: tiles 0, 1 split into stages 0, 1; tiles 2, 3 in flight in the two sets; the fragments of tile 0 in set 0.
-  // An empty k range loads nothing and goes straight to the epilogue / its slab with zero accumulators (as gemm_split.hip).
-  if (n > 0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {             // q: 0, 1 request tiles 0, 1; 2: split 0, request 2; 3: split 1, request 3
-      const int set = q & 1;
-      if (q >= 2) {
-        const SplitTile t = split_tile(seg, kbeg + (q - 2 < n ? q - 2 : n - 1));
-        HalfGroup gs[6];
-#pragma unroll
-        for (int sidx = 0; sidx < 24; ++sidx)
-          half_micro<LoaderA, LoaderB, true>(sidx, gs, ra[set], rb[set], slds + (q - 2) * H_STAGE + wa_off, slds + (q - 2) * H_STAGE + wb_off,
-                                             t.k0, t.klim, sa, sb);
+      if (u < 4) {
+        LoaderA::put(wa, u, 0, s.hp[0], s.hp[1]);
+        LoaderA::put(wa, u, PLA, s.lp[0], s.lp[1]);
+      } else {
+        LoaderB::put(wb, u - 4, 0, s.hp[0], s.hp[1]);
+        LoaderB::put(wb, u - 4, PLB, s.lp[0], s.lp[1]);
       }
-      const SplitTile t = split_tile(seg, kbeg + (q < n ? q : n - 1));
-#pragma unroll
-      for (int i = 0; i < NFA; ++i) ra[set][i] = LoaderA::load_any(i, t.A, t.lda, m0, a_last, t.k0, t.klim);
-#pragma unroll
-      for (int i = 0; i < NFB; ++i) rb[set][i] = LoaderB::load_any(i, t.B, t.ldb, n0, b_last, t.k0, t.klim);
     }
-    __syncthreads();
+  }
+
+  // a full second set of fragment registers: the next tile's 12 reads of 16 bytes (8 for a half tile) go into the other set
+  struct Frags {
+    uint4v a[2][4][2], b[2][2][2];            // [set = tile parity][sub-tile][plane h, l]
+  };
+  template <int POS>
+  static __device__ __forceinline__ floatx16 mfma(const Frags& fr, int t, int i, int j, floatx16 acc) {
+    constexpr int PA_[3] = {1, 0, 0}, PB_[3] = {0, 1, 0};          // l h, h l, h h: the small pairs first
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fr.b[POS][j][PB_[t]]), __builtin_bit_cast(f16x8, fr.a[POS][i][PA_[t]]), acc, 0, 0, 0);
+  }
+  template <bool HALF>
+  static __device__ __forceinline__ void read_first(Frags& fr, const unsigned char* st, unsigned fa_off, unsigned fb_off) {
 #pragma unroll
-    for (int i = 0; i < NA; ++i)
+    for (int i = 0; i < (HALF ? 2 : 4); ++i)
 #pragma unroll
-      for (int p = 0; p < 2; ++p) fa[0][i][p] = frag16(slds + fa_off + i * 32 * SROW + p * H_PLA);
+      for (int p = 0; p < 2; ++p) fr.a[0][i][p] = frag16(st + fa_off + i * 32 * SROW + p * PLA);
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int p = 0; p < 2; ++p) fb[0][j][p] = frag16(slds + fb_off + j * 32 * SROW + p * H_PLB);
-    __syncthreads();                          // (step 0 writes tile 2 into stage 0: everybody has read tile 0 out of it)
+      for (int p = 0; p < 2; ++p) fr.b[0][j][p] = frag16(st + fb_off + j * 32 * SROW + p * PLB);
   }
+  template <int POS, bool HALF>
+  static __device__ __forceinline__ void read_next(Frags& fr, int m, const unsigned char* rstage, unsigned fa_off, unsigned fb_off) {
+    if (m < 8) { if ((m >> 1) < (HALF ? 2 : 4)) fr.a[POS ^ 1][m >> 1][m & 1] = frag16(rstage + fa_off + (m >> 1) * 32 * SROW + (m & 1) * PLA); }
+    else if (m < 12) fr.b[POS ^ 1][(m - 8) >> 1][m & 1] = frag16(rstage + fb_off + ((m - 8) >> 1) * 32 * SROW + (m & 1) * PLB);
+  }
+  template <bool HALF>
+  static __device__ __forceinline__ void end_tile(Frags&) {}
+  // (group 3 of A took its values at m = 12, group 1 of B at m = 20)
+  static constexpr int LOAD_A = 13, LOAD_B = 21;
 
-  auto tile_step = [&](auto pos_c, auto full_c, int lt) {
-    constexpr int POS = decltype(pos_c)::value;          // local tile index mod 2: its stage, its register sets
-    constexpr bool FULL = decltype(full_c)::value;
-    const unsigned char* rstage = slds + (POS ^ 1) * H_STAGE;      // tile lt + 1
-    unsigned char* wa = slds + POS * H_STAGE + wa_off;             // tile lt + 2 goes where tile lt was
-    unsigned char* wb = slds + POS * H_STAGE + wb_off;
-    HalfGroup gs[6];
-    int k0s = 0, klims = 0;
-    SplitTile tnext;
-    unsigned soffA = 0, soffB = 0;
-    if constexpr (!FULL) {
-      const SplitTile ts = split_tile(seg, kbeg + (lt + 2 < n ? lt + 2 : n - 1));
-      k0s = ts.k0;
-      klims = ts.klim;
-      tnext = split_tile(seg, kbeg + (lt + 4 < n ? lt + 4 : n - 1));
-    } else {
-      tnext.A = A; tnext.B = B; tnext.lda = a.lda; tnext.ldb = a.ldb; tnext.klim = K; tnext.k0 = 0;
-      const int tl = min(kbeg + lt + 4, nk_full - 1);
-      soffA = LoaderA::soffset(a.lda, tl * SBK);
-      soffB = LoaderB::soffset(a.ldb, tl * SBK);
-    }
-    constexpr int PA_[3] = {1, 0, 0}, PB_[3] = {0, 1, 0};          // l h, h l, h h: the small pairs first
-#pragma clang loop unroll(full)
-    for (int m = 0; m < 24; ++m) {
-      const int t = m / 8, ij = m % 8, i = ij >> 1, j = ij & 1;
-      if (!HALF || i < 2)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fb[POS][j][PB_[t]]), __builtin_bit_cast(f16x8, fa[POS][i][PA_[t]]),
-                                                           acc[i][j], 0, 0, 0);
-      // the next tile's fragments into the other register set: 12 reads of 16 bytes (8 for a half tile)
-      if (m < 8) { if ((m >> 1) < NA) fa[POS ^ 1][m >> 1][m & 1] = frag16(rstage + fa_off + (m >> 1) * 32 * SROW + (m & 1) * H_PLA); }
-      else if (m < 12) fb[POS ^ 1][(m - 8) >> 1][m & 1] = frag16(rstage + fb_off + ((m - 8) >> 1) * 32 * SROW + (m & 1) * H_PLB);
-      half_micro<LoaderA, LoaderB, !FULL>(m, gs, ra[POS], rb[POS], wa, wb, k0s, klims, sa, sb);
-      if (m >= 13 && m < 13 + NFA) {            // (group 3 of A took its values at m = 12)
-        if constexpr (FULL) ra[POS][m - 13] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrcA, offA[m - 13], soffA, 0));
-        else ra[POS][m - 13] = LoaderA::load_any(m - 13, tnext.A, tnext.lda, m0, a_last, tnext.k0, tnext.klim);
-      }
-      if (m >= 21 && m < 21 + NFB) {            // (group 1 of B took its values at m = 20)
-        if constexpr (FULL) rb[POS][m - 21] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrcB, offB[m - 21], soffB, 0));
-        else rb[POS][m - 21] = LoaderB::load_any(m - 21, tnext.B, tnext.ldb, n0, b_last, tnext.k0, tnext.klim);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();
-  };
-  typedef std::true_type FULL_;
-  typedef std::false_type ANY_;
-#define HALF_POS(P_) std::integral_constant<int, P_>()
-  int lt = 0;
-  const int last_special = nk - nk_full;
-  const int full_steps = min(last_special > 0 && kend > nk_full ? nk_full - 4 - kbeg : nk_full - 2 - kbeg, n);
-  for (; lt + 2 <= full_steps; lt += 2) {
-    tile_step(HALF_POS(0), FULL_(), lt);
-    tile_step(HALF_POS(1), FULL_(), lt + 1);
-  }
-  for (; lt < n; ++lt) {
-    if ((lt & 1) == 0) tile_step(HALF_POS(0), ANY_(), lt);
-    else tile_step(HALF_POS(1), ANY_(), lt);
-  }
-#undef HALF_POS
-
-  // descale: two multiplications (1 / (sa sb) alone may leave the normal range)
-#pragma unroll
-  for (int i = 0; i < NA; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = (acc[i][j][r] * isa) * isb;
-
-  float* const lds_f = reinterpret_cast<float*>(slds);
-  if (S > 1) {
-    float* slab = a.ws + ((size_t)tj * S + piece) * (size_t)(S_BM * S_BN) + (size_t)wave * (TM * TN * 16 * 64) + lane * 4;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<float4*>(slab + ((i * TN + j) * 4 + g) * 256) =
-              make_float4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
-    return;
-  }
-  if constexpr (HALF) {
-    floatx16 ah[2][TN];                    // (by value: a reference to a part of acc would put the accumulators in memory)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) ah[i][j] = acc[i][j];
-    gemm_epilogue<2, TN>(a, C, M, N, m0 + wm * 64, n0 + wn * TN * 32, ah, lds_f + wave * 32 * (TN * 32 + 4), lane);
-  } else {
-    gemm_epilogue<TM, TN>(a, C, M, N, m0 + wm * TM * 32, n0 + wn * TN * 32, acc, lds_f + wave * 32 * (TN * 32 + 4), lane);
-  }
-}
+  static bool prepare(GemmPlan<2, 2, 4, 2>& plan, int batch, int m_extent, float* ws, int64_t& ws_floats);
+  static int before(const GemmArgs& a, int form, int batch, int m_extent, hipStream_t stream);
+};
 
 template <bool TA, bool TB>
 __global__ __launch_bounds__(256, 1) void k_gemm_half(const GemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char slds[];
-  int b, tile_id, piece, S;
-  unsigned tj;
-  {
-    TileMap<S_BM> map;
-    map.init(a, threadIdx.x & 63);
-    if (!map.select(a, blockIdx.x, threadIdx.x & 63, b, tile_id, tj, piece, S)) return;
-  }
-  b = __builtin_amdgcn_readfirstlane(b);
-  tile_id = __builtin_amdgcn_readfirstlane(tile_id);
-  piece = __builtin_amdgcn_readfirstlane(piece);
-  S = __builtin_amdgcn_readfirstlane(S);
-  tj = __builtin_amdgcn_readfirstlane(tj);
-  const TileBase tb(a, b);
-  const int rows_left = tb.M - (tile_id / a.tiles_n) * S_BM;
-  if (S == 1 && rows_left <= 128) {
-    half_body<TA, TB, true>(a, b, tile_id, piece, S, tj, slds);
-    return;
-  }
-  half_body<TA, TB, false>(a, b, tile_id, piece, S, tj, slds);
+  split_gemm_tile<F16x2, TA, TB>(a, slds);
 }
 
 // ---- max |x| per OUTPUT TILE's operand panel: for batch item b, scale[b * (ta + tn) + t] = the bits of max |x| over rows
@@ -402,9 +235,6 @@ __global__ __launch_bounds__(256) void k_gemm_absmax(const GemmArgs a, unsigned*
   }
 }
 
-// Workgroups the chip holds at once: one per CU (the register budget: 512 per lane)
-static const int kHalfResident = 256;
-
 static int64_t g_half_launches = 0;
 // tile x k-tile steps below which gemm_half_launch declines (tuning hook, tests: 0 = never decline)
 static int64_t g_half_min_work = 28000;
@@ -417,48 +247,42 @@ extern "C" int64_t cgc_gemm_half_count(void) { return __atomic_load_n(&g_half_la
 int64_t gemm_half_scale_floats() { return H_SCALE_FLOATS; }
 extern "C" int64_t cgc_gemm_half_ws_floats(void) { return H_SCALE_FLOATS; }
 
-// Launch for a product that qualifies (gemm.hip: gemm_dispatch decided: 128 x 128 route, every operand segment fit for unguarded
-// 16-byte loads).  CGC_EINVAL: no workspace for the scales / more panels than slots / a shape outside what the kernel indexes / a
-// product too small for the mode to pay -- the caller then tries the bf16 kernel and, failing that, the exact one.
-int gemm_half_launch(const GemmArgs& a0, int transA, int transB, int batch, int m_extent, int k_extent, float* ws, int64_t ws_floats,
-                     hipStream_t stream) {
-  if (transA && transB) return CGC_EINVAL;
-  if (ws == nullptr || ws_floats < H_SCALE_FLOATS || batch > 65535) return CGC_EINVAL;
-  GemmPlan<2, 2, 4, 2> plan;
-  if (!plan.init(a0, batch, m_extent, k_extent, SBK)) return CGC_EINVAL;
-  const int ta = ceil_div(m_extent, S_BM);
-  const long long slots = (long long)batch * (ta + plan.a.tiles_n);
-  if (slots > H_SCALE_FLOATS) return CGC_EINVAL;
+// false: no workspace for the scales / more panels than slots / a product too small for the mode to pay.  Otherwise the scale slots
+// are taken from the end of the workspace.
+bool F16x2::prepare(GemmPlan<2, 2, 4, 2>& plan, int batch, int m_extent, float* ws, int64_t& ws_floats) {
+  if (ws == nullptr || ws_floats < H_SCALE_FLOATS || batch > 65535) return false;
+  const long long slots = (long long)batch * (ceil_div(m_extent, S_BM) + plan.a.tiles_n);
+  if (slots > H_SCALE_FLOATS) return false;
   // The mode pays once the product kernel's saving (~30 % of the bf16 kernel's time) exceeds its own fixed cost (the slot fill, the
   // maximum pass: two launches and one more trip over the operands).  Measured on the step's six products at 32 / 16 / 8 / 4 graphs
   // (profiles/r06_configurations.txt): ahead of the bf16 mode by 18 / 17 / 10 % down to 8 graphs (37-47 k tile x k-tile steps per
   // product), behind it by 6 % at 4 (19-23 k) and at C1 = 180 (5 k).  Below 28 k steps the caller runs the bf16 kernel instead.
-  if (plan.tiles * plan.kt < __atomic_load_n(&g_half_min_work, __ATOMIC_RELAXED)) return CGC_EINVAL;
-  unsigned* scale = reinterpret_cast<unsigned*>(ws + (ws_floats - H_SCALE_FLOATS));
-  plan.a.scale = scale;
-  plan.tail_split(ws, ws_floats - H_SCALE_FLOATS, 8, kHalfResident);    // a piece keeps >= 8 k-tiles: the pipeline is five deep
-  plan.timing_begin(m_extent, k_extent, stream);
-  const GemmArgs& a = plan.a;
-  {
-    const hipError_t e = hipMemsetAsync(scale, 0, sizeof(unsigned) * (size_t)slots, stream);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (plan.tiles * plan.kt < __atomic_load_n(&g_half_min_work, __ATOMIC_RELAXED)) return false;
+  ws_floats -= H_SCALE_FLOATS;
+  plan.a.scale = reinterpret_cast<unsigned*>(ws + ws_floats);
+  return true;
+}
+// the slot fill and the maximum pass
+int F16x2::before(const GemmArgs& a, int form, int batch, int m_extent, hipStream_t stream) {
+  unsigned* scale = const_cast<unsigned*>(a.scale);
+  int ta = ceil_div(m_extent, S_BM);
+  const hipError_t e = hipMemsetAsync(scale, 0, sizeof(unsigned) * (size_t)batch * (ta + a.tiles_n), stream);
+  if (e != hipSuccess) return (int)e;
   // ~4 workgroups per CU for each operand, a panel's rows shared by up to 64 of them
   auto subs = [&](int panels) { const long long n = (long long)batch * panels; const int v = n >= 1024 ? 1 : ceil_div(1024, (int)n); return v > 64 ? 64 : v; };
-  const int sub_a = subs(ta), sub_b = subs(a.tiles_n);
-  const dim3 grid = plan.grid(), block(256), mgrid((unsigned)(ta * sub_a + a.tiles_n * sub_b), (unsigned)batch);
-#define HALF_LAUNCH(TA_, TB_)                                                                               \
-  do {                                                                                                      \
-    static bool attr__[CGC_MAX_DEVICES] = {};                                                               \
-    cgc_allow_lds(reinterpret_cast<const void*>(&k_gemm_half<TA_, TB_>), H_LDS, attr__);                    \
-    hipLaunchKernelGGL((k_gemm_absmax<TA_, TB_>), mgrid, block, 0, stream, a, scale, ta, sub_a, sub_b);                       \
-    hipLaunchKernelGGL((k_gemm_half<TA_, TB_>), grid, block, H_LDS, stream, a);                             \
-  } while (0)
-  if (!transA && !transB) HALF_LAUNCH(false, false);
-  else if (!transA) HALF_LAUNCH(false, true);
-  else HALF_LAUNCH(true, false);
-#undef HALF_LAUNCH
-  CGC_RETURN_IF_LAUNCH_FAILED();
-  __atomic_fetch_add(&g_half_launches, 1, __ATOMIC_RELAXED);
-  return plan.finish(stream);
+  int sub_a = subs(ta), sub_b = subs(a.tiles_n);
+  static const void* const kern[3] = {reinterpret_cast<const void*>(&k_gemm_absmax<false, false>), reinterpret_cast<const void*>(&k_gemm_absmax<false, true>),
+                                      reinterpret_cast<const void*>(&k_gemm_absmax<true, false>)};
+  void* args[] = {const_cast<GemmArgs*>(&a), &scale, &ta, &sub_a, &sub_b};
+  (void)hipLaunchKernel(kern[form], dim3((unsigned)(ta * sub_a + a.tiles_n * sub_b), (unsigned)batch), dim3(256), args, 0, stream);
+  return 0;
+}
+
+// CGC_EINVAL: the mode declines (F16x2::prepare) or the shape is outside what the kernel indexes -- the caller then tries the bf16
+// kernel and, failing that, the exact one.
+int gemm_half_launch(const GemmArgs& a0, int transA, int transB, int batch, int m_extent, int k_extent, float* ws, int64_t ws_floats,
+                     hipStream_t stream) {
+  static const void* const kern[3] = {reinterpret_cast<const void*>(&k_gemm_half<false, false>), reinterpret_cast<const void*>(&k_gemm_half<false, true>),
+                                      reinterpret_cast<const void*>(&k_gemm_half<true, false>)};
+  return split_gemm_launch<F16x2>(kern, g_half_launches, a0, transA, transB, batch, m_extent, k_extent, ws, ws_floats, stream);
 }

@@ -418,7 +418,7 @@ class HipKernels(KernelSpec):
     tail_split = True   # hand cgc_gemm_f32 its slab workspace (False: every output tile is computed whole; tests / A-B timing)
     # cgc_gemm_f32's `mode` for the products issued through this table (the per-operator path): GEMM_EXACT (default),
     # GEMM_SPLIT_BF16 -- the big products as six bf16 MFMA pairs per fp32 product (csrc/gemm_split.hip) -- or GEMM_SPLIT_F16 -- as
-    # three fp16 pairs of operands scaled per batch item (csrc/gemm_half.hip).  The encoder sets it from its own ``gemm_mode`` at
+    # three fp16 pairs of operands scaled per output tile's operand panels (csrc/gemm_half.hip).  The encoder sets it from its own ``gemm_mode`` at
     # the top of forward(); the sequencer gets the same choice through cgc_level_desc.flags bits 1 / 2.
     gemm_mode = 0
     # graph structure graph by graph in two launches when the Batch says how its edge list is grouped (cgc_graph_build_local;
