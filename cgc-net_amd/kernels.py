@@ -91,6 +91,25 @@ class KernelSpec(object):
         Pixels with a label outside [0, max_label] raise ValueError (the reference raises for negative labels)."""
         raise NotImplementedError
 
+    def label_components(self, image, connectivity, min_size, want_sizes=False):
+        """Connected components of one image (F5, in front of nucleus_features; csrc/label.hip).  image: contiguous [H, W] of a 1-, 2-, 4-
+        or 8-byte integer type or bool, H * W < 2^31.  Returns (labels int32 [H, W], n, sizes int32 [n] or None); reads n on the host,
+        which is the only host read.
+
+        1.  0 is background; every other value, negative ones included, is foreground.
+        2.  Two foreground pixels belong to one component iff a path of neighbouring pixels that ALL CARRY THE SAME VALUE joins them:
+            connectivity 1 = the 4 edge neighbours, connectivity 2 = the 8 neighbours.  A bool or 0/1 image gets ordinary
+            connected-component labelling; an integer image has every value split into its connected pieces, and adjacent pixels of
+            different values are never merged.
+        3.  labels: 0 for background, components numbered 1..n by the raster (row-major) order of each component's first pixel -- for a
+            binary image scipy.ndimage.label's output with the matching structuring element, bit for bit.
+        4.  min_size > 0: components of fewer than min_size pixels become background and take no number; the survivors are still
+            numbered 1..n by first pixel (skimage.morphology.remove_small_objects on the boolean image, then labelling).
+        5.  want_sizes: sizes[k - 1] = pixels of component k.
+        6.  H * W = 0 gives empty labels and n = 0; an all-background image zeros and n = 0.
+        The result is a pure function of the input: no launch's outcome depends on the order in which workgroups run."""
+        raise NotImplementedError
+
     def bgr_to_gray(self, bgr):
         """cv2.cvtColor(img, COLOR_BGR2GRAY) on uint8 [H, W, 3]: (1868 B + 9617 G + 4899 R + 8192) >> 14 -> uint8 [H, W]."""
         raise NotImplementedError
@@ -585,6 +604,24 @@ class HipKernels(KernelSpec):
                                                ctypes.c_int64(big_px), _ptr(big_ws), _ptr(feats), _ptr(cen), _ptr(info), self._stream()),
                   'cgc_nuclei_features')
         return feats, cen, kept[:n], info
+
+    def label_components(self, image, connectivity, min_size, want_sizes=False):
+        self._dev(image)
+        assert image.dim() == 2 and image.is_contiguous() and image.element_size() in (1, 2, 4, 8) and not image.is_floating_point()
+        H, W = image.shape
+        dev = image.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        counts = int(min_size > 1 or want_sizes)
+        labels, nbuf = torch.empty(H, W, **i32), torch.empty(1, **i32)
+        ws = torch.empty(int(self.lib.cgc_label_ws_bytes(H, W, counts)), dtype=torch.uint8, device=dev)
+        self._chk(self.lib.cgc_label_components(_ptr(image), image.element_size(), H, W, int(connectivity), int(min_size), counts, _ptr(ws),
+                                                _ptr(labels), _ptr(nbuf), self._stream()), 'cgc_label_components')
+        n = int(nbuf.item())                            # the host sync of this stage: the component count
+        sizes = None
+        if want_sizes:
+            sizes = torch.empty(n, **i32)
+            self._chk(self.lib.cgc_label_sizes(_ptr(ws), H, W, n, _ptr(sizes), self._stream()), 'cgc_label_sizes')
+        return labels, n, sizes
 
     def bgr_to_gray(self, bgr):
         self._dev(bgr)

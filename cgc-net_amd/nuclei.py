@@ -1,5 +1,10 @@
-"""Nucleus features and centroids from an instance mask on the GPU: the step that makes the node tables of every graph
+"""Instance masks, then nucleus features and centroids from them, on the GPU: the steps that make the node tables of every graph
 (dataflow/construct_feature_graph.py:50-123 + common/nuc_feature.py, then dataflow/prepare_cv_dataset.py:57-72).
+
+``label_instances(image)`` is the step in front: it turns a thresholded foreground map into an instance mask (connected-component
+labelling, scipy.ndimage.label's numbering) or splits every value of an integer mask into its connected pieces (csrc/label.hip; the
+contract item by item: kernels.KernelSpec.label_components).  Its ``labels`` and ``n`` go straight into
+``nucleus_features(labels, gray, max_label=n)``.  The reference starts from finished masks and has no such step.
 
 ``nucleus_features(labels, gray)`` returns the reference's ``feature`` / ``coordinate`` arrays of one image (csrc/nuclei.hip; the
 arithmetic item by item: kernels.KernelSpec.nucleus_features), ``graph_item`` turns them into the ``Data`` that
@@ -23,14 +28,46 @@ FEATURE_NAMES = ('mean_im_out', 'diff', 'var_im', 'skew_im', 'mean_ent', 'glcm_d
 _INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
 
 
-def nucleus_features(labels, gray, min_size=10, return_info=False):
+def label_instances(image, connectivity=1, min_size=0, return_sizes=False):
+    """image: 2-D bool / uint8 / int8 / int16 / int32 / int64 tensor on the GPU, any strides; 0 = background, every other value
+    (negative ones too) foreground.  Returns (labels int32 [H, W], n) and, with ``return_sizes``, int32 [n] pixel counts (sizes[k - 1]
+    belongs to label k).  Two pixels share a component iff a path of neighbours (``connectivity`` 1: 4 neighbours, 2: 8) that all
+    carry the same value joins them, so a bool or 0/1 image is labelled as scipy.ndimage.label does -- components numbered 1..n by the
+    raster order of their first pixels, bit for bit -- and an integer mask has each value split into its connected pieces.  With
+    ``min_size`` > 0 components of fewer pixels become background and take no number (skimage's remove_small_objects, then labelling).
+
+    Host syncs: one, the read of n."""
+    if not torch.is_tensor(image) or not image.is_cuda:
+        raise TypeError('label_instances takes a torch tensor on the GPU')
+    if image.dtype != torch.bool and image.dtype not in _INT_DTYPES:
+        raise TypeError('image must be a bool or integer image, got %s' % image.dtype)
+    if image.dim() != 2:
+        raise ValueError('image must be 2-D (got %s)' % (tuple(image.shape),))
+    if connectivity not in (1, 2):
+        raise ValueError('connectivity must be 1 (4 neighbours) or 2 (8 neighbours), got %r' % (connectivity,))
+    if min_size < 0:
+        raise ValueError('min_size must not be negative (got %r)' % (min_size,))
+    H, W = image.shape
+    if H * W >= 2 ** 31:
+        raise ValueError('images of 2^31 pixels or more are not supported (%d x %d)' % (H, W))
+    if H * W == 0:
+        labels, n = torch.zeros(H, W, dtype=torch.int32, device=image.device), 0
+        sizes = torch.zeros(0, dtype=torch.int32, device=image.device)
+    else:
+        with torch.cuda.device(image.device):
+            labels, n, sizes = kernels.get().label_components(image.contiguous(), int(connectivity), int(min_size), bool(return_sizes))
+    return (labels, n, sizes) if return_sizes else (labels, n)
+
+
+def nucleus_features(labels, gray, min_size=10, return_info=False, max_label=None):
     """labels: integer [H, W] instance mask on the GPU (0 = background; other integer dtypes are converted to int32), gray: uint8
     [H, W] on the same GPU.  Returns (features f32 [n, 16], centroids f32 [n, 2] as (row, col), kept_labels int32 [n]) -- row k
     describes the k-th surviving label in ascending order -- plus, with ``return_info``, int32 [n, 4]: the traced contour's start
     (row, col) in the crop, its vertex count and the path taken (0 LDS, 1 global workspace).
 
     Host syncs: one read of the label range (negative labels raise ValueError; the tables are indexed by label value, so very sparse
-    label ids cost memory in proportion to the largest) and one read of the row count."""
+    label ids cost memory in proportion to the largest) and one read of the row count.  ``max_label`` (an int >= the largest label,
+    e.g. the n of ``label_instances``) replaces the read of the label range; pixels outside [0, max_label] then raise ValueError."""
     if not (torch.is_tensor(labels) and torch.is_tensor(gray)):
         raise TypeError('nucleus_features takes torch tensors on the GPU')
     if labels.dim() != 2 or tuple(gray.shape) != tuple(labels.shape):
@@ -44,7 +81,11 @@ def nucleus_features(labels, gray, min_size=10, return_info=False):
     if H * W >= 2 ** 31:
         raise ValueError('images of 2^31 pixels or more are not supported (%d x %d)' % (H, W))
     dev = labels.device
-    if H * W == 0:
+    if max_label is not None:
+        lo, hi = 0, int(max_label)
+        if hi < 0:
+            raise ValueError('max_label must not be negative (got %d)' % hi)
+    elif H * W == 0:
         lo = hi = 0
     else:
         lo, hi = torch.stack([labels.min(), labels.max()]).to(torch.int64).tolist()
@@ -52,7 +93,7 @@ def nucleus_features(labels, gray, min_size=10, return_info=False):
         raise ValueError('negative labels in the instance mask (remove_small_objects refuses them)')
     if hi >= 2 ** 31 - 1:
         raise ValueError('label values must fit int32 (largest: %d)' % hi)
-    if hi == 0:
+    if hi == 0 and (max_label is None or H * W == 0):
         out = (torch.zeros(0, NUM_FEATURES, dtype=torch.float32, device=dev), torch.zeros(0, 2, dtype=torch.float32, device=dev),
                torch.zeros(0, dtype=torch.int32, device=dev))
         return out + (torch.zeros(0, 4, dtype=torch.int32, device=dev),) if return_info else out

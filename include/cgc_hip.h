@@ -55,8 +55,9 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *      (of cgc_bn_act_apply2), cgc_sage_narrow_bwd (of cgc_sage_narrow_bwd_ld), cgc_level_fwd (of cgc_level_fwd_reg), cgc_level_bwd
  *      (of cgc_level_bwd_reg)
  *   9: nucleus features from instance masks: cgc_nuclei_lds_max_pixels, cgc_nuclei_ws_bytes, cgc_nuclei_label_pass,
- *      cgc_nuclei_big_ws_bytes, cgc_nuclei_features, cgc_bgr_to_gray */
-#define CGC_ABI_VERSION 9
+ *      cgc_nuclei_big_ws_bytes, cgc_nuclei_features, cgc_bgr_to_gray
+ *  10: connected-component labelling in front of them: cgc_label_ws_bytes, cgc_label_components, cgc_label_sizes */
+#define CGC_ABI_VERSION 10
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -132,6 +133,23 @@ int cgc_nuclei_features(const int* labels, const uint8_t* gray, int H, int W, in
                         const int* kept_labels, int n, int nbig, int64_t max_big_px, void* big_ws, float* features, float* centroids,
                         int* info, cgc_stream_t stream);
 int cgc_bgr_to_gray(const uint8_t* bgr, int64_t npix, uint8_t* gray, cgc_stream_t stream);
+
+/* ---- F5 (in front of F4): connected-component labelling of a binary mask, relabelling of an integer mask (csrc/label.hip).  Replaces
+ * scipy.ndimage.label on the host between a segmentation network's thresholded output and cgc_nuclei_label_pass; the contract item by
+ * item: cgc-net_amd/kernels.py KernelSpec.label_components.  image [H, W] of pixel_bytes = 1, 2, 4 or 8 bytes per pixel (an integer
+ * type of either signedness: only "is zero" and "equals" are used), 0 = background; H * W < 2^31.  connectivity 1 (4 neighbours) or
+ * 2 (8 neighbours): two pixels share a component iff a path of neighbours that all carry the SAME value joins them.
+ *   cgc_label_components: ws = cgc_label_ws_bytes(H, W, with_counts) bytes.  Out: labels int32 [H, W], 0 = background, components
+ *     numbered 1..n by the raster order of their first pixels (for a 0/1 image: scipy.ndimage.label's output); *n_out (device) = n.
+ *     with_counts != 0 keeps per-component pixel counts in ws: required for min_size > 1 (components of fewer pixels become
+ *     background and take no number) and by cgc_label_sizes.  H * W = 0: only *n_out = 0 is written.
+ *   cgc_label_sizes: after the host has read n, sizes int32 [n], sizes[k - 1] = pixels of component k; the same ws, untouched since a
+ *     cgc_label_components call with with_counts != 0.
+ * No workgroup waits for another one in any of the launches; the result is a pure function of the image. */
+int64_t cgc_label_ws_bytes(int H, int W, int with_counts);
+int cgc_label_components(const void* image, int pixel_bytes, int H, int W, int connectivity, int min_size, int with_counts, void* ws,
+                         int* labels, int* n_out, cgc_stream_t stream);
+int cgc_label_sizes(const void* ws, int H, int W, int n, int* sizes, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
