@@ -17,6 +17,8 @@ import torch
 ACT_CODES = {'identity': 0, 'relu': 1, 'elu': 2, 'leakyrelu': 3}
 L2_EPS = 1e-12       # F.normalize eps
 RENORM_EPS = 1e-15   # model/network.py:8
+EDT_INF = 2 ** 31 - 1      # CGC_EDT_INF: dist2 of a pixel without a site (within the bound)
+EDT_MAX_SIDE = 32767       # 2 * 32766^2 < 2^31 - 1: squared distances fit int32
 
 
 class KernelSpec(object):
@@ -108,6 +110,23 @@ class KernelSpec(object):
         5.  want_sizes: sizes[k - 1] = pixels of component k.
         6.  H * W = 0 gives empty labels and n = 0; an all-background image zeros and n = 0.
         The result is a pure function of the input: no launch's outcome depends on the order in which workgroups run."""
+        raise NotImplementedError
+
+    def distance_transform(self, image, sites_nonzero, d2max, want_nearest=False):
+        """Exact Euclidean distance transform of one image with the nearest site of every pixel (F6, beside label_components;
+        csrc/edt.hip).  image: contiguous [H, W] of a 1-, 2-, 4- or 8-byte integer type or bool, H <= 32767 and W <= 32767 (ValueError
+        otherwise: a squared distance must fit int32).  Returns (dist2 int32 [H, W], nearest int32 [H, W] or None); no host read.
+
+        1.  A site is a pixel with value != 0 (sites_nonzero) or value == 0 (not sites_nonzero).
+        2.  dist2[p] = the smallest dy^2 + dx^2 from p to a site; 0 on sites.  Integer arithmetic only: every value is exact.
+        3.  nearest[p] = the raster index y' * W + x' of the site that attains it; ties go to the SMALLEST raster index.  Only computed
+            with want_nearest.
+        4.  An image without a site: dist2 = EDT_INF (2^31 - 1) and nearest = -1 everywhere.
+        5.  d2max >= 0: pixels whose true dist2 exceeds d2max report EDT_INF and -1, all others are exact; d2max < 0: no bound.
+        6.  Distances are measured to sites inside the image only (scipy's convention): the image border is not a site.
+        7.  H * W = 0 gives empty outputs.
+        The result is a pure function of the input.  Cost per pixel grows with the distance to its nearest site, capped by
+        sqrt(d2max): O(W) per pixel where a row's columns hold no site at all."""
         raise NotImplementedError
 
     def bgr_to_gray(self, bgr):
@@ -622,6 +641,22 @@ class HipKernels(KernelSpec):
             sizes = torch.empty(n, **i32)
             self._chk(self.lib.cgc_label_sizes(_ptr(ws), H, W, n, _ptr(sizes), self._stream()), 'cgc_label_sizes')
         return labels, n, sizes
+
+    def distance_transform(self, image, sites_nonzero, d2max, want_nearest=False):
+        self._dev(image)
+        assert image.dim() == 2 and image.is_contiguous() and image.element_size() in (1, 2, 4, 8) and not image.is_floating_point()
+        H, W = image.shape
+        if H > EDT_MAX_SIDE or W > EDT_MAX_SIDE:
+            raise ValueError('distance_transform takes images of at most %d x %d pixels (got %d x %d)' % (EDT_MAX_SIDE, EDT_MAX_SIDE, H, W))
+        i32 = dict(dtype=torch.int32, device=image.device)
+        dist2 = torch.empty(H, W, **i32)
+        nearest = torch.empty(H, W, **i32) if want_nearest else None
+        if H * W == 0:
+            return dist2, nearest
+        ws = torch.empty(int(self.lib.cgc_edt_ws_bytes(H, W)), dtype=torch.uint8, device=image.device)
+        self._chk(self.lib.cgc_edt(_ptr(image), image.element_size(), H, W, int(bool(sites_nonzero)), int(d2max), _ptr(ws), _ptr(dist2),
+                                   _ptr(nearest), self._stream()), 'cgc_edt')
+        return dist2, nearest
 
     def bgr_to_gray(self, bgr):
         self._dev(bgr)

@@ -6,6 +6,10 @@ labelling, scipy.ndimage.label's numbering) or splits every value of an integer 
 contract item by item: kernels.KernelSpec.label_components).  Its ``labels`` and ``n`` go straight into
 ``nucleus_features(labels, gray, max_label=n)``.  The reference starts from finished masks and has no such step.
 
+``distance_transform``, ``expand_labels`` and ``split_touching`` sit between the two: an exact Euclidean distance transform with the
+nearest site of every pixel (csrc/edt.hip; kernels.KernelSpec.distance_transform), skimage's expand_labels on top of it, and the
+erode-label-grow split that keeps touching nuclei from merging into one node.
+
 ``nucleus_features(labels, gray)`` returns the reference's ``feature`` / ``coordinate`` arrays of one image (csrc/nuclei.hip; the
 arithmetic item by item: kernels.KernelSpec.nucleus_features), ``graph_item`` turns them into the ``Data`` that
 ``_read_one_raw_graph`` builds, and ``save_reference_files`` writes them where the reference's dataset preparation reads them.
@@ -15,6 +19,7 @@ Differences from the reference, all stated: an image without a surviving nucleus
 (``ValueError``; the reference resizes, which is the identity then).  OpenCV, scikit-image and xtract-features are restated from their
 documented behaviour, not linked: see DESIGN.md, "Nucleus features".
 """
+import math
 import os
 
 import numpy as np
@@ -26,6 +31,7 @@ NUM_FEATURES = 16
 FEATURE_NAMES = ('mean_im_out', 'diff', 'var_im', 'skew_im', 'mean_ent', 'glcm_dissimilarity', 'glcm_homogeneity', 'glcm_energy',
                  'glcm_ASM', 'eccentricity', 'area', 'majoraxis_length', 'minoraxis_length', 'perimeter', 'solidity', 'orientation')
 _INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+EDT_INF = kernels.EDT_INF          # dist2 of a pixel that has no site (within max_distance)
 
 
 def label_instances(image, connectivity=1, min_size=0, return_sizes=False):
@@ -57,6 +63,117 @@ def label_instances(image, connectivity=1, min_size=0, return_sizes=False):
         with torch.cuda.device(image.device):
             labels, n, sizes = kernels.get().label_components(image.contiguous(), int(connectivity), int(min_size), bool(return_sizes))
     return (labels, n, sizes) if return_sizes else (labels, n)
+
+
+def _check_image(fn, name, image):
+    if not torch.is_tensor(image) or not image.is_cuda:
+        raise TypeError('%s takes torch tensors on the GPU' % fn)
+    if image.dtype != torch.bool and image.dtype not in _INT_DTYPES:
+        raise TypeError('%s must be a bool or integer image, got %s' % (name, image.dtype))
+    if image.dim() != 2:
+        raise ValueError('%s must be 2-D (got %s)' % (name, tuple(image.shape)))
+    H, W = image.shape
+    if H > kernels.EDT_MAX_SIDE or W > kernels.EDT_MAX_SIDE:
+        raise ValueError('%s: sides over %d pixels are not supported (%d x %d): a squared distance must fit int32'
+                         % (fn, kernels.EDT_MAX_SIDE, H, W))
+
+
+def _d2max(distance, name):
+    """The largest integer k with sqrt(k) <= distance (float64 sqrt, which is correctly rounded), capped at EDT_INF - 1, which no
+    squared distance of a supported image exceeds.  int(d * d) alone can be off by one in either direction: its neighbours are checked."""
+    d = float(distance)
+    if not d >= 0:
+        raise ValueError('%s must be a number >= 0 (got %r)' % (name, distance))
+    if d * d >= EDT_INF:
+        return EDT_INF - 1
+    k = int(d * d)
+    while math.sqrt(k + 1) <= d:
+        k += 1
+    while k > 0 and math.sqrt(k) > d:
+        k -= 1
+    return k
+
+
+def distance_transform(image, sites='zero', max_distance=None, return_nearest=False):
+    """image: 2-D bool / uint8 / int8 / int16 / int32 / int64 tensor on the GPU, any strides, each side <= 32767.  Returns dist2
+    (int32 [H, W]): the exact squared Euclidean distance dy^2 + dx^2 from every pixel to the nearest site, 0 on sites -- and, with
+    ``return_nearest``, nearest (int32 [H, W]): the raster index y' * W + x' of that site, of several equally near ones the one with
+    the smallest raster index.  ``sites='zero'`` (default): the sites are the zero pixels, i.e. scipy.ndimage.distance_transform_edt
+    (image) squared; ``sites='nonzero'``: the non-zero pixels.  Distances are measured to sites inside the image only (scipy's
+    convention): a nucleus cut by the border is not near background there.  An image without a site gives dist2 = EDT_INF (2^31 - 1)
+    and nearest = -1.  ``max_distance`` (float >= 0): pixels farther than that from every site report EDT_INF and -1, all others are
+    exact, and the search stops there -- without it the cost per pixel grows with the distance to its nearest site (O(W) per pixel on
+    rows whose columns hold no site).  ``dist2.double().sqrt()`` is the distance.
+
+    Host syncs: none."""
+    _check_image('distance_transform', 'image', image)
+    if sites not in ('zero', 'nonzero'):
+        raise ValueError("sites must be 'zero' or 'nonzero', got %r" % (sites,))
+    d2max = -1 if max_distance is None else _d2max(max_distance, 'max_distance')
+    with torch.cuda.device(image.device):
+        dist2, nearest = kernels.get().distance_transform(image.contiguous(), sites == 'nonzero', d2max, bool(return_nearest))
+    return (dist2, nearest) if return_nearest else dist2
+
+
+def expand_labels(labels, distance, within=None):
+    """skimage.segmentation.expand_labels on the GPU, with a stated tie rule.  labels: 2-D bool / integer tensor on the GPU (0 =
+    background).  Every background pixel whose nearest labelled pixel lies within ``distance`` (Euclidean, sqrt(dist2) <= distance)
+    takes that pixel's value; of several equally near labelled pixels the one with the smallest raster index decides.  ``within``
+    (same shape, bool / integer): only background pixels that are also non-zero in ``within`` may be filled.  Nearness stays
+    Euclidean, not geodesic: ``within`` selects which pixels are filled, not the paths along which distance is measured, so a label
+    can reach across a gap of ``within``.  Labelled pixels never change; the output has the input's dtype.  The distance transform
+    underneath is bounded by ``distance``.
+
+    Host syncs: none."""
+    _check_image('expand_labels', 'labels', labels)
+    d2max = _d2max(distance, 'distance')
+    if within is not None:
+        _check_image('expand_labels', 'within', within)
+        if tuple(within.shape) != tuple(labels.shape) or within.device != labels.device:
+            raise ValueError('within must have the shape and device of labels (got %s and %s)' % (tuple(within.shape), tuple(labels.shape)))
+    if labels.numel() == 0:
+        return labels.clone()
+    with torch.cuda.device(labels.device):
+        _, nearest = kernels.get().distance_transform(labels.contiguous(), True, d2max, True)
+    # a labelled pixel is its own nearest site, so the gather returns it unchanged; nearest = -1: nothing within reach
+    fill = nearest >= 0
+    if within is not None:
+        fill &= (labels != 0) | (within != 0)
+    src = labels.reshape(-1)[nearest.clamp_(min=0).reshape(-1).long()].reshape(labels.shape)
+    return torch.where(fill, src, labels)
+
+
+def split_touching(mask, core_radius, connectivity=1, min_size=0):
+    """The erode-label-grow split of a foreground mask (2-D bool / integer tensor on the GPU, 0 = background) into instances, for
+    nuclei that touch: returns (labels int32 [H, W], n) as ``label_instances`` does, ready for ``nucleus_features(labels, gray,
+    max_label=n)``.
+      1. dist2 = distance_transform(mask): squared distance of every foreground pixel to the background inside the image;
+      2. the cores -- pixels farther than ``core_radius`` from the background -- are labelled (``connectivity``);
+      3. the cores grow back by ``core_radius`` + 1 inside the mask (expand_labels(..., within=mask)): the opening of the mask,
+         partitioned by nearest core, plus the one-pixel rim that the opening of a digital shape leaves behind (grown by
+         ``core_radius`` alone, a disc of radius 10 sheds 24 single-pixel slivers at core_radius 8, each of which would count as a
+         nucleus; the mask clips what the extra pixel oversteps);
+      4. what is left of the mask (thin bridges, slivers, objects without a core) is labelled on its own: no foreground pixel is lost;
+      5. label_instances(combined, connectivity, min_size) splits every value into its connected pieces, applies ``min_size`` and
+         numbers the result 1..n by first pixel.
+    ``core_radius`` = 0 is label_instances(mask != 0, connectivity, min_size).
+
+    Host syncs: three, the reads of n of the three labelling calls."""
+    _check_image('split_touching', 'mask', mask)
+    radius2 = _d2max(core_radius, 'core_radius')
+    if connectivity not in (1, 2):
+        raise ValueError('connectivity must be 1 (4 neighbours) or 2 (8 neighbours), got %r' % (connectivity,))
+    if min_size < 0:
+        raise ValueError('min_size must not be negative (got %r)' % (min_size,))
+    if mask.numel() == 0:
+        return torch.zeros(tuple(mask.shape), dtype=torch.int32, device=mask.device), 0
+    fg = mask != 0
+    dist2 = distance_transform(fg)
+    cores, k = label_instances(dist2 > radius2, connectivity)
+    grown = expand_labels(cores, float(core_radius) + 1.0, within=fg)
+    rest, _ = label_instances(fg & (grown == 0), connectivity)
+    combined = torch.where(rest > 0, rest + k, grown)
+    return label_instances(combined, connectivity, min_size)
 
 
 def nucleus_features(labels, gray, min_size=10, return_info=False, max_label=None):

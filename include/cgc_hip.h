@@ -56,8 +56,9 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *      (of cgc_level_bwd_reg)
  *   9: nucleus features from instance masks: cgc_nuclei_lds_max_pixels, cgc_nuclei_ws_bytes, cgc_nuclei_label_pass,
  *      cgc_nuclei_big_ws_bytes, cgc_nuclei_features, cgc_bgr_to_gray
- *  10: connected-component labelling in front of them: cgc_label_ws_bytes, cgc_label_components, cgc_label_sizes */
-#define CGC_ABI_VERSION 10
+ *  10: connected-component labelling in front of them: cgc_label_ws_bytes, cgc_label_components, cgc_label_sizes
+ *  11: exact distance transform with nearest sites: cgc_edt_ws_bytes, cgc_edt, CGC_EDT_INF */
+#define CGC_ABI_VERSION 11
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -150,6 +151,22 @@ int64_t cgc_label_ws_bytes(int H, int W, int with_counts);
 int cgc_label_components(const void* image, int pixel_bytes, int H, int W, int connectivity, int min_size, int with_counts, void* ws,
                          int* labels, int* n_out, cgc_stream_t stream);
 int cgc_label_sizes(const void* ws, int H, int W, int n, int* sizes, cgc_stream_t stream);
+
+/* ---- F6 (beside F5): exact Euclidean distance transform of a 2-D image with the nearest site of every pixel (csrc/edt.hip).  Replaces
+ * scipy.ndimage.distance_transform_edt / skimage.segmentation.expand_labels on the host; the contract item by item:
+ * cgc-net_amd/kernels.py KernelSpec.distance_transform.  image [H, W] of elem_bytes = 1, 2, 4 or 8 bytes per pixel (only "is zero" is
+ * used); a site is a pixel with value != 0 (sites_nonzero != 0) or value == 0 (sites_nonzero = 0).  H <= 32767 and W <= 32767, so that
+ * every squared distance fits int32; otherwise CGC_EINVAL and nothing is launched.  ws = cgc_edt_ws_bytes(H, W) bytes.
+ *   dist2 int32 [H, W]: the smallest dy^2 + dx^2 from the pixel to a site INSIDE THE IMAGE (0 on sites).
+ *   nearest int32 [H, W] or NULL (skipped): the raster index y' * W + x' of the site that attains it; of several the smallest index.
+ *   No site in the image: dist2 = CGC_EDT_INF and nearest = -1 everywhere.  d2max >= 0: pixels whose true dist2 exceeds d2max report
+ *   CGC_EDT_INF and -1, all others are exact; d2max < 0: no bound.  H * W = 0: nothing is written.
+ * Three launches, no workgroup waits for another one, nothing allocates or synchronises; the result is a pure function of the image.
+ * Cost per pixel grows with the distance to its nearest site (bounded by sqrt(d2max)): O(W) where a row's columns hold no site. */
+#define CGC_EDT_INF 2147483647
+int64_t cgc_edt_ws_bytes(int H, int W);
+int cgc_edt(const void* image, int elem_bytes, int H, int W, int sites_nonzero, int d2max, void* ws, int* dist2, int* nearest_or_null,
+            cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
