@@ -134,18 +134,25 @@ def hull_area(pts):
     return abs(_shoelace2(h)) * 0.5 if len(h) >= 3 else 0.0
 
 
-def fit_ellipse(pts):
+def fit_ellipse(pts, ratios=None):
     """Item 10 (OpenCV 4.1 fitEllipseNoDirect restated): (width, height, angle) of the box, float32.  Points centred on their mean and
-    scaled into [-1, 1]; lstsq with singular values below RCOND of the largest dropped."""
+    scaled into [-1, 1]; lstsq with singular values below RCOND of the largest dropped.  ``ratios`` (a list) receives the conditioning
+    of the three solves: per solve the singular values over the largest, s / s[0] -- a test uses it to keep its inputs clear of RCOND."""
+    def lstsq(A, b):
+        x, _, _, s = np.linalg.lstsq(A, b, rcond=RCOND)
+        if ratios is not None:
+            ratios.append(s / s[0] if s[0] > 0 else np.zeros_like(s))
+        return x
+
     P = np.asarray(pts, np.float64)
     u, v = P[:, 0] - P[:, 0].mean(), P[:, 1] - P[:, 1].mean()
     amax = max(np.abs(u).max(), np.abs(v).max())
     sc = 1.0 / amax if amax > 0 else 1.0
     u, v = u * sc, v * sc
-    g = np.linalg.lstsq(np.stack([-u * u, -v * v, -u * v, u, v], 1), np.ones(u.size), rcond=RCOND)[0]
-    c = np.linalg.lstsq(np.array([[2 * g[0], g[2]], [g[2], 2 * g[1]]]), g[3:5], rcond=RCOND)[0]
+    g = lstsq(np.stack([-u * u, -v * v, -u * v, u, v], 1), np.ones(u.size))
+    c = lstsq(np.array([[2 * g[0], g[2]], [g[2], 2 * g[1]]]), g[3:5])
     uu, vv = u - c[0], v - c[1]
-    h = np.linalg.lstsq(np.stack([uu * uu, vv * vv, uu * vv], 1), np.ones(u.size), rcond=RCOND)[0] * sc * sc
+    h = lstsq(np.stack([uu * uu, vv * vv, uu * vv], 1), np.ones(u.size)) * sc * sc
     th = -0.5 * np.arctan2(h[2], h[1] - h[0])
     t = h[2] / np.sin(-2.0 * th) if abs(h[2]) > 1e-8 else h[1] - h[0]
     ra, rb = abs(h[0] + h[1] - t), abs(h[0] + h[1] + t)
@@ -158,8 +165,8 @@ def fit_ellipse(pts):
     return w, hh, ang
 
 
-def shape_features(pts):
-    """Item 9: (area, hull_area, solidity, perimeter, eccentricity, major, minor, orientation)."""
+def shape_features(pts, ratios=None):
+    """Item 9: (area, hull_area, solidity, perimeter, eccentricity, major, minor, orientation).  ``ratios``: see fit_ellipse."""
     V = len(pts)
     area = abs(_shoelace2(pts)) * 0.5 if V >= 3 else 0.0
     ha = hull_area(pts) if V >= 3 else 0.0
@@ -172,7 +179,7 @@ def shape_features(pts):
             perim += float(np.sqrt(np.float32((x - px) ** 2 + (y - py) ** 2)))
             px, py = x, y
     if V > 4:
-        w, h, ang = fit_ellipse(pts)
+        w, h, ang = fit_ellipse(pts, ratios)
         major, minor = max(w, h), min(w, h)
     else:
         major, minor, ang = np.float32(1), np.float32(1), np.float32(0)
@@ -206,9 +213,9 @@ def glcm_features(fg, g):
     return d.sum() / T, (1.0 / (1.0 + d * d)).sum() / T, np.sqrt(asm), asm
 
 
-def nucleus_features(labels, gray, min_size=10):
+def nucleus_features(labels, gray, min_size=10, ratios=None):
     """Returns (features f32 [n, 16], centroids f32 [n, 2], kept_labels int32 [n], info int64 [n, 3] = contour start row, start col,
-    vertex count)."""
+    vertex count).  ``ratios`` (a dict) receives per kept label that had an ellipse fit the three arrays fit_ellipse reports."""
     labels = np.asarray(labels)
     gray = np.asarray(gray)
     if labels.shape != gray.shape:
@@ -235,7 +242,10 @@ def nucleus_features(labels, gray, min_size=10):
         dis, hom, energy, asm = glcm_features(fg, g)
         y0, x0 = choose_contour(fg)
         pts = trace_border(fg, y0, x0)
-        area, _, solidity, perim, ecc, major, minor, ang = shape_features(pts)
+        fit = None if ratios is None else []
+        area, _, solidity, perim, ecc, major, minor, ang = shape_features(pts, fit)
+        if fit:
+            ratios[int(L)] = fit
         feats[k] = [mean_fg, diff, var, skew, e[fg].mean(), dis, hom, energy, asm, ecc, area, major, minor, perim, solidity, ang]
         cens[k] = [sr[L] / cnt[L], sc[L] / cnt[L]]
         info[k] = [y0, x0, len(pts)]

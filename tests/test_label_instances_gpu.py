@@ -272,7 +272,7 @@ def test_pipeline_into_nucleus_features():
     assert np.array_equal(L.cpu().numpy(), want)
     f, c, k, info = (x.cpu().numpy() for x in nuclei.nucleus_features(L, g, return_info=True, max_label=n))
     rf, rc, rk, rinfo = nuclei_ref.nucleus_features(want, gray, min_size=10)
-    # the per-column bars of tests/test_nuclei_gpu.py::check_against_reference, restated
+    # the per-column bars of tests/nuclei_cases.py::check_against_reference, restated
     assert f.shape == rf.shape and np.array_equal(k, rk)
     assert np.array_equal(info[:, :3], rinfo)
     assert _ulp_close(c, rc).all()

@@ -8,45 +8,10 @@ from cgc_net_amd import network, nuclei
 from cgc_net_amd.data import Batch
 
 import nuclei_ref as ref
+from nuclei_cases import _gpu, check_against_reference
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda:0')
-C = {k: i for i, k in enumerate(nuclei.FEATURE_NAMES)}
-
-
-def _ulp_close(a, b, n=1):
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    tol = n * np.spacing(np.maximum(np.abs(a), np.abs(b)))
-    return np.abs(a.astype(np.float64) - b.astype(np.float64)) <= tol
-
-
-def _gpu(labels, gray, **kw):
-    f, c, k, info = nuclei.nucleus_features(torch.from_numpy(labels).to(DEV), torch.from_numpy(gray).to(DEV), return_info=True, **kw)
-    torch.cuda.synchronize()
-    return f.cpu().numpy(), c.cpu().numpy(), k.cpu().numpy(), info.cpu().numpy()
-
-
-def check_against_reference(labels, gray, min_size=10):
-    f, c, k, info = _gpu(labels, gray, min_size=min_size)
-    rf, rc, rk, rinfo = ref.nucleus_features(labels, gray, min_size=min_size)
-    assert f.shape == rf.shape and np.array_equal(k, rk)
-    assert np.array_equal(info[:, :3], rinfo), np.nonzero((info[:, :3] != rinfo).any(1))[0][:10]
-    assert _ulp_close(c, rc).all()
-    for name in ('area', 'perimeter', 'solidity', 'mean_im_out', 'diff', 'var_im'):
-        ok = _ulp_close(f[:, C[name]], rf[:, C[name]])
-        assert ok.all(), (name, np.nonzero(~ok)[0][:5], f[~ok, C[name]][:5], rf[~ok, C[name]][:5])
-    for name in ('glcm_dissimilarity', 'glcm_homogeneity', 'glcm_energy', 'glcm_ASM'):
-        np.testing.assert_allclose(f[:, C[name]], rf[:, C[name]], rtol=1e-6, atol=0, err_msg=name)
-    np.testing.assert_allclose(f[:, C['skew_im']], rf[:, C['skew_im']], rtol=0, atol=1e-6)
-    np.testing.assert_allclose(f[:, C['mean_ent']], rf[:, C['mean_ent']], rtol=1e-5, atol=0)
-    for name in ('majoraxis_length', 'minoraxis_length', 'eccentricity'):
-        np.testing.assert_allclose(f[:, C[name]], rf[:, C[name]], rtol=1e-4, atol=1e-6, err_msg=name)
-    maj, mnr = rf[:, C['majoraxis_length']].astype(np.float64), rf[:, C['minoraxis_length']].astype(np.float64)
-    sel = (maj - mnr) / np.maximum(maj, 1e-30) > 1e-3
-    d = np.abs(f[sel, C['orientation']].astype(np.float64) - rf[sel, C['orientation']]) % 180
-    assert (np.minimum(d, 180 - d) <= 1e-3).all()
-    assert np.isfinite(f).all()
-    return f, c, k, info
 
 
 @pytest.mark.parametrize('size,count,seed', [(512, 120, 0), (512, 120, 1), (512, 160, 2), (2048, 1800, 0), (2048, 1800, 1),

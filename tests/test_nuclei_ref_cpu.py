@@ -163,3 +163,185 @@ def test_inputs_are_checked_before_any_launch():
         nuclei.nucleus_features(torch.zeros(4, 4), torch.zeros(4, 4, dtype=torch.uint8))
     with pytest.raises(ValueError):
         nuclei.nucleus_features(torch.full((4, 4), -2, dtype=torch.int64), torch.zeros(4, 4, dtype=torch.uint8))
+
+
+# ---- the hand-made scenes of tests/nuclei_cases.py: they are what they claim, and the restatement is right on them
+import nuclei_cases as cases  # noqa: E402
+
+_SCENE_REF = {}
+
+
+def _scene(name):
+    """(labels, gray, min_size, names, features, centroids, kept, info, fit ratios by label): computed once per scene."""
+    if name not in _SCENE_REF:
+        labels, gray, min_size, names = cases.SCENES[name]()
+        ratios = {}
+        out = ref.nucleus_features(labels, gray, min_size=min_size, ratios=ratios)
+        _SCENE_REF[name] = (labels, gray, min_size, names) + out + (ratios,)
+    return _SCENE_REF[name]
+
+
+def _row(name, shape):
+    labels, gray, _, names, f, c, kept, info, _ = _scene(name)
+    i = int(np.nonzero(kept == cases.by_name(names)[shape])[0][0])
+    return f[i], c[i], info[i]
+
+
+@pytest.mark.parametrize('name', sorted(cases.SCENES))
+def test_scene_is_well_formed_and_deterministic(name):
+    labels, gray, min_size, names = cases.SCENES[name]()
+    again = cases.SCENES[name]()
+    assert labels.dtype == np.int32 and gray.dtype == np.uint8 and labels.shape == gray.shape
+    assert labels.shape[0] <= 512 and labels.shape[1] <= 512
+    assert np.array_equal(labels, again[0]) and np.array_equal(gray, again[1])
+    assert set(names) == set(np.unique(labels[labels > 0]).tolist())
+    assert np.isfinite(_scene(name)[4]).all()
+
+
+@pytest.mark.parametrize('name', sorted(cases.SCENES))
+def test_scene_fits_are_clear_of_the_rank_threshold(name):
+    """A condition on the inputs: every singular-value ratio of every ellipse fit is two decades away from the 1e-6 at which the
+    restatement (lstsq) and the kernel (normal equations) drop a direction, so both drop the same ones."""
+    ratios = _scene(name)[8]
+    r = np.concatenate([x for fit in ratios.values() for x in fit]) if ratios else np.zeros(0)
+    assert ((r >= 1e-4) | (r <= 1e-8)).all(), r[(r < 1e-4) & (r > 1e-8)]
+    assert all(len(fit) == 3 and [x.size for x in fit] == [5, 2, 3] for fit in ratios.values())
+    if name == 'shapes':
+        by = cases.by_name(_scene(name)[3])
+        assert ratios[by['L']][2].min() <= 1e-8 and ratios[by['staircase']][1].min() <= 1e-8      # dropped directions are reached
+        assert set(ratios) == {by[k] for k in ('plus', 'dumbbell', 'L', 'staircase', 'staircase_blocks', 'thin_ellipse', 'ring',
+                                               'ring_inner')}
+
+
+def test_fit_ellipse_report_leaves_the_values_alone():
+    pts = [(0, 0), (5, 1), (9, 4), (8, 9), (3, 10), (-2, 6)]
+    got = []
+    assert ref.fit_ellipse(pts, got) == ref.fit_ellipse(pts) and len(got) == 3
+    assert all(x[0] == 1 and (np.diff(x) <= 0).all() for x in got)
+
+
+def test_shapes_crops_on_both_sides_of_the_lds_limit():
+    labels, _, min_size, names = cases.shapes()
+    by = cases.by_name(names)
+    assert min_size == 1
+    assert [cases.crop_pixels(labels, by[k]) for k in ('rect_lds_2048', 'rect_global_2080', 'rect_corner_2048')] == [2048, 2080, 2048]
+    assert cases.LDS_PIXELS == 2048
+    r0, r1, c0, c1 = cases.crop_box(labels, by['rect_corner_2048'])
+    assert (r1, c1) == labels.shape and (labels[r0:r1, c0:c1] == by['rect_corner_2048']).all()      # clipped: no background pixel
+    for L, name in names.items():                    # every shape but the ring pair keeps clear of the others' crops
+        r0, r1, c0, c1 = cases.crop_box(labels, L)
+        inside = set(np.unique(labels[r0:r1, c0:c1]).tolist()) - {0, L}
+        assert inside == ({by['ring_inner']} if name == 'ring' else set()), (name, inside)
+
+
+def test_shapes_few_vertices_closed_forms():
+    f, _, info = _row('shapes', 'pixel')
+    assert info.tolist() == [0, 0, 1]
+    assert f[COL['area']] == 0 and f[COL['perimeter']] == 0 and f[COL['solidity']] == 0
+    assert (f[COL['majoraxis_length']], f[COL['minoraxis_length']], f[COL['orientation']], f[COL['eccentricity']]) == (1, 1, 0, 0)
+    for shape, length in (('hline', 2.0 * 11), ('vline', 2.0 * 11), ('diagonal', 2 * np.sqrt(2.0) * 11)):
+        f, _, info = _row('shapes', shape)
+        assert info.tolist() == [0, 0, 2], shape
+        assert f[COL['area']] == 0 and f[COL['solidity']] == 0, shape                    # hull 0 -> 1, area 0
+        assert f[COL['perimeter']] == pytest.approx(length, rel=1e-6), shape
+        assert (f[COL['majoraxis_length']], f[COL['minoraxis_length']], f[COL['orientation']]) == (1, 1, 0), shape
+    f, _, info = _row('shapes', 'block2')
+    assert info.tolist() == [0, 0, 4] and (f[COL['area']], f[COL['perimeter']], f[COL['solidity']]) == (1, 4, 1)
+    f, _, info = _row('shapes', 'rect_5x9')
+    assert info.tolist() == [0, 0, 4] and (f[COL['area']], f[COL['perimeter']], f[COL['solidity']]) == (4 * 8, 2 * (4 + 8), 1)
+
+
+def test_shapes_repeated_contour_pixels():
+    """One-pixel strokes and bridges put a pixel on the contour more than once; the hull still closes, on coordinates."""
+    labels, gray, min_size, names = _scene('shapes')[:4]
+    by = cases.by_name(names)
+    for shape, hull2 in (('dumbbell', 2 * 6 * 17), ('staircase', 2 * 5), ('staircase_blocks', 2 * 21)):
+        r0, r1, c0, c1 = cases.crop_box(labels, by[shape])
+        fg = labels[r0:r1, c0:c1] > 0
+        pts = ref.trace_border(fg, *ref.choose_contour(fg))
+        assert len(set(pts)) < len(pts), shape
+        assert 2 * ref.hull_area(pts) == hull2, shape
+        f, _, info = _row('shapes', shape)
+        assert info[2] == len(pts) and f[COL['solidity']] == np.float32(f[COL['area']].astype(np.float64) * 2 / hull2), shape
+    f, _, info = _row('shapes', 'L')
+    # the way back cuts the corner, (1, 11) -> (0, 10): the stroke encloses half a pixel; hull = the triangle 9 * 11 / 2
+    assert info[2] == 5 and f[COL['area']] == 0.5 and f[COL['solidity']] == np.float32(1 / 99)
+    f, _, _ = _row('shapes', 'dumbbell')
+    assert f[COL['area']] == 2 * 36 + 4 * 0.5        # the bridge itself adds nothing; entering and leaving it cuts four corners
+
+
+def test_shapes_zero_rules_of_moments_and_glcm():
+    glcm = [COL[k] for k in ('glcm_dissimilarity', 'glcm_homogeneity', 'glcm_energy', 'glcm_ASM')]
+    f, _, _ = _row('shapes', 'vline')
+    assert (f[glcm] == 0).all()                                                             # no horizontal pair at all
+    f, _, _ = _row('shapes', 'block_const')
+    assert f[COL['var_im']] == 0 and f[COL['skew_im']] == 0 and f[COL['mean_ent']] == 0
+    assert f[COL['glcm_dissimilarity']] == 0 and (f[glcm[1:]] == 1).all()
+    assert f[COL['mean_im_out']] == pytest.approx(77, rel=1e-6) and f[COL['diff']] < 1e-4
+    f, _, _ = _row('shapes', 'block_zero')
+    assert (f[:9] == 0).all()                                                               # gray 0: no GLCM pair, T -> 1
+    f, _, _ = _row('shapes', 'rect_corner_2048')
+    assert f[COL['diff']] == f[COL['mean_im_out']] and f[COL['mean_im_out']] > 0            # n_bg = 0
+
+
+def test_shapes_ring_and_the_nucleus_in_its_hole():
+    labels, _, _, names, f, c, kept, info, _ = _scene('shapes')
+    by = cases.by_name(names)
+    assert by['ring'] in kept and by['ring_inner'] in kept
+    _, _, ring = _row('shapes', 'ring')
+    r0, r1, c0, c1 = cases.crop_box(labels, by['ring'])
+    crop = labels[r0:r1, c0:c1]
+    assert (crop == by['ring_inner']).any()                                                 # the later-starting component is in the crop
+    assert crop[ring[0], ring[1]] == by['ring'] and ring[1] > 0                             # ... and the contour starts on the ring
+    assert ring[:2].tolist() == list(divmod(int(np.flatnonzero(crop == by['ring'])[0]), crop.shape[1]))
+    _, _, inner = _row('shapes', 'ring_inner')
+    r0, r1, c0, c1 = cases.crop_box(labels, by['ring_inner'])
+    assert labels[r0 + inner[0], c0 + inner[1]] == by['ring_inner'] and inner[2] > 4
+
+
+def test_many_big_fills_the_slots_more_than_once():
+    labels, _, min_size, names = cases.many_big()
+    px = np.array([cases.crop_pixels(labels, L) for L in sorted(names)])
+    assert px.size == 40 > cases.BIG_SLOTS and (px > cases.LDS_PIXELS).all() and min_size == 10
+    for j in range(cases.BIG_SLOTS, 40):             # crop j runs after crop j - 32 in the same slot, and is smaller
+        assert px[j] < px[j - cases.BIG_SLOTS], (j, px[j], px[j - cases.BIG_SLOTS])
+    for L in names:                                  # no ellipse reaches into another crop
+        r0, r1, c0, c1 = cases.crop_box(labels, L)
+        assert set(np.unique(labels[r0:r1, c0:c1]).tolist()) <= {0, L}
+
+
+def test_spirals_are_single_components_one_pixel_wide():
+    labels, _, _, names = cases.spirals()
+    by = cases.by_name(names)
+    assert [cases.crop_pixels(labels, by[k]) for k in ('spiral_global', 'spiral_lds')] == [4096, 2025]
+    for L in names:
+        m = labels == L
+        assert ndi_count(m) == 1
+        full = (m[:-1, :-1] & m[1:, :-1] & m[:-1, 1:] & m[1:, 1:]).any()
+        assert not full and m.sum() > 0.45 * cases.crop_pixels(labels, L)                  # one pixel wide, about every other line
+    a, b = (labels[cases.crop_box(labels, by[k])[0]:, cases.crop_box(labels, by[k])[2]:] > 0 for k in ('spiral_global', 'spiral_lds'))
+    assert a[1, 0] != b[1, 0]                        # opposite senses: one goes down its left side, the other its right
+    info = _scene('spirals')[7]
+    assert (info[:, 2] > 100).all()
+
+
+def test_stripes_and_label_edges_keep_what_they_claim():
+    labels, gray, min_size, _ = cases.stripes()
+    assert labels.shape == (40, 67) and min_size == 10
+    _, c, kept, _ = ref.nucleus_features(labels, gray, min_size=min_size)
+    assert kept.tolist() == list(range(1, 68))
+    assert np.array_equal(c, np.stack([np.full(67, 19.5), np.arange(67)], 1).astype(np.float32))
+    labels, gray, min_size, _ = cases.label_edges()
+    counts = np.bincount(labels.ravel())
+    assert min_size == 10 and all(counts[L] == 12 for L in cases.LABEL_EDGE_KEPT)
+    for keptL, L in cases.LABEL_EDGE_DROPPED.items():
+        r0, r1, c0, c1 = cases.crop_box(labels, keptL)
+        assert counts[L] == 9 and (labels[r0:r1, c0:c1] == L).sum() == 3                    # one column inside the kept crop
+    for ms in (10, 12):
+        f, _, kept, info = ref.nucleus_features(labels, gray, min_size=ms)
+        assert kept.tolist() == list(cases.LABEL_EDGE_KEPT) and (info == [0, 0, 4]).all()
+    assert ref.nucleus_features(labels, gray, min_size=13)[2].size == 0
+    f9 = ref.nucleus_features(labels, gray, min_size=9)
+    assert f9[2].size == 13                          # at 9 the neighbours count: the rule under test changes the kept rows' crops
+    i9, i10 = f9[2].tolist().index(65), list(cases.LABEL_EDGE_KEPT).index(65)
+    assert f9[0][i9, COL['diff']] != f[i10, COL['diff']]
