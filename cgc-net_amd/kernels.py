@@ -19,6 +19,8 @@ L2_EPS = 1e-12       # F.normalize eps
 RENORM_EPS = 1e-15   # model/network.py:8
 EDT_INF = 2 ** 31 - 1      # CGC_EDT_INF: dist2 of a pixel without a site (within the bound)
 EDT_MAX_SIDE = 32767       # 2 * 32766^2 < 2^31 - 1: squared distances fit int32
+GEO_INF = 2 ** 31 - 1      # CGC_GEO_INF: dist of a pixel that no seed reaches (within the bound)
+GEO_FIRST_BATCH, GEO_MAX_BATCH = 8, 64      # rounds of geodesic_transform per host read: 8, 16, 32, 64, 64, ...
 
 
 class KernelSpec(object):
@@ -127,6 +129,36 @@ class KernelSpec(object):
         7.  H * W = 0 gives empty outputs.
         The result is a pure function of the input.  Cost per pixel grows with the distance to its nearest site, capped by
         sqrt(d2max): O(W) per pixel where a row's columns hold no site at all."""
+        raise NotImplementedError
+
+    def geodesic_transform(self, seeds, within, a, b, connectivity, dmax, want_nearest=False):
+        """Geodesic distance transform of one image with the nearest seed of every pixel (F7, beside distance_transform;
+        csrc/geodesic.hip): distance is measured along paths that stay inside a domain.  Returns (dist int32 [H, W], nearest int32
+        [H, W] or None).  All arithmetic is integer: every result is exact and a pure function of the input.
+
+        1.  seeds, within: contiguous [H, W] of a 1-, 2-, 4- or 8-byte integer type or bool; only "is zero" is read.  The domain is
+            D = {within != 0} u {seeds != 0}: a seed always belongs to it.  within = None: every pixel.
+        2.  An axial step between two 4-neighbours that are both in D costs a, a diagonal step between two corner neighbours that are
+            both in D costs b; b == 0: no diagonal steps.  1 <= a <= b <= 2a or b == 0 (ValueError).  connectivity 2: a diagonal step
+            needs only its two end points in D.  connectivity 1: the diagonal step (y, x) -> (y + dy, x + dx) also needs (y + dy, x)
+            or (y, x + dx) in D -- a path never squeezes through a corner contact.  So the reached pixels are exactly the pixels of
+            those ``connectivity``-components of D that hold a seed (with b == 0: of the connectivity-1 components).
+        3.  dist[p] = the smallest path cost from any seed pixel, 0 on seeds; nearest[p] = the raster index y' * W + x' of the seed
+            that attains it, ties to the SMALLEST raster index (distance_transform's rule).  A domain pixel that no seed reaches and
+            every pixel outside D: GEO_INF (2^31 - 1) and -1.  nearest is only unpacked with want_nearest.
+        4.  dmax >= 0: pixels whose true cost exceeds dmax report GEO_INF and -1, all others are exact; dmax < 0: no bound.
+        5.  (b or a) * H * W < 2^31, so that no path cost overflows int32 (ValueError otherwise, nothing is launched).  H * W = 0 gives
+            empty outputs.
+        Why a parallel relaxation gives exactly this: with key = (dist, seed index) packed into 64 bits, the definition is the unique
+        fixed point of key[p] = min(key0[p], min over steps q -> p of (key[q].dist + cost, key[q].seed)) -- the predecessor of p on a
+        shortest path from the winning seed carries the same seed, costs are positive, keys only decrease -- whatever the order of the
+        updates.  Rounds are launches (one 64 x 64 tile per workgroup, relaxed to its own fixed point in LDS; a tile whose keys and
+        halo did not move since its last run costs one load), and the loop is here: the host reads the number of tiles that moved in
+        the last round of a batch of GEO_FIRST_BATCH (8), then twice as many up to GEO_MAX_BATCH (64), rounds.  Host reads: one per
+        batch.  R = 2 + the tile edges that the longest shortest path crosses rounds are needed (the last one moves nothing), so: one
+        read when it crosses at most six (a bound of a few pixels, even where a porous domain makes the path weave across an edge),
+        otherwise the smallest k with 8 (2^k - 1) >= R (k <= 3), and one more per 64 rounds beyond 56.
+        Worst case: a serpentine corridor over a whole image crosses a tile edge per turn and needs hundreds of rounds."""
         raise NotImplementedError
 
     def bgr_to_gray(self, bgr):
@@ -657,6 +689,42 @@ class HipKernels(KernelSpec):
         self._chk(self.lib.cgc_edt(_ptr(image), image.element_size(), H, W, int(bool(sites_nonzero)), int(d2max), _ptr(ws), _ptr(dist2),
                                    _ptr(nearest), self._stream()), 'cgc_edt')
         return dist2, nearest
+
+    def geodesic_transform(self, seeds, within, a, b, connectivity, dmax, want_nearest=False):
+        self._dev(seeds, within)
+        for t in (seeds, within):
+            assert t is None or (t.dim() == 2 and t.is_contiguous() and t.element_size() in (1, 2, 4, 8) and not t.is_floating_point())
+        assert within is None or within.shape == seeds.shape
+        H, W = seeds.shape
+        a, b = int(a), int(b)
+        if a < 1 or (b != 0 and not a <= b <= 2 * a):
+            raise ValueError('geodesic_transform needs steps 1 <= a <= b <= 2a or b == 0 (got a = %d, b = %d)' % (a, b))
+        if connectivity not in (1, 2):
+            raise ValueError('connectivity must be 1 or 2, got %r' % (connectivity,))
+        if (b or a) * H * W >= 2 ** 31:
+            raise ValueError('geodesic_transform: %d * %d * %d reaches 2^31: a path cost must fit int32' % (b or a, H, W))
+        dev = seeds.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        dist = torch.empty(H, W, **i32)
+        nearest = torch.empty(H, W, **i32) if want_nearest else None
+        if H * W == 0:
+            return dist, nearest
+        ws = torch.empty(int(self.lib.cgc_geodesic_ws_bytes(H, W)), dtype=torch.uint8, device=dev)
+        changed = torch.empty(1, **i32)
+        st = self._stream()
+        self._chk(self.lib.cgc_geodesic_begin(_ptr(seeds), seeds.element_size(), _ptr(within), within.element_size() if within is not None else 0,
+                                              H, W, a, b, _ptr(ws), st), 'cgc_geodesic_begin')
+        done, batch = 0, GEO_FIRST_BATCH
+        while True:
+            self._chk(self.lib.cgc_geodesic_rounds(H, W, a, b, int(connectivity), int(dmax), _ptr(ws), done, batch, _ptr(changed), st),
+                      'cgc_geodesic_rounds')
+            done += batch
+            if int(changed.item()) == 0:                # the host sync of this stage, once per batch: did the last round move a key?
+                break
+            batch = min(2 * batch, GEO_MAX_BATCH)
+        self.geodesic_rounds = done                     # rounds launched by the last call (tests, tools)
+        self._chk(self.lib.cgc_geodesic_finish(H, W, _ptr(ws), _ptr(dist), _ptr(nearest), st), 'cgc_geodesic_finish')
+        return dist, nearest
 
     def bgr_to_gray(self, bgr):
         self._dev(bgr)

@@ -8,7 +8,10 @@ contract item by item: kernels.KernelSpec.label_components).  Its ``labels`` and
 
 ``distance_transform``, ``expand_labels`` and ``split_touching`` sit between the two: an exact Euclidean distance transform with the
 nearest site of every pixel (csrc/edt.hip; kernels.KernelSpec.distance_transform), skimage's expand_labels on top of it, and the
-erode-label-grow split that keeps touching nuclei from merging into one node.
+erode-label-grow split that keeps touching nuclei from merging into one node.  ``geodesic_distance_transform`` measures distance
+along paths that stay inside a mask instead (csrc/geodesic.hip; kernels.KernelSpec.geodesic_transform): ``expand_labels(...,
+geodesic=True)`` grows labels along such paths, so that no label reaches across a gap, and ``split_touching(..., growth='geodesic')``
+gives every mask pixel that is connected to a core the geodesically nearest core.
 
 ``nucleus_features(labels, gray)`` returns the reference's ``feature`` / ``coordinate`` arrays of one image (csrc/nuclei.hip; the
 arithmetic item by item: kernels.KernelSpec.nucleus_features), ``graph_item`` turns them into the ``Data`` that
@@ -32,6 +35,8 @@ FEATURE_NAMES = ('mean_im_out', 'diff', 'var_im', 'skew_im', 'mean_ent', 'glcm_d
                  'glcm_ASM', 'eccentricity', 'area', 'majoraxis_length', 'minoraxis_length', 'perimeter', 'solidity', 'orientation')
 _INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
 EDT_INF = kernels.EDT_INF          # dist2 of a pixel that has no site (within max_distance)
+GEO_INF = kernels.GEO_INF          # geodesic dist of a pixel that no seed reaches (within max_distance)
+GEODESIC_STEPS = {'cityblock': (1, 0), 'chessboard': (1, 1), 'chamfer': (5, 7)}      # (axial, diagonal) step costs; 0: no such step
 
 
 def label_instances(image, connectivity=1, min_size=0, return_sizes=False):
@@ -65,7 +70,7 @@ def label_instances(image, connectivity=1, min_size=0, return_sizes=False):
     return (labels, n, sizes) if return_sizes else (labels, n)
 
 
-def _check_image(fn, name, image):
+def _check_image(fn, name, image, max_side=True):
     if not torch.is_tensor(image) or not image.is_cuda:
         raise TypeError('%s takes torch tensors on the GPU' % fn)
     if image.dtype != torch.bool and image.dtype not in _INT_DTYPES:
@@ -73,7 +78,7 @@ def _check_image(fn, name, image):
     if image.dim() != 2:
         raise ValueError('%s must be 2-D (got %s)' % (name, tuple(image.shape)))
     H, W = image.shape
-    if H > kernels.EDT_MAX_SIDE or W > kernels.EDT_MAX_SIDE:
+    if max_side and (H > kernels.EDT_MAX_SIDE or W > kernels.EDT_MAX_SIDE):
         raise ValueError('%s: sides over %d pixels are not supported (%d x %d): a squared distance must fit int32'
                          % (fn, kernels.EDT_MAX_SIDE, H, W))
 
@@ -115,7 +120,86 @@ def distance_transform(image, sites='zero', max_distance=None, return_nearest=Fa
     return (dist2, nearest) if return_nearest else dist2
 
 
-def expand_labels(labels, distance, within=None):
+def _check_within(fn, within, image):
+    _check_image(fn, 'within', within, max_side=False)
+    if tuple(within.shape) != tuple(image.shape) or within.device != image.device:
+        raise ValueError('within must have the shape and device of the image (got %s on %s and %s on %s)'
+                         % (tuple(within.shape), within.device, tuple(image.shape), image.device))
+
+
+def _geodesic_steps(metric):
+    """(a, b) of a name of GEODESIC_STEPS or of an (a, b) pair of integers with 1 <= a <= b <= 2a or b == 0."""
+    if isinstance(metric, str):
+        if metric not in GEODESIC_STEPS:
+            raise ValueError('metric must be one of %s or an (a, b) pair, got %r' % (sorted(GEODESIC_STEPS), metric))
+        return GEODESIC_STEPS[metric]
+    try:
+        a, b = metric
+        ok = int(a) == a and int(b) == b and int(a) >= 1 and (int(b) == 0 or int(a) <= int(b) <= 2 * int(a))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('metric must be one of %s or a pair of integer step costs (a, b) with 1 <= a <= b <= 2a or b == 0, got %r'
+                         % (sorted(GEODESIC_STEPS), metric))
+    return int(a), int(b)
+
+
+def _geodesic_bound(distance, a, name):
+    """The largest integer k with k / a <= distance (a distance in pixels -> a bound in raw cost units), capped at GEO_INF - 1, which no
+    path cost of a supported image exceeds.  int(d * a) alone can be off by one in either direction: its neighbours are checked."""
+    d = float(distance)
+    if not d >= 0:
+        raise ValueError('%s must be a number >= 0 (got %r)' % (name, distance))
+    if d * a >= GEO_INF:
+        return GEO_INF - 1
+    k = int(d * a)
+    while (k + 1) / a <= d:
+        k += 1
+    while k > 0 and k / a > d:
+        k -= 1
+    return k
+
+
+def _geodesic(fn, seeds, within, metric, connectivity, distance, name, want_nearest):
+    _check_image(fn, 'seeds' if fn == 'geodesic_distance_transform' else 'labels', seeds, max_side=False)
+    if within is not None:
+        _check_within(fn, within, seeds)
+    a, b = _geodesic_steps(metric)
+    if connectivity not in (1, 2):
+        raise ValueError('connectivity must be 1 (4 neighbours) or 2 (8 neighbours), got %r' % (connectivity,))
+    dmax = -1 if distance is None else _geodesic_bound(distance, a, name)
+    H, W = seeds.shape
+    if (b or a) * H * W >= 2 ** 31:
+        raise ValueError('%s: images of %d x %d pixels are not supported with step costs (%d, %d): a path cost must fit int32'
+                         % (fn, H, W, a, b))
+    with torch.cuda.device(seeds.device):
+        return kernels.get().geodesic_transform(seeds.contiguous(), None if within is None else within.contiguous(), a, b,
+                                                int(connectivity), dmax, bool(want_nearest))
+
+
+def geodesic_distance_transform(seeds, within=None, metric='chamfer', connectivity=1, max_distance=None, return_nearest=False):
+    """seeds, within: 2-D bool / uint8 / int8 / int16 / int32 / int64 tensors on the same GPU, of the same shape, any strides.  Returns
+    dist (int32 [H, W]): the smallest cost of a path from any seed (a non-zero pixel of ``seeds``) to the pixel that stays inside the
+    domain {within != 0} u {seeds != 0} (``within=None``: the whole image), 0 on seeds -- and, with ``return_nearest``, nearest (int32
+    [H, W]): the raster index y' * W + x' of the seed that attains it, of several the one with the smallest raster index.  ``metric``:
+    a name of GEODESIC_STEPS -- 'cityblock' (1, 0), 'chessboard' (1, 1), 'chamfer' (5, 7) -- or a pair (a, b) of integers with 1 <= a
+    <= b <= 2a or b == 0: an axial step costs a, a diagonal one b, b == 0 means no diagonal steps.  ``dist`` is in raw cost units:
+    ``dist / a`` is the distance in pixels.  ``connectivity`` 2: a diagonal step needs only its two end points in the domain; 1
+    (default): also one of the two pixels it passes between, so a path never squeezes through a corner contact -- the reached pixels
+    are exactly the ``connectivity``-components of the domain that hold a seed.  A pixel outside the domain, or one no seed can reach,
+    reports GEO_INF (2^31 - 1) and -1.  ``max_distance`` (pixels, float >= 0): pixels whose cost exceeds the largest integer k with
+    k / a <= max_distance report GEO_INF and -1, all others are exact.  (b or a) * H * W must stay below 2^31 (ValueError).
+
+    Host syncs: one per batch of relaxation rounds (8, then 16, 32, then 64 rounds each) until a round moves nothing: one when the
+    growth crosses at most six edges of the 64 x 64 tiles (any bound of a few pixels), three for 56 rounds.  The number of rounds
+    is 2 + the tile edges crossed by the longest shortest path: a serpentine corridor over a whole image is the case to avoid or to
+    bound (kernels.KernelSpec.geodesic_transform)."""
+    dist, nearest = _geodesic('geodesic_distance_transform', seeds, within, metric, connectivity, max_distance, 'max_distance',
+                              return_nearest)
+    return (dist, nearest) if return_nearest else dist
+
+
+def expand_labels(labels, distance, within=None, geodesic=False, metric='chamfer', connectivity=1):
     """skimage.segmentation.expand_labels on the GPU, with a stated tie rule.  labels: 2-D bool / integer tensor on the GPU (0 =
     background).  Every background pixel whose nearest labelled pixel lies within ``distance`` (Euclidean, sqrt(dist2) <= distance)
     takes that pixel's value; of several equally near labelled pixels the one with the smallest raster index decides.  ``within``
@@ -124,7 +208,21 @@ def expand_labels(labels, distance, within=None):
     can reach across a gap of ``within``.  Labelled pixels never change; the output has the input's dtype.  The distance transform
     underneath is bounded by ``distance``.
 
-    Host syncs: none."""
+    ``geodesic=True``: nearness is geodesic instead -- the seeds are the labelled pixels, the domain is ``within`` (None: the whole
+    image), and a background pixel of the domain whose path cost (``metric``, ``connectivity``: see geodesic_distance_transform) is
+    within ``distance`` pixels takes the value of the labelled pixel that attains it (ties: the smallest raster index): no label
+    crosses a gap of ``within``.  ``distance=None`` (only then) means unbounded: every domain pixel joined to a label is filled.
+
+    Host syncs: none; with ``geodesic=True`` those of geodesic_distance_transform (one for a bound of a few pixels)."""
+    if geodesic:
+        _, nearest = _geodesic('expand_labels', labels, within, metric, connectivity, distance, 'distance', True)
+        if labels.numel() == 0:
+            return labels.clone()
+        # a labelled pixel is its own nearest seed; nearest = -1: outside the domain, not joined to a label or beyond the bound
+        src = labels.reshape(-1)[nearest.clamp(min=0).reshape(-1).long()].reshape(labels.shape)
+        return torch.where(nearest >= 0, src, labels)
+    if distance is None:
+        raise ValueError('distance=None (unbounded growth) needs geodesic=True')
     _check_image('expand_labels', 'labels', labels)
     d2max = _d2max(distance, 'distance')
     if within is not None:
@@ -143,7 +241,7 @@ def expand_labels(labels, distance, within=None):
     return torch.where(fill, src, labels)
 
 
-def split_touching(mask, core_radius, connectivity=1, min_size=0):
+def split_touching(mask, core_radius, connectivity=1, min_size=0, growth='euclidean'):
     """The erode-label-grow split of a foreground mask (2-D bool / integer tensor on the GPU, 0 = background) into instances, for
     nuclei that touch: returns (labels int32 [H, W], n) as ``label_instances`` does, ready for ``nucleus_features(labels, gray,
     max_label=n)``.
@@ -158,8 +256,17 @@ def split_touching(mask, core_radius, connectivity=1, min_size=0):
          numbers the result 1..n by first pixel.
     ``core_radius`` = 0 is label_instances(mask != 0, connectivity, min_size).
 
-    Host syncs: three, the reads of n of the three labelling calls."""
+    ``growth='geodesic'``: step 3 is expand_labels(cores, None, within=mask, geodesic=True, connectivity=connectivity) instead --
+    unbounded, chamfer (5, 7) steps along paths inside the mask: every mask pixel that is connected to a core takes the geodesically
+    nearest core, however narrow the part it sits in, and never a core of another object.  Step 4 is then exactly the components
+    that hold no core.  The Euclidean growth cannot reach parts narrower than the core radius (tapered tips, necks), which become
+    instances of their own, and hands pixels to the nearest core across a gap, which step 5 splits off as fragments.
+
+    Host syncs: three, the reads of n of the three labelling calls; with ``growth='geodesic'`` plus those of the convergence loop of
+    geodesic_distance_transform (one when the longest path inside a nucleus crosses at most six tile edges, two up to 22)."""
     _check_image('split_touching', 'mask', mask)
+    if growth not in ('euclidean', 'geodesic'):
+        raise ValueError("growth must be 'euclidean' or 'geodesic', got %r" % (growth,))
     radius2 = _d2max(core_radius, 'core_radius')
     if connectivity not in (1, 2):
         raise ValueError('connectivity must be 1 (4 neighbours) or 2 (8 neighbours), got %r' % (connectivity,))
@@ -170,7 +277,10 @@ def split_touching(mask, core_radius, connectivity=1, min_size=0):
     fg = mask != 0
     dist2 = distance_transform(fg)
     cores, k = label_instances(dist2 > radius2, connectivity)
-    grown = expand_labels(cores, float(core_radius) + 1.0, within=fg)
+    if growth == 'geodesic':
+        grown = expand_labels(cores, None, within=fg, geodesic=True, connectivity=connectivity)
+    else:
+        grown = expand_labels(cores, float(core_radius) + 1.0, within=fg)
     rest, _ = label_instances(fg & (grown == 0), connectivity)
     combined = torch.where(rest > 0, rest + k, grown)
     return label_instances(combined, connectivity, min_size)

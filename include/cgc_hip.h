@@ -57,8 +57,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *   9: nucleus features from instance masks: cgc_nuclei_lds_max_pixels, cgc_nuclei_ws_bytes, cgc_nuclei_label_pass,
  *      cgc_nuclei_big_ws_bytes, cgc_nuclei_features, cgc_bgr_to_gray
  *  10: connected-component labelling in front of them: cgc_label_ws_bytes, cgc_label_components, cgc_label_sizes
- *  11: exact distance transform with nearest sites: cgc_edt_ws_bytes, cgc_edt, CGC_EDT_INF */
-#define CGC_ABI_VERSION 11
+ *  11: exact distance transform with nearest sites: cgc_edt_ws_bytes, cgc_edt, CGC_EDT_INF
+ *  12: geodesic distance transform with nearest seeds: cgc_geodesic_ws_bytes, cgc_geodesic_begin, cgc_geodesic_rounds,
+ *      cgc_geodesic_finish, CGC_GEO_INF */
+#define CGC_ABI_VERSION 12
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -167,6 +169,32 @@ int cgc_label_sizes(const void* ws, int H, int W, int n, int* sizes, cgc_stream_
 int64_t cgc_edt_ws_bytes(int H, int W);
 int cgc_edt(const void* image, int elem_bytes, int H, int W, int sites_nonzero, int d2max, void* ws, int* dist2, int* nearest_or_null,
             cgc_stream_t stream);
+
+/* ---- F7 (beside F6): geodesic distance transform of a 2-D image with the nearest seed of every pixel (csrc/geodesic.hip): distance is
+ * measured along paths that stay inside a domain, which F6 cannot do.  The contract item by item: cgc-net_amd/kernels.py
+ * KernelSpec.geodesic_transform.  seeds, within_or_null [H, W] of 1, 2, 4 or 8 bytes per pixel (only "is zero" is used); the domain is
+ * {within != 0} u {seeds != 0}, every pixel when within is NULL.  An axial step between two domain pixels costs a, a diagonal one b
+ * (b = 0: no diagonal steps); 1 <= a <= b <= 2a or b = 0.  connectivity 2: a diagonal step needs its two end points in the domain;
+ * connectivity 1: also one of the two pixels it passes between.  (b != 0 ? b : a) * H * W < 2^31, so that no path cost overflows int32;
+ * otherwise CGC_EINVAL and nothing is launched.  ws = cgc_geodesic_ws_bytes(H, W) bytes (0: H * W is out of range).
+ *   cgc_geodesic_begin: keys and domain into ws (one launch).
+ *   cgc_geodesic_rounds: rounds number first_round .. first_round + rounds - 1 of the relaxation, one launch each (plus one 4-byte
+ *     fill); the first call after begin passes first_round = 0, every later one the number of rounds already launched.  *changed
+ *     (device) = the number of tiles whose keys moved in the LAST of these rounds: 0 means the keys are final (further rounds are
+ *     harmless).  dmax >= 0: costs above dmax are never stored; dmax < 0: no bound.  a, b, connectivity as given to begin.
+ *   cgc_geodesic_finish: dist int32 [H, W] = the smallest path cost from a seed (0 on seeds), nearest int32 [H, W] or NULL (skipped) =
+ *     the raster index y' * W + x' of the seed that attains it, of several the smallest index.  A pixel outside the domain, one that no
+ *     seed reaches, or one whose cost exceeds dmax: CGC_GEO_INF and -1.  H * W = 0: nothing is written.
+ * No workgroup waits for another one in any launch, nothing allocates or synchronises: the caller reads *changed between batches of
+ * rounds.  The result is exact and a pure function of the input.  Worst case: the number of rounds needed is 2 + the number of 64 x 64
+ * tile edges that the longest shortest path crosses -- a serpentine corridor over a whole image needs hundreds. */
+#define CGC_GEO_INF 2147483647
+int64_t cgc_geodesic_ws_bytes(int H, int W);
+int cgc_geodesic_begin(const void* seeds, int seed_bytes, const void* within_or_null, int within_bytes, int H, int W, int a, int b,
+                       void* ws, cgc_stream_t stream);
+int cgc_geodesic_rounds(int H, int W, int a, int b, int connectivity, int dmax, void* ws, int first_round, int rounds, int* changed,
+                        cgc_stream_t stream);
+int cgc_geodesic_finish(int H, int W, const void* ws, int* dist, int* nearest_or_null, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
