@@ -16,15 +16,14 @@
 #include <stdint.h>
 
 #include "common.hpp"
+#include "image_common.hpp"
 
 namespace {
 
 constexpr int EDT_SEG = 64;               // rows per column segment: one bit each in a 64-bit word
 constexpr int EDT_MAX_SIDE = 32767;       // 2 * 32766^2 < 2^31 - 1: every distance^2 fits int32 below CGC_EDT_INF; rows fit int16
 
-static inline int64_t edt_align256(int64_t b) { return (b + 255) / 256 * 256; }
 static inline int edt_segments(int H) { return ceil_div(H, EDT_SEG); }
-static inline int64_t edt_mask_bytes(int H, int W) { return edt_align256((int64_t)edt_segments(H) * W * 8); }
 static inline bool edt_bad_dims(int H, int W) { return H < 0 || W < 0 || H > EDT_MAX_SIDE || W > EDT_MAX_SIDE; }
 
 // (a) site words.  Consecutive threads read consecutive pixels of a row.
@@ -128,18 +127,28 @@ static inline int edt_window(int d2max, int W) {        // min(floor(sqrt(d2max)
   return r;
 }
 
+struct EdtWs {
+  unsigned long long* mask;      // [segments, W] site words
+  short* srow;                   // [H, W] nearest site row of the pixel's own column
+};
+static inline EdtWs edt_layout(Carver&& c, int H, int W) {      // the one definition of the workspace
+  EdtWs w;
+  w.mask = c.take<unsigned long long>((int64_t)edt_segments(H) * W);
+  w.srow = c.take<short>((int64_t)H * W);
+  return w;
+}
+
 template <typename T>
 int edt_run(const void* image, int H, int W, int sites_nonzero, int d2max, void* ws, int* dist2, int* nearest, hipStream_t st) {
-  unsigned long long* mask = static_cast<unsigned long long*>(ws);
-  short* srow = reinterpret_cast<short*>(static_cast<char*>(ws) + edt_mask_bytes(H, W));
+  const EdtWs w = edt_layout(Carver(ws), H, W);
   const int nseg = edt_segments(H);
   const dim3 cols(ceil_div(W, CGC_BLOCK), nseg);
-  hipLaunchKernelGGL(k_edt_mask<T>, cols, dim3(CGC_BLOCK), 0, st, static_cast<const T*>(image), H, W, sites_nonzero, mask);
+  hipLaunchKernelGGL(k_edt_mask<T>, cols, dim3(CGC_BLOCK), 0, st, static_cast<const T*>(image), H, W, sites_nonzero, w.mask);
   CGC_RETURN_IF_LAUNCH_FAILED();
-  hipLaunchKernelGGL(k_edt_column, cols, dim3(CGC_BLOCK), 0, st, mask, H, W, nseg, srow);
+  hipLaunchKernelGGL(k_edt_column, cols, dim3(CGC_BLOCK), 0, st, w.mask, H, W, nseg, w.srow);
   CGC_RETURN_IF_LAUNCH_FAILED();
   const int kcap = edt_window(d2max, W);
-  hipLaunchKernelGGL(k_edt_row, dim3(H), dim3(CGC_BLOCK), (size_t)W * sizeof(short), st, srow, W, d2max, kcap, dist2, nearest);
+  hipLaunchKernelGGL(k_edt_row, dim3(H), dim3(CGC_BLOCK), (size_t)W * sizeof(short), st, w.srow, W, d2max, kcap, dist2, nearest);
   CGC_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
@@ -148,13 +157,13 @@ int edt_run(const void* image, int H, int W, int sites_nonzero, int d2max, void*
 
 extern "C" int64_t cgc_edt_ws_bytes(int H, int W) {
   if (edt_bad_dims(H, W)) return 0;
-  return edt_mask_bytes(H, W) + edt_align256((int64_t)H * W * 2);
+  return layout_bytes(edt_layout, H, W);
 }
 
 extern "C" int cgc_edt(const void* image, int elem_bytes, int H, int W, int sites_nonzero, int d2max, void* ws, int* dist2, int* nearest,
                        cgc_stream_t stream) {
   if (edt_bad_dims(H, W)) return CGC_EINVAL;
-  if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) return CGC_EINVAL;
+  if (bad_elem_bytes(elem_bytes)) return CGC_EINVAL;
   if ((int64_t)H * W == 0) return 0;
   if (image == nullptr || ws == nullptr || dist2 == nullptr) return CGC_EINVAL;
   hipStream_t st = as_stream(stream);

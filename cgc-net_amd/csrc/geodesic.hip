@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "common.hpp"
+#include "image_common.hpp"
 
 namespace {
 
@@ -40,9 +41,7 @@ constexpr int GEO_LPX = GEO_LW * GEO_LW;
 constexpr geo_key GEO_NONE = ((geo_key)CGC_GEO_INF << 32) | 0xffffffffull;
 constexpr geo_key GEO_REACHED = (geo_key)CGC_GEO_INF << 32;      // a key below this one carries a seed
 
-static inline int64_t geo_align256(int64_t b) { return (b + 255) / 256 * 256; }
 static inline int geo_tiles(int n) { return ceil_div(n, GEO_TILE); }
-static inline bool geo_bad_dims(int H, int W) { return H < 0 || W < 0 || (int64_t)H * W >= ((int64_t)1 << 31); }
 static inline bool geo_bad_steps(int H, int W, int a, int b) {       // 1 <= a <= b <= 2a or b == 0; no path cost overflows int32
   if (a < 1 || (b != 0 && (b < a || (int64_t)b > 2 * (int64_t)a))) return true;
   return (int64_t)(b != 0 ? b : a) * H * W >= ((int64_t)1 << 31);
@@ -53,12 +52,11 @@ struct GeoWs {
   unsigned char* dom;    // [H*W] 1 = in the domain
   int* stamp;            // [tiles] the last round the tile has been asked to run in
 };
-static inline GeoWs geo_carve(void* ws, int64_t npix) {
-  char* p = static_cast<char*>(ws);
+static inline GeoWs geo_layout(Carver&& c, int H, int W) {      // the one definition of the workspace
   GeoWs w;
-  w.key = reinterpret_cast<geo_key*>(p);
-  w.dom = reinterpret_cast<unsigned char*>(p + geo_align256(npix * 8));
-  w.stamp = reinterpret_cast<int*>(p + geo_align256(npix * 8) + geo_align256(npix));
+  w.key = c.take<geo_key>((int64_t)H * W);
+  w.dom = c.take<unsigned char>((int64_t)H * W);
+  w.stamp = c.take<int>((int64_t)geo_tiles(H) * geo_tiles(W));
   return w;
 }
 
@@ -195,19 +193,17 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_geo_finish(const geo_key* __restr
 }  // namespace
 
 extern "C" int64_t cgc_geodesic_ws_bytes(int H, int W) {
-  if (geo_bad_dims(H, W)) return 0;
-  const int64_t npix = (int64_t)H * W;
-  return geo_align256(npix * 8) + geo_align256(npix) + geo_align256((int64_t)geo_tiles(H) * geo_tiles(W) * 4);
+  if (bad_image_dims(H, W)) return 0;
+  return layout_bytes(geo_layout, H, W);
 }
 
 extern "C" int cgc_geodesic_begin(const void* seeds, int seed_bytes, const void* within, int within_bytes, int H, int W, int a, int b,
                                   void* ws, cgc_stream_t stream) {
-  if (geo_bad_dims(H, W) || geo_bad_steps(H, W, a, b)) return CGC_EINVAL;
-  if (seed_bytes != 1 && seed_bytes != 2 && seed_bytes != 4 && seed_bytes != 8) return CGC_EINVAL;
-  if (within != nullptr && within_bytes != 1 && within_bytes != 2 && within_bytes != 4 && within_bytes != 8) return CGC_EINVAL;
+  if (bad_image_dims(H, W) || geo_bad_steps(H, W, a, b)) return CGC_EINVAL;
+  if (bad_elem_bytes(seed_bytes) || (within != nullptr && bad_elem_bytes(within_bytes))) return CGC_EINVAL;
   if ((int64_t)H * W == 0) return 0;
   if (seeds == nullptr || ws == nullptr) return CGC_EINVAL;
-  const GeoWs w = geo_carve(ws, (int64_t)H * W);
+  const GeoWs w = geo_layout(Carver(ws), H, W);
   const int tiles_x = geo_tiles(W), tiles_y = geo_tiles(H);
   hipLaunchKernelGGL(k_geo_begin, dim3(tiles_x * tiles_y), dim3(CGC_BLOCK), 0, as_stream(stream), seeds, seed_bytes, within, within_bytes,
                      H, W, tiles_x, w.key, w.dom, w.stamp);
@@ -217,7 +213,7 @@ extern "C" int cgc_geodesic_begin(const void* seeds, int seed_bytes, const void*
 
 extern "C" int cgc_geodesic_rounds(int H, int W, int a, int b, int connectivity, int dmax, void* ws, int first_round, int rounds,
                                    int* changed, cgc_stream_t stream) {
-  if (geo_bad_dims(H, W) || geo_bad_steps(H, W, a, b)) return CGC_EINVAL;
+  if (bad_image_dims(H, W) || geo_bad_steps(H, W, a, b)) return CGC_EINVAL;
   if ((connectivity != 1 && connectivity != 2) || first_round < 0 || rounds < 1 || first_round > 0x7fffffff - rounds - 1) return CGC_EINVAL;
   if (changed == nullptr) return CGC_EINVAL;
   hipStream_t st = as_stream(stream);
@@ -227,7 +223,7 @@ extern "C" int cgc_geodesic_rounds(int H, int W, int a, int b, int connectivity,
   }
   if ((int64_t)H * W == 0) return 0;
   if (ws == nullptr) return CGC_EINVAL;
-  const GeoWs w = geo_carve(ws, (int64_t)H * W);
+  const GeoWs w = geo_layout(Carver(ws), H, W);
   const int tiles_x = geo_tiles(W), tiles_y = geo_tiles(H);
   const geo_key limit = dmax < 0 ? GEO_REACHED : ((geo_key)(unsigned)dmax + 1) << 32;
   for (int r = 0; r < rounds; ++r) {              // only the last round of the batch counts the tiles that moved
@@ -239,11 +235,11 @@ extern "C" int cgc_geodesic_rounds(int H, int W, int a, int b, int connectivity,
 }
 
 extern "C" int cgc_geodesic_finish(int H, int W, const void* ws, int* dist, int* nearest, cgc_stream_t stream) {
-  if (geo_bad_dims(H, W)) return CGC_EINVAL;
+  if (bad_image_dims(H, W)) return CGC_EINVAL;
   if ((int64_t)H * W == 0) return 0;
   if (ws == nullptr || dist == nullptr) return CGC_EINVAL;
   const int64_t npix = (int64_t)H * W;
-  const GeoWs w = geo_carve(const_cast<void*>(ws), npix);
+  const GeoWs w = geo_layout(Carver(const_cast<void*>(ws)), H, W);
   hipLaunchKernelGGL(k_geo_finish, dim3((unsigned)ceil_div64(npix, CGC_BLOCK)), dim3(CGC_BLOCK), 0, as_stream(stream), w.key, npix, dist,
                      nearest);
   CGC_RETURN_IF_LAUNCH_FAILED();

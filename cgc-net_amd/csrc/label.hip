@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "common.hpp"
+#include "image_common.hpp"
 
 namespace {
 
@@ -26,23 +27,17 @@ constexpr int LBL_TILE_PX = LBL_TILE * LBL_TILE;
 constexpr int LBL_SCAN_PX = 2048;                 // consecutive raster indices per numbering block, 8 per thread
 constexpr int LBL_PER_THREAD = LBL_SCAN_PX / CGC_BLOCK;
 
-static inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
-
 struct LabelWs {
   int* parent;     // [H*W] union-find parents, then the numbers of the roots
   int* blocks;     // [nblocks] root counts per numbering block, then their exclusive scan
   int* count;      // [H*W] pixels per root (only with counts)
 };
 static inline int64_t label_blocks(int64_t npix) { return ceil_div64(npix, LBL_SCAN_PX); }
-static inline int64_t label_ws_bytes(int64_t npix, bool counts) {
-  return align256(npix * 4) * (counts ? 2 : 1) + align256(label_blocks(npix) * 4);
-}
-static inline LabelWs label_carve(void* ws, int64_t npix) {
-  char* p = static_cast<char*>(ws);
+static inline LabelWs label_layout(Carver&& c, int64_t npix, bool counts) {     // the one definition of the workspace
   LabelWs w;
-  w.parent = reinterpret_cast<int*>(p);
-  w.blocks = reinterpret_cast<int*>(p + align256(npix * 4));
-  w.count = reinterpret_cast<int*>(p + align256(npix * 4) + align256(label_blocks(npix) * 4));
+  w.parent = c.take<int>(npix);
+  w.blocks = c.take<int>(label_blocks(npix));
+  w.count = counts ? c.take<int>(npix) : nullptr;
   return w;
 }
 
@@ -317,7 +312,7 @@ int label_run(const void* image, int H, int W, int conn8, int min_size, bool cou
     hipLaunchKernelGGL(k_label_merge<T>, dim3((int)(mb < 65536 ? mb : 65536)), dim3(CGC_BLOCK), 0, st, img, H, W, nh, nv, conn8, w.parent);
     CGC_RETURN_IF_LAUNCH_FAILED();
   }
-  int* count = counts ? w.count : nullptr;
+  int* count = w.count;                          // null without counts
   if (counts) {
     const hipError_t e = hipMemsetAsync(w.count, 0, (size_t)npix * 4, st);
     if (e != hipSuccess) return (int)e;
@@ -336,19 +331,17 @@ int label_run(const void* image, int H, int W, int conn8, int min_size, bool cou
   return 0;
 }
 
-static inline bool label_bad_dims(int H, int W) { return H < 0 || W < 0 || (int64_t)H * W >= ((int64_t)1 << 31); }
-
 }  // namespace
 
 extern "C" int64_t cgc_label_ws_bytes(int H, int W, int with_counts) {
-  if (label_bad_dims(H, W)) return 0;
-  return label_ws_bytes((int64_t)H * W, with_counts != 0);
+  if (bad_image_dims(H, W)) return 0;
+  return layout_bytes(label_layout, (int64_t)H * W, with_counts != 0);
 }
 
 extern "C" int cgc_label_components(const void* image, int pixel_bytes, int H, int W, int connectivity, int min_size, int with_counts,
                                     void* ws, int* labels, int* n_out, cgc_stream_t stream) {
-  if (label_bad_dims(H, W) || (connectivity != 1 && connectivity != 2) || min_size < 0 || n_out == nullptr) return CGC_EINVAL;
-  if (pixel_bytes != 1 && pixel_bytes != 2 && pixel_bytes != 4 && pixel_bytes != 8) return CGC_EINVAL;
+  if (bad_image_dims(H, W) || (connectivity != 1 && connectivity != 2) || min_size < 0 || n_out == nullptr) return CGC_EINVAL;
+  if (bad_elem_bytes(pixel_bytes)) return CGC_EINVAL;
   if (min_size > 1 && !with_counts) return CGC_EINVAL;
   hipStream_t st = as_stream(stream);
   const int64_t npix = (int64_t)H * W;
@@ -357,8 +350,8 @@ extern "C" int cgc_label_components(const void* image, int pixel_bytes, int H, i
     return e == hipSuccess ? 0 : (int)e;
   }
   if (image == nullptr || ws == nullptr || labels == nullptr) return CGC_EINVAL;
-  const LabelWs w = label_carve(ws, npix);
   const bool counts = with_counts != 0, all = with_counts != 0;
+  const LabelWs w = label_layout(Carver(ws), npix, counts);
   const int conn8 = connectivity == 2;
   switch (pixel_bytes) {
     case 1: return label_run<uint8_t>(image, H, W, conn8, min_size, counts, all, w, labels, n_out, st);
@@ -369,11 +362,11 @@ extern "C" int cgc_label_components(const void* image, int pixel_bytes, int H, i
 }
 
 extern "C" int cgc_label_sizes(const void* ws, int H, int W, int n, int* sizes, cgc_stream_t stream) {
-  if (label_bad_dims(H, W) || n < 0 || (int64_t)n > (int64_t)H * W) return CGC_EINVAL;
+  if (bad_image_dims(H, W) || n < 0 || (int64_t)n > (int64_t)H * W) return CGC_EINVAL;
   if (n == 0) return 0;
   if (ws == nullptr || sizes == nullptr) return CGC_EINVAL;
   const int64_t npix = (int64_t)H * W;
-  const LabelWs w = label_carve(const_cast<void*>(ws), npix);
+  const LabelWs w = label_layout(Carver(const_cast<void*>(ws)), npix, true);      // sizes come from a call that counted
   hipLaunchKernelGGL(k_label_sizes, dim3((int)ceil_div64(npix, CGC_BLOCK)), dim3(CGC_BLOCK), 0, as_stream(stream), w.parent, w.count, npix, n,
                      sizes);
   CGC_RETURN_IF_LAUNCH_FAILED();

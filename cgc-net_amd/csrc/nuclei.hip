@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "common.hpp"
+#include "image_common.hpp"
 
 #define NUC_LDS_PIXELS 2048           // crops of at most this many pixels take the LDS path (3a)
 #define NUC_LDS_SLOTS 8192            // GLCM pair hash (3a), reused afterwards for the contour vertices: = 4 * NUC_LDS_PIXELS
@@ -32,27 +33,19 @@ struct LabelTables {                   // carved out of the label-pass workspace
   int max_label;
 };
 
-__host__ __device__ inline int64_t align256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
-__host__ __device__ inline LabelTables carve(void* ws, int max_label) {
+static inline LabelTables tables_layout(Carver&& c, int max_label) {      // the one definition of the label-pass workspace
   const int64_t m = (int64_t)max_label + 1;
-  char* p = static_cast<char*>(ws);
   LabelTables t;
-  t.cnt = reinterpret_cast<int*>(p); p += align256(4 * m);
-  t.rmin = reinterpret_cast<int*>(p); p += align256(4 * m);
-  t.rmax = reinterpret_cast<int*>(p); p += align256(4 * m);
-  t.cmin = reinterpret_cast<int*>(p); p += align256(4 * m);
-  t.cmax = reinterpret_cast<int*>(p); p += align256(4 * m);
-  t.sr = reinterpret_cast<long long*>(p); p += align256(8 * m);
-  t.sc = reinterpret_cast<long long*>(p); p += align256(8 * m);
-  t.big_rows = reinterpret_cast<int*>(p);
+  t.cnt = c.take<int>(m);
+  t.rmin = c.take<int>(m);
+  t.rmax = c.take<int>(m);
+  t.cmin = c.take<int>(m);
+  t.cmax = c.take<int>(m);
+  t.sr = c.take<long long>(m);
+  t.sc = c.take<long long>(m);
+  t.big_rows = c.take<int>(m);
   t.max_label = max_label;
   return t;
-}
-
-__host__ __device__ inline int64_t tables_bytes(int max_label) {
-  const int64_t m = (int64_t)max_label + 1;
-  return 5 * align256(4 * m) + 2 * align256(8 * m) + align256(4 * m);
 }
 
 // crop of label L: rows [r0, r0 + ch), columns [c0, c0 + cw)
@@ -696,19 +689,17 @@ __global__ void k_bgr_to_gray(const uint8_t* __restrict__ bgr, int64_t npix, uin
   }
 }
 
-bool bad_dims(int H, int W) { return H < 0 || W < 0 || (int64_t)H * W > (int64_t)INT32_MAX; }
-
 }  // namespace
 
 extern "C" int cgc_nuclei_lds_max_pixels(void) { return NUC_LDS_PIXELS; }
 
-extern "C" int64_t cgc_nuclei_ws_bytes(int max_label) { return max_label < 0 ? 0 : tables_bytes(max_label); }
+extern "C" int64_t cgc_nuclei_ws_bytes(int max_label) { return max_label < 0 ? 0 : layout_bytes(tables_layout, max_label); }
 
 extern "C" int cgc_nuclei_label_pass(const int* labels, int H, int W, int max_label, int min_size, void* ws, int* kept_labels, int* meta,
                                      cgc_stream_t stream) {
-  if (bad_dims(H, W) || max_label < 0 || ws == nullptr || meta == nullptr || (max_label > 0 && kept_labels == nullptr)) return CGC_EINVAL;
+  if (bad_image_dims(H, W) || max_label < 0 || ws == nullptr || meta == nullptr || (max_label > 0 && kept_labels == nullptr)) return CGC_EINVAL;
   hipStream_t st = as_stream(stream);
-  const LabelTables t = carve(ws, max_label);
+  const LabelTables t = tables_layout(Carver(ws), max_label);
   const int64_t ib = ceil_div64((int64_t)max_label + 1, 256);
   hipLaunchKernelGGL(k_nuc_init, dim3((int)(ib < 1024 ? ib : 1024)), dim3(256), 0, st, t, meta);
   CGC_RETURN_IF_LAUNCH_FAILED();
@@ -732,11 +723,11 @@ extern "C" int64_t cgc_nuclei_big_ws_bytes(int nbig, int64_t max_big_px) {
 extern "C" int cgc_nuclei_features(const int* labels, const uint8_t* gray, int H, int W, int max_label, int min_size, const void* ws,
                                    const int* kept_labels, int n, int nbig, int64_t max_big_px, void* big_ws, float* features,
                                    float* centroids, int* info, cgc_stream_t stream) {
-  if (bad_dims(H, W) || max_label < 0 || n < 0 || nbig < 0 || nbig > n || ws == nullptr) return CGC_EINVAL;
+  if (bad_image_dims(H, W) || max_label < 0 || n < 0 || nbig < 0 || nbig > n || ws == nullptr) return CGC_EINVAL;
   if (n == 0) return 0;
   if (nbig > 0 && (big_ws == nullptr || max_big_px <= NUC_LDS_PIXELS || max_big_px > (int64_t)H * W)) return CGC_EINVAL;
   hipStream_t st = as_stream(stream);
-  const LabelTables t = carve(const_cast<void*>(ws), max_label);
+  const LabelTables t = tables_layout(Carver(const_cast<void*>(ws)), max_label);
   hipLaunchKernelGGL(k_nuc_lds, dim3(n), dim3(NUC_THREADS), 0, st, labels, gray, H, W, min_size, t, kept_labels, features, centroids, info);
   CGC_RETURN_IF_LAUNCH_FAILED();
   if (nbig > 0) {

@@ -96,8 +96,8 @@ class KernelSpec(object):
         raise NotImplementedError
 
     def label_components(self, image, connectivity, min_size, want_sizes=False):
-        """Connected components of one image (F5, in front of nucleus_features; csrc/label.hip).  image: contiguous [H, W] of a 1-, 2-, 4-
-        or 8-byte integer type or bool, H * W < 2^31.  Returns (labels int32 [H, W], n, sizes int32 [n] or None); reads n on the host,
+        """Connected components of one image (F5, in front of nucleus_features; csrc/label.hip).  image: [H, W] of a 1-, 2-, 4- or 8-byte
+        integer type or bool, any strides, H * W < 2^31.  Returns (labels int32 [H, W], n, sizes int32 [n] or None); reads n on the host,
         which is the only host read.
 
         1.  0 is background; every other value, negative ones included, is foreground.
@@ -116,7 +116,7 @@ class KernelSpec(object):
 
     def distance_transform(self, image, sites_nonzero, d2max, want_nearest=False):
         """Exact Euclidean distance transform of one image with the nearest site of every pixel (F6, beside label_components;
-        csrc/edt.hip).  image: contiguous [H, W] of a 1-, 2-, 4- or 8-byte integer type or bool, H <= 32767 and W <= 32767 (ValueError
+        csrc/edt.hip).  image: [H, W] of a 1-, 2-, 4- or 8-byte integer type or bool, any strides, H <= 32767 and W <= 32767 (ValueError
         otherwise: a squared distance must fit int32).  Returns (dist2 int32 [H, W], nearest int32 [H, W] or None); no host read.
 
         1.  A site is a pixel with value != 0 (sites_nonzero) or value == 0 (not sites_nonzero).
@@ -136,7 +136,7 @@ class KernelSpec(object):
         csrc/geodesic.hip): distance is measured along paths that stay inside a domain.  Returns (dist int32 [H, W], nearest int32
         [H, W] or None).  All arithmetic is integer: every result is exact and a pure function of the input.
 
-        1.  seeds, within: contiguous [H, W] of a 1-, 2-, 4- or 8-byte integer type or bool; only "is zero" is read.  The domain is
+        1.  seeds, within: [H, W] of a 1-, 2-, 4- or 8-byte integer type or bool, any strides; only "is zero" is read.  The domain is
             D = {within != 0} u {seeds != 0}: a seed always belongs to it.  within = None: every pixel.
         2.  An axial step between two 4-neighbours that are both in D costs a, a diagonal step between two corner neighbours that are
             both in D costs b; b == 0: no diagonal steps.  1 <= a <= b <= 2a or b == 0 (ValueError).  connectivity 2: a diagonal step
@@ -656,9 +656,15 @@ class HipKernels(KernelSpec):
                   'cgc_nuclei_features')
         return feats, cen, kept[:n], info
 
+    def _image(self, t):
+        """An image as the image kernels read it: on the current device, [H, W] of a 1-, 2-, 4- or 8-byte integer type or bool,
+        contiguous (copied if not)."""
+        self._dev(t)
+        assert t is None or (t.dim() == 2 and t.element_size() in (1, 2, 4, 8) and not t.is_floating_point())
+        return t if t is None else t.contiguous()
+
     def label_components(self, image, connectivity, min_size, want_sizes=False):
-        self._dev(image)
-        assert image.dim() == 2 and image.is_contiguous() and image.element_size() in (1, 2, 4, 8) and not image.is_floating_point()
+        image = self._image(image)
         H, W = image.shape
         dev = image.device
         i32 = dict(dtype=torch.int32, device=dev)
@@ -675,8 +681,7 @@ class HipKernels(KernelSpec):
         return labels, n, sizes
 
     def distance_transform(self, image, sites_nonzero, d2max, want_nearest=False):
-        self._dev(image)
-        assert image.dim() == 2 and image.is_contiguous() and image.element_size() in (1, 2, 4, 8) and not image.is_floating_point()
+        image = self._image(image)
         H, W = image.shape
         if H > EDT_MAX_SIDE or W > EDT_MAX_SIDE:
             raise ValueError('distance_transform takes images of at most %d x %d pixels (got %d x %d)' % (EDT_MAX_SIDE, EDT_MAX_SIDE, H, W))
@@ -691,9 +696,6 @@ class HipKernels(KernelSpec):
         return dist2, nearest
 
     def geodesic_transform(self, seeds, within, a, b, connectivity, dmax, want_nearest=False):
-        self._dev(seeds, within)
-        for t in (seeds, within):
-            assert t is None or (t.dim() == 2 and t.is_contiguous() and t.element_size() in (1, 2, 4, 8) and not t.is_floating_point())
         assert within is None or within.shape == seeds.shape
         H, W = seeds.shape
         a, b = int(a), int(b)
@@ -703,6 +705,7 @@ class HipKernels(KernelSpec):
             raise ValueError('connectivity must be 1 or 2, got %r' % (connectivity,))
         if (b or a) * H * W >= 2 ** 31:
             raise ValueError('geodesic_transform: %d * %d * %d reaches 2^31: a path cost must fit int32' % (b or a, H, W))
+        seeds, within = self._image(seeds), self._image(within)      # after the refusals: may copy
         dev = seeds.device
         i32 = dict(dtype=torch.int32, device=dev)
         dist = torch.empty(H, W, **i32)

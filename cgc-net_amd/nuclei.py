@@ -39,6 +39,38 @@ GEO_INF = kernels.GEO_INF          # geodesic dist of a pixel that no seed reach
 GEODESIC_STEPS = {'cityblock': (1, 0), 'chessboard': (1, 1), 'chamfer': (5, 7)}      # (axial, diagonal) step costs; 0: no such step
 
 
+def _check_image(fn, name, image, dtypes=(torch.bool,) + _INT_DTYPES, on_gpu=True):
+    """The form of every image argument: a 2-D bool / integer tensor on the GPU of fewer than 2^31 pixels.  (nucleus_features takes
+    no bool labels, and finds a tensor on the host at its launch: what it refuses before that, it refuses without a GPU.)"""
+    if not torch.is_tensor(image) or (on_gpu and not image.is_cuda):
+        raise TypeError('%s takes torch tensors on the GPU (%s)' % (fn, name))
+    if image.dtype not in dtypes:
+        raise TypeError('%s: %s must be %s integer image, got %s' % (fn, name, 'a bool or' if torch.bool in dtypes else 'an', image.dtype))
+    if image.dim() != 2:
+        raise ValueError('%s: %s must be 2-D (got %s)' % (fn, name, tuple(image.shape)))
+    if image.shape[0] * image.shape[1] >= 2 ** 31:
+        raise ValueError('%s: images of 2^31 pixels or more are not supported (%d x %d)' % ((fn,) + tuple(image.shape)))
+
+
+def _check_within(fn, within, image):
+    if within is None:
+        return
+    _check_image(fn, 'within', within)
+    if tuple(within.shape) != tuple(image.shape) or within.device != image.device:
+        raise ValueError('%s: within must have the shape and device of the image (got %s on %s and %s on %s)'
+                         % (fn, tuple(within.shape), within.device, tuple(image.shape), image.device))
+
+
+def _check_connectivity(connectivity):
+    if connectivity not in (1, 2):
+        raise ValueError('connectivity must be 1 (4 neighbours) or 2 (8 neighbours), got %r' % (connectivity,))
+
+
+def _check_min_size(min_size):
+    if min_size < 0:
+        raise ValueError('min_size must not be negative (got %r)' % (min_size,))
+
+
 def label_instances(image, connectivity=1, min_size=0, return_sizes=False):
     """image: 2-D bool / uint8 / int8 / int16 / int32 / int64 tensor on the GPU, any strides; 0 = background, every other value
     (negative ones too) foreground.  Returns (labels int32 [H, W], n) and, with ``return_sizes``, int32 [n] pixel counts (sizes[k - 1]
@@ -48,55 +80,39 @@ def label_instances(image, connectivity=1, min_size=0, return_sizes=False):
     ``min_size`` > 0 components of fewer pixels become background and take no number (skimage's remove_small_objects, then labelling).
 
     Host syncs: one, the read of n."""
-    if not torch.is_tensor(image) or not image.is_cuda:
-        raise TypeError('label_instances takes a torch tensor on the GPU')
-    if image.dtype != torch.bool and image.dtype not in _INT_DTYPES:
-        raise TypeError('image must be a bool or integer image, got %s' % image.dtype)
-    if image.dim() != 2:
-        raise ValueError('image must be 2-D (got %s)' % (tuple(image.shape),))
-    if connectivity not in (1, 2):
-        raise ValueError('connectivity must be 1 (4 neighbours) or 2 (8 neighbours), got %r' % (connectivity,))
-    if min_size < 0:
-        raise ValueError('min_size must not be negative (got %r)' % (min_size,))
+    _check_image('label_instances', 'image', image)
+    _check_connectivity(connectivity)
+    _check_min_size(min_size)
     H, W = image.shape
-    if H * W >= 2 ** 31:
-        raise ValueError('images of 2^31 pixels or more are not supported (%d x %d)' % (H, W))
     if H * W == 0:
         labels, n = torch.zeros(H, W, dtype=torch.int32, device=image.device), 0
         sizes = torch.zeros(0, dtype=torch.int32, device=image.device)
     else:
         with torch.cuda.device(image.device):
-            labels, n, sizes = kernels.get().label_components(image.contiguous(), int(connectivity), int(min_size), bool(return_sizes))
+            labels, n, sizes = kernels.get().label_components(image, int(connectivity), int(min_size), bool(return_sizes))
     return (labels, n, sizes) if return_sizes else (labels, n)
 
 
-def _check_image(fn, name, image, max_side=True):
-    if not torch.is_tensor(image) or not image.is_cuda:
-        raise TypeError('%s takes torch tensors on the GPU' % fn)
-    if image.dtype != torch.bool and image.dtype not in _INT_DTYPES:
-        raise TypeError('%s must be a bool or integer image, got %s' % (name, image.dtype))
-    if image.dim() != 2:
-        raise ValueError('%s must be 2-D (got %s)' % (name, tuple(image.shape)))
-    H, W = image.shape
-    if max_side and (H > kernels.EDT_MAX_SIDE or W > kernels.EDT_MAX_SIDE):
-        raise ValueError('%s: sides over %d pixels are not supported (%d x %d): a squared distance must fit int32'
-                         % (fn, kernels.EDT_MAX_SIDE, H, W))
+def _bound(distance, name, guess, value, cap):
+    """The largest integer k with value(k) <= distance, for an increasing ``value``, capped at ``cap``.  guess(distance) is the
+    inverse of ``value`` in floating point: int(guess) can be off by one in either direction, so its neighbours are checked."""
+    d = float(distance)
+    if not d >= 0:
+        raise ValueError('%s must be a number >= 0 (got %r)' % (name, distance))
+    if guess(d) >= cap + 1:
+        return cap
+    k = int(guess(d))
+    while value(k + 1) <= d:
+        k += 1
+    while k > 0 and value(k) > d:
+        k -= 1
+    return k
 
 
 def _d2max(distance, name):
     """The largest integer k with sqrt(k) <= distance (float64 sqrt, which is correctly rounded), capped at EDT_INF - 1, which no
-    squared distance of a supported image exceeds.  int(d * d) alone can be off by one in either direction: its neighbours are checked."""
-    d = float(distance)
-    if not d >= 0:
-        raise ValueError('%s must be a number >= 0 (got %r)' % (name, distance))
-    if d * d >= EDT_INF:
-        return EDT_INF - 1
-    k = int(d * d)
-    while math.sqrt(k + 1) <= d:
-        k += 1
-    while k > 0 and math.sqrt(k) > d:
-        k -= 1
-    return k
+    squared distance of a supported image exceeds."""
+    return _bound(distance, name, lambda d: d * d, math.sqrt, EDT_INF - 1)
 
 
 def distance_transform(image, sites='zero', max_distance=None, return_nearest=False):
@@ -115,16 +131,9 @@ def distance_transform(image, sites='zero', max_distance=None, return_nearest=Fa
     if sites not in ('zero', 'nonzero'):
         raise ValueError("sites must be 'zero' or 'nonzero', got %r" % (sites,))
     d2max = -1 if max_distance is None else _d2max(max_distance, 'max_distance')
-    with torch.cuda.device(image.device):
-        dist2, nearest = kernels.get().distance_transform(image.contiguous(), sites == 'nonzero', d2max, bool(return_nearest))
+    with torch.cuda.device(image.device):      # the kernel table refuses sides over EDT_MAX_SIDE
+        dist2, nearest = kernels.get().distance_transform(image, sites == 'nonzero', d2max, bool(return_nearest))
     return (dist2, nearest) if return_nearest else dist2
-
-
-def _check_within(fn, within, image):
-    _check_image(fn, 'within', within, max_side=False)
-    if tuple(within.shape) != tuple(image.shape) or within.device != image.device:
-        raise ValueError('within must have the shape and device of the image (got %s on %s and %s on %s)'
-                         % (tuple(within.shape), within.device, tuple(image.shape), image.device))
 
 
 def _geodesic_steps(metric):
@@ -146,35 +155,15 @@ def _geodesic_steps(metric):
 
 def _geodesic_bound(distance, a, name):
     """The largest integer k with k / a <= distance (a distance in pixels -> a bound in raw cost units), capped at GEO_INF - 1, which no
-    path cost of a supported image exceeds.  int(d * a) alone can be off by one in either direction: its neighbours are checked."""
-    d = float(distance)
-    if not d >= 0:
-        raise ValueError('%s must be a number >= 0 (got %r)' % (name, distance))
-    if d * a >= GEO_INF:
-        return GEO_INF - 1
-    k = int(d * a)
-    while (k + 1) / a <= d:
-        k += 1
-    while k > 0 and k / a > d:
-        k -= 1
-    return k
+    path cost of a supported image exceeds."""
+    return _bound(distance, name, lambda d: d * a, lambda k: k / a, GEO_INF - 1)
 
 
-def _geodesic(fn, seeds, within, metric, connectivity, distance, name, want_nearest):
-    _check_image(fn, 'seeds' if fn == 'geodesic_distance_transform' else 'labels', seeds, max_side=False)
-    if within is not None:
-        _check_within(fn, within, seeds)
+def _geodesic(seeds, within, metric, connectivity, distance, name, want_nearest):
     a, b = _geodesic_steps(metric)
-    if connectivity not in (1, 2):
-        raise ValueError('connectivity must be 1 (4 neighbours) or 2 (8 neighbours), got %r' % (connectivity,))
     dmax = -1 if distance is None else _geodesic_bound(distance, a, name)
-    H, W = seeds.shape
-    if (b or a) * H * W >= 2 ** 31:
-        raise ValueError('%s: images of %d x %d pixels are not supported with step costs (%d, %d): a path cost must fit int32'
-                         % (fn, H, W, a, b))
-    with torch.cuda.device(seeds.device):
-        return kernels.get().geodesic_transform(seeds.contiguous(), None if within is None else within.contiguous(), a, b,
-                                                int(connectivity), dmax, bool(want_nearest))
+    with torch.cuda.device(seeds.device):      # the kernel table refuses a bad connectivity and path costs that overflow int32
+        return kernels.get().geodesic_transform(seeds, within, a, b, connectivity, dmax, bool(want_nearest))
 
 
 def geodesic_distance_transform(seeds, within=None, metric='chamfer', connectivity=1, max_distance=None, return_nearest=False):
@@ -194,8 +183,9 @@ def geodesic_distance_transform(seeds, within=None, metric='chamfer', connectivi
     growth crosses at most six edges of the 64 x 64 tiles (any bound of a few pixels), three for 56 rounds.  The number of rounds
     is 2 + the tile edges crossed by the longest shortest path: a serpentine corridor over a whole image is the case to avoid or to
     bound (kernels.KernelSpec.geodesic_transform)."""
-    dist, nearest = _geodesic('geodesic_distance_transform', seeds, within, metric, connectivity, max_distance, 'max_distance',
-                              return_nearest)
+    _check_image('geodesic_distance_transform', 'seeds', seeds)
+    _check_within('geodesic_distance_transform', within, seeds)
+    dist, nearest = _geodesic(seeds, within, metric, connectivity, max_distance, 'max_distance', return_nearest)
     return (dist, nearest) if return_nearest else dist
 
 
@@ -214,29 +204,21 @@ def expand_labels(labels, distance, within=None, geodesic=False, metric='chamfer
     crosses a gap of ``within``.  ``distance=None`` (only then) means unbounded: every domain pixel joined to a label is filled.
 
     Host syncs: none; with ``geodesic=True`` those of geodesic_distance_transform (one for a bound of a few pixels)."""
-    if geodesic:
-        _, nearest = _geodesic('expand_labels', labels, within, metric, connectivity, distance, 'distance', True)
-        if labels.numel() == 0:
-            return labels.clone()
-        # a labelled pixel is its own nearest seed; nearest = -1: outside the domain, not joined to a label or beyond the bound
-        src = labels.reshape(-1)[nearest.clamp(min=0).reshape(-1).long()].reshape(labels.shape)
-        return torch.where(nearest >= 0, src, labels)
-    if distance is None:
-        raise ValueError('distance=None (unbounded growth) needs geodesic=True')
     _check_image('expand_labels', 'labels', labels)
-    d2max = _d2max(distance, 'distance')
-    if within is not None:
-        _check_image('expand_labels', 'within', within)
-        if tuple(within.shape) != tuple(labels.shape) or within.device != labels.device:
-            raise ValueError('within must have the shape and device of labels (got %s and %s)' % (tuple(within.shape), tuple(labels.shape)))
-    if labels.numel() == 0:
-        return labels.clone()
-    with torch.cuda.device(labels.device):
-        _, nearest = kernels.get().distance_transform(labels.contiguous(), True, d2max, True)
-    # a labelled pixel is its own nearest site, so the gather returns it unchanged; nearest = -1: nothing within reach
-    fill = nearest >= 0
-    if within is not None:
-        fill &= (labels != 0) | (within != 0)
+    _check_within('expand_labels', within, labels)
+    if geodesic:
+        _, nearest = _geodesic(labels, within, metric, connectivity, distance, 'distance', True)
+        fill = nearest >= 0                     # -1: outside the domain, not joined to a label or beyond the bound
+    else:
+        if distance is None:
+            raise ValueError('distance=None (unbounded growth) needs geodesic=True')
+        d2max = _d2max(distance, 'distance')
+        with torch.cuda.device(labels.device):
+            _, nearest = kernels.get().distance_transform(labels, True, d2max, True)
+        fill = nearest >= 0                     # -1: nothing within reach
+        if within is not None:
+            fill &= (labels != 0) | (within != 0)
+    # a labelled pixel is its own nearest site, so the gather returns it unchanged
     src = labels.reshape(-1)[nearest.clamp_(min=0).reshape(-1).long()].reshape(labels.shape)
     return torch.where(fill, src, labels)
 
@@ -268,13 +250,9 @@ def split_touching(mask, core_radius, connectivity=1, min_size=0, growth='euclid
     if growth not in ('euclidean', 'geodesic'):
         raise ValueError("growth must be 'euclidean' or 'geodesic', got %r" % (growth,))
     radius2 = _d2max(core_radius, 'core_radius')
-    if connectivity not in (1, 2):
-        raise ValueError('connectivity must be 1 (4 neighbours) or 2 (8 neighbours), got %r' % (connectivity,))
-    if min_size < 0:
-        raise ValueError('min_size must not be negative (got %r)' % (min_size,))
-    if mask.numel() == 0:
-        return torch.zeros(tuple(mask.shape), dtype=torch.int32, device=mask.device), 0
-    fg = mask != 0
+    _check_connectivity(connectivity)
+    _check_min_size(min_size)
+    fg = mask != 0                          # an empty image goes through every step as an empty tensor, without a host read
     dist2 = distance_transform(fg)
     cores, k = label_instances(dist2 > radius2, connectivity)
     if growth == 'geodesic':
@@ -295,18 +273,15 @@ def nucleus_features(labels, gray, min_size=10, return_info=False, max_label=Non
     Host syncs: one read of the label range (negative labels raise ValueError; the tables are indexed by label value, so very sparse
     label ids cost memory in proportion to the largest) and one read of the row count.  ``max_label`` (an int >= the largest label,
     e.g. the n of ``label_instances``) replaces the read of the label range; pixels outside [0, max_label] then raise ValueError."""
-    if not (torch.is_tensor(labels) and torch.is_tensor(gray)):
-        raise TypeError('nucleus_features takes torch tensors on the GPU')
-    if labels.dim() != 2 or tuple(gray.shape) != tuple(labels.shape):
+    _check_image('nucleus_features', 'labels', labels, _INT_DTYPES, on_gpu=False)
+    if not torch.is_tensor(gray):
+        raise TypeError('nucleus_features takes torch tensors on the GPU (gray)')
+    if tuple(gray.shape) != tuple(labels.shape):
         raise ValueError('labels and gray must be 2-D images of the same size (got %s and %s)'
                          % (tuple(labels.shape), tuple(gray.shape)))
-    if labels.dtype not in _INT_DTYPES:
-        raise TypeError('labels must be an integer image, got %s' % labels.dtype)
     if gray.dtype != torch.uint8:
         raise TypeError('gray must be uint8, got %s' % gray.dtype)
     H, W = labels.shape
-    if H * W >= 2 ** 31:
-        raise ValueError('images of 2^31 pixels or more are not supported (%d x %d)' % (H, W))
     dev = labels.device
     if max_label is not None:
         lo, hi = 0, int(max_label)

@@ -14,17 +14,13 @@ import cgc_net_amd  # noqa: F401
 from cgc_net_amd import nuclei
 
 import edt_ref as ref
+from image_cases import DEV, gpu, tissue, two_discs
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device('cuda:0')
 
 SHAPES = [(1, 1), (1, 37), (41, 1), (7, 5), (31, 33), (64, 64), (65, 63), (64, 65), (7, 293), (129, 257), (300, 300), (3, 2100), (2100, 3),
           (63, 9), (127, 3), (128, 3), (5, 255), (5, 256), (5, 257)]
 DENSITIES = [0.0, 0.001, 0.02, 0.3, 0.9, 1.0]
-
-
-def gpu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def run(image, **kw):
@@ -170,13 +166,6 @@ def test_empty_images():
 
 
 # ------------------------------------------------------------------ expand_labels
-@functools.lru_cache(maxsize=None)
-def tissue():
-    labels, gray = nuclei.synthetic_tissue(300, 300, 60)
-    within = np.random.RandomState(31).rand(300, 300) < 0.7
-    return labels, gray, within
-
-
 @pytest.mark.parametrize('distance', [0, 1, 2.5, 6])
 def test_expand_labels_tissue(distance):
     labels, _, within = tissue()
@@ -223,11 +212,6 @@ def test_expand_labels_facing_labels(gap):
 
 
 # ------------------------------------------------------------------ split_touching
-def two_discs():
-    yy, xx = np.mgrid[0:48, 0:48]
-    return ((yy - 24) ** 2 + (xx - 17) ** 2 <= 100) | ((yy - 24) ** 2 + (xx - 31) ** 2 <= 100)
-
-
 def test_split_two_discs():
     m = two_discs()
     t = gpu(m)

@@ -16,17 +16,12 @@ from cgc_net_amd import kernels, nuclei
 
 import edt_ref
 import geodesic_ref as ref
+from image_cases import DEV, DTYPES, gpu, tissue, two_discs
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device('cuda:0')
 
 SHAPES = [(1, 1), (1, 37), (41, 1), (7, 5), (63, 9), (64, 64), (65, 63), (64, 65), (5, 129), (129, 5), (130, 131), (200, 70)]
 METRICS = [(5, 7), (1, 0), (1, 1), (3, 4)]
-DTYPES = [torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64]
-
-
-def gpu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def run(seeds, within=None, **kw):
@@ -217,13 +212,6 @@ def test_empty_images():
 
 
 # ------------------------------------------------------------------ expand_labels(geodesic=True)
-@functools.lru_cache(maxsize=None)
-def tissue():
-    labels, gray = nuclei.synthetic_tissue(300, 300, 60)
-    within = np.random.RandomState(31).rand(300, 300) < 0.7
-    return labels, gray, within
-
-
 @pytest.mark.parametrize('distance', [1, 2.5, 6, None])
 def test_expand_labels_geodesic_tissue(distance):
     labels, _, within = tissue()
@@ -260,11 +248,6 @@ def test_expand_labels_through_the_opening_of_a_wall():
 
 
 # ------------------------------------------------------------------ split_touching(growth='geodesic')
-def two_discs():
-    yy, xx = np.mgrid[0:48, 0:48]
-    return ((yy - 24) ** 2 + (xx - 17) ** 2 <= 100) | ((yy - 24) ** 2 + (xx - 31) ** 2 <= 100)
-
-
 @pytest.mark.parametrize('core_radius,connectivity,min_size', [(2, 1, 0), (3, 1, 0), (4, 1, 10), (2.5, 2, 10)])
 def test_split_geodesic_tissue(core_radius, connectivity, min_size):
     labels, _, _ = tissue()
