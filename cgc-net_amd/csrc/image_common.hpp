@@ -1,4 +1,4 @@
-// Host-side helpers of the image stage (nuclei.hip, label.hip, edt.hip, geodesic.hip): the argument rules the four files share and the
+// Host-side helpers of the image stage (nuclei.hip, label.hip, edt.hip, geodesic.hip, reconstruct.hip): the argument rules these files share and the
 // carver that lays out their workspaces.  Each stage has ONE layout function that uses up a Carver and fills the stage's pointer struct;
 // its *_ws_bytes entry point runs that function on a counting carver (layout_bytes) and its launchers run it on the caller's buffer,
 // so a size and the offsets behind it cannot drift apart.

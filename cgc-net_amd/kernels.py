@@ -161,6 +161,33 @@ class KernelSpec(object):
         Worst case: a serpentine corridor over a whole image crosses a tile edge per turn and needs hundreds of rounds."""
         raise NotImplementedError
 
+    def morph_reconstruct(self, marker, mask, connectivity, by_erosion=False):
+        """Grayscale morphological reconstruction (Vincent 1993) of one image (F8, beside geodesic_transform; csrc/reconstruct.hip).
+        Returns R int32 [H, W], contiguous.  All arithmetic is integer comparison: every result is exact and a pure function of the
+        input.
+
+        1.  marker, mask: int32 [H, W] of the same shape, any strides, H * W < 2^31; the whole int32 range is allowed.
+        2.  connectivity 1: the neighbours of a pixel are its 4 edge neighbours; 2: its 8 neighbours (ValueError otherwise).  With
+            connectivity 1 a diagonal corner contact does not conduct, with connectivity 2 it does.
+        3.  By dilation: R0 = min(marker, mask) pointwise -- a marker above the mask is clamped, not refused, so nothing is read on
+            the host -- and R is the fixed point of R[p] = min(mask[p], max(R[p], max over the neighbours q of R[q])) that is reached
+            from R0 by raising values.
+        4.  Equivalently R[p] = the largest, over pixels q and over paths of neighbours from q to p (q = p included), of
+            min(R0[q], the smallest mask value on the path).  It is unique; R0 <= R <= mask.
+        5.  by_erosion: the dual (min and max exchanged), computed as R = ~dilation(~marker, ~mask) with BITWISE NOT, which reverses
+            the order of all of int32 and cannot overflow (negation can); mask <= R <= max(marker, mask).
+        6.  H * W = 0 gives an empty output.
+        Why a parallel relaxation gives exactly this: values only increase, and every stored value is the value of a real path (item
+        4), whatever the order of the updates.  Rounds are launches (one 64 x 64 tile per workgroup, relaxed to its own fixed point
+        in LDS by forward and backward scans along rows, then columns; a tile that already equals its mask costs one load, a tile
+        whose values and halo did not move since its last run nothing), and the loop is here, on geodesic_transform's schedule: the
+        host reads the number of tiles that moved in the last round of a batch of GEO_FIRST_BATCH (8), then twice as many up to
+        GEO_MAX_BATCH (64), rounds.  Host reads: one per batch.  R = 2 + the tile edges crossed by the longest path along which a
+        value has to travel rounds are needed (the last one moves nothing).  Worst case: a serpentine plateau over a whole image
+        crosses a tile edge per turn and needs hundreds of rounds.  ``reconstruct_rounds`` holds the rounds launched by the last
+        call."""
+        raise NotImplementedError
+
     def bgr_to_gray(self, bgr):
         """cv2.cvtColor(img, COLOR_BGR2GRAY) on uint8 [H, W, 3]: (1868 B + 9617 G + 4899 R + 8192) >> 14 -> uint8 [H, W]."""
         raise NotImplementedError
@@ -728,6 +755,34 @@ class HipKernels(KernelSpec):
         self.geodesic_rounds = done                     # rounds launched by the last call (tests, tools)
         self._chk(self.lib.cgc_geodesic_finish(H, W, _ptr(ws), _ptr(dist), _ptr(nearest), st), 'cgc_geodesic_finish')
         return dist, nearest
+
+    def morph_reconstruct(self, marker, mask, connectivity, by_erosion=False):
+        assert marker.dtype == torch.int32 and mask.dtype == torch.int32 and marker.shape == mask.shape
+        if connectivity not in (1, 2):
+            raise ValueError('connectivity must be 1 or 2, got %r' % (connectivity,))
+        marker, mask = self._image(marker), self._image(mask)      # after the refusal: may copy
+        H, W = marker.shape
+        dev = marker.device
+        out = torch.empty(H, W, dtype=torch.int32, device=dev)
+        self.reconstruct_rounds = 0                     # rounds launched by the last call (tests, tools)
+        if H * W == 0:
+            return out
+        ws = torch.empty(int(self.lib.cgc_reconstruct_ws_bytes(H, W)), dtype=torch.uint8, device=dev)
+        changed = torch.empty(1, dtype=torch.int32, device=dev)
+        st = self._stream()
+        self._chk(self.lib.cgc_reconstruct_begin(_ptr(marker), _ptr(mask), H, W, int(bool(by_erosion)), _ptr(ws), st),
+                  'cgc_reconstruct_begin')
+        done, batch = 0, GEO_FIRST_BATCH
+        while True:
+            self._chk(self.lib.cgc_reconstruct_rounds(H, W, int(connectivity), _ptr(ws), done, batch, _ptr(changed), st),
+                      'cgc_reconstruct_rounds')
+            done += batch
+            if int(changed.item()) == 0:                # the host sync of this stage, once per batch: did the last round move a value?
+                break
+            batch = min(2 * batch, GEO_MAX_BATCH)
+        self.reconstruct_rounds = done
+        self._chk(self.lib.cgc_reconstruct_finish(H, W, int(bool(by_erosion)), _ptr(ws), _ptr(out), st), 'cgc_reconstruct_finish')
+        return out
 
     def bgr_to_gray(self, bgr):
         self._dev(bgr)

@@ -13,6 +13,11 @@ along paths that stay inside a mask instead (csrc/geodesic.hip; kernels.KernelSp
 geodesic=True)`` grows labels along such paths, so that no label reaches across a gap, and ``split_touching(..., growth='geodesic')``
 gives every mask pixel that is connected to a core the geodesically nearest core.
 
+``reconstruct`` is grayscale morphological reconstruction (csrc/reconstruct.hip; kernels.KernelSpec.morph_reconstruct), and
+``h_maxima``, ``regional_maxima`` and ``fill_holes`` stand on it: ``fill_holes`` closes the holes of a binary or an instance mask
+before the features are taken, and ``split_touching(..., markers='h_maxima', h=...)`` takes as cores the maxima of the distance map
+whose dynamic is at least ``h``, which finds one core per nucleus whatever its size.
+
 ``nucleus_features(labels, gray)`` returns the reference's ``feature`` / ``coordinate`` arrays of one image (csrc/nuclei.hip; the
 arithmetic item by item: kernels.KernelSpec.nucleus_features), ``graph_item`` turns them into the ``Data`` that
 ``_read_one_raw_graph`` builds, and ``save_reference_files`` writes them where the reference's dataset preparation reads them.
@@ -23,6 +28,7 @@ Differences from the reference, all stated: an image without a surviving nucleus
 documented behaviour, not linked: see DESIGN.md, "Nucleus features".
 """
 import math
+import operator
 import os
 
 import numpy as np
@@ -34,6 +40,8 @@ NUM_FEATURES = 16
 FEATURE_NAMES = ('mean_im_out', 'diff', 'var_im', 'skew_im', 'mean_ent', 'glcm_dissimilarity', 'glcm_homogeneity', 'glcm_energy',
                  'glcm_ASM', 'eccentricity', 'area', 'majoraxis_length', 'minoraxis_length', 'perimeter', 'solidity', 'orientation')
 _INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+_INT32_DTYPES = (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32)      # reconstruction: values must fit int32
+INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
 EDT_INF = kernels.EDT_INF          # dist2 of a pixel that has no site (within max_distance)
 GEO_INF = kernels.GEO_INF          # geodesic dist of a pixel that no seed reaches (within max_distance)
 GEODESIC_STEPS = {'cityblock': (1, 0), 'chessboard': (1, 1), 'chamfer': (5, 7)}      # (axial, diagonal) step costs; 0: no such step
@@ -223,7 +231,116 @@ def expand_labels(labels, distance, within=None, geodesic=False, metric='chamfer
     return torch.where(fill, src, labels)
 
 
-def split_touching(mask, core_radius, connectivity=1, min_size=0, growth='euclidean'):
+def reconstruct(marker, mask, method='dilation', connectivity=1):
+    """Grayscale morphological reconstruction (Vincent 1993).  marker, mask: 2-D bool / uint8 / int8 / int16 / int32 tensors on the
+    same GPU, of the same shape, any strides (int64 is a TypeError: values must fit int32, and checking that would cost a host read).
+    Returns the reconstruction in the marker's dtype, contiguous; bool counts as 0 / 1.
+
+    ``method='dilation'``: R0 = min(marker, mask) pointwise (a marker above the mask is clamped, not refused) and R is the fixed
+    point of R[p] = min(mask[p], max(R[p], max over the neighbours q of R[q])): R[p] is the largest, over pixels q and paths of
+    neighbours from q to p, of min(R0[q], the smallest mask value on the path) -- the marker's peaks spread under the mask as far as
+    the mask lets them.  ``connectivity`` 1: 4 neighbours, a diagonal corner contact does not conduct; 2: 8 neighbours, it does.
+    ``method='erosion'``: the dual (min and max exchanged; a marker below the mask is raised to it), computed as
+    ~dilation(~marker, ~mask) with bitwise NOT, which reverses order on all of int32 and cannot overflow.
+    The computation is in int32 and exact (kernels.KernelSpec.morph_reconstruct); the result lies between min(marker, mask) and mask
+    (dilation), so it fits the marker's dtype whenever the mask's values do.
+
+    Host syncs: one per batch of relaxation rounds (8, then 16, 32, then 64 rounds each) until a round moves nothing; the number of
+    rounds is 2 + the 64 x 64 tile edges crossed by the longest path along which a value has to travel.  A serpentine plateau over
+    a whole image is the case to avoid."""
+    _check_image('reconstruct', 'marker', marker, _INT32_DTYPES)
+    _check_image('reconstruct', 'mask', mask, _INT32_DTYPES)
+    if tuple(marker.shape) != tuple(mask.shape) or marker.device != mask.device:
+        raise ValueError('reconstruct: marker and mask must have the same shape and device (got %s on %s and %s on %s)'
+                         % (tuple(marker.shape), marker.device, tuple(mask.shape), mask.device))
+    if method not in ('dilation', 'erosion'):
+        raise ValueError("method must be 'dilation' or 'erosion', got %r" % (method,))
+    _check_connectivity(connectivity)
+    with torch.cuda.device(marker.device):
+        out = kernels.get().morph_reconstruct(marker.to(torch.int32), mask.to(torch.int32), int(connectivity), method == 'erosion')
+    return out != 0 if marker.dtype == torch.bool else out.to(marker.dtype)
+
+
+def _check_h(h):
+    try:
+        h = operator.index(h)
+    except TypeError:
+        raise TypeError('h must be an integer (got %r)' % (h,))
+    if not 1 <= h <= INT32_MAX:
+        raise ValueError('h must lie in [1, 2^31 - 1] (got %d)' % h)
+    return h
+
+
+def h_maxima(image, h, connectivity=1):
+    """The h-maxima markers of an image.  image: 2-D bool / uint8 / int8 / int16 / int32 tensor on the GPU, any strides; ``h``: an
+    integer, 1 <= h <= 2^31 - 1.  Returns the bool map (image - reconstruct(image - h, image)) >= h, where image - h saturates at the
+    int32 minimum: True exactly on the summit plateaus of those regional maxima whose dynamic -- the height of the summit above the
+    highest saddle on a path to any higher pixel -- is at least ``h``.  A maximum that a saddle shallower than ``h`` joins to a higher
+    one is not marked.  The highest summit has no higher pixel, so its dynamic is unbounded and it is marked for every ``h`` (where
+    skimage's h_maxima returns nothing once ``h`` exceeds max - min) -- except where image - h saturates: a pixel less than ``h``
+    above the int32 minimum is never marked, so an ``h`` larger than the room between the image and the int32 minimum gives all
+    False.
+
+    Host syncs: those of reconstruct."""
+    _check_image('h_maxima', 'image', image, _INT32_DTYPES)
+    h = _check_h(h)
+    _check_connectivity(connectivity)
+    wide = image.to(torch.int64)
+    mask = wide.to(torch.int32)
+    marker = (wide - h).clamp_(min=INT32_MIN).to(torch.int32)
+    with torch.cuda.device(image.device):
+        rec = kernels.get().morph_reconstruct(marker, mask, int(connectivity), False)
+    return (wide - rec) >= h
+
+
+def regional_maxima(image, connectivity=1):
+    """The regional maxima of an image (arguments as h_maxima): True on every ``connectivity``-connected plateau of equal values that
+    has no higher neighbour.  It is h_maxima(image, 1, connectivity).
+
+    Host syncs: those of reconstruct."""
+    return h_maxima(image, 1, connectivity)
+
+
+def fill_holes(image, connectivity=1):
+    """Fill the holes of a mask.  image: 2-D bool / uint8 / int8 / int16 / int32 tensor on the GPU, any strides.  A hole is a
+    ``connectivity``-component (1: 4 neighbours, 2: 8) of the background {image == 0} that does not touch the image border.  Returns
+    a tensor of the input's dtype.
+      bool image: the holes become True; with connectivity 1 this is scipy.ndimage.binary_fill_holes, bit for bit.  One reconstruction
+        of the marker (background on the border) under the mask (background): what it does not reach are the holes.
+      integer image (an instance mask): every hole pixel takes the value of the geodesically nearest labelled pixel along paths
+        inside the hole -- expand_labels(image, None, within=holes, geodesic=True, connectivity=connectivity): a ring of one label
+        closes with that label, a hole bordered by two labels is shared between them (ties: expand_labels' rule).
+    Labelled pixels and the background outside the holes never change.
+
+    Host syncs: those of reconstruct -- the flood starts at the four borders and meets in the middle, so about max(H, W) / 128 rounds
+    when the open background is one sheet (three reads for 3584 x 3584), more where it winds -- plus, for an integer image, those of geodesic_distance_transform (one for holes narrower than
+    a few tiles)."""
+    _check_image('fill_holes', 'image', image, _INT32_DTYPES)
+    _check_connectivity(connectivity)
+    H, W = image.shape
+    if H * W == 0:
+        return image.clone()
+    background = image == 0
+    border = torch.zeros_like(background)
+    border[0, :] = border[-1, :] = border[:, 0] = border[:, -1] = True
+    outside = reconstruct(background & border, background, 'dilation', connectivity)
+    holes = background & ~outside
+    if image.dtype == torch.bool:
+        return image | holes
+    return expand_labels(image, None, within=holes, geodesic=True, connectivity=connectivity)
+
+
+def _eighths(dist2):
+    """T (int32): the largest integer with T^2 <= 64 dist2 -- the distance in eighths of a pixel, defined in integers: float64 sqrt
+    (64 dist2 < 2^37 is exact in float64, the root is off by at most one), then corrected by +-1 in integer arithmetic."""
+    v = dist2.to(torch.int64) * 64
+    t = v.to(torch.float64).sqrt_().to(torch.int64)
+    t -= (t * t > v).to(torch.int64)
+    t += ((t + 1) * (t + 1) <= v).to(torch.int64)
+    return t.to(torch.int32)
+
+
+def split_touching(mask, core_radius, connectivity=1, min_size=0, growth='euclidean', markers='core', h=None):
     """The erode-label-grow split of a foreground mask (2-D bool / integer tensor on the GPU, 0 = background) into instances, for
     nuclei that touch: returns (labels int32 [H, W], n) as ``label_instances`` does, ready for ``nucleus_features(labels, gray,
     max_label=n)``.
@@ -244,17 +361,45 @@ def split_touching(mask, core_radius, connectivity=1, min_size=0, growth='euclid
     that hold no core.  The Euclidean growth cannot reach parts narrower than the core radius (tapered tips, necks), which become
     instances of their own, and hands pixels to the nearest core across a gap, which step 5 splits off as fragments.
 
+    ``markers='h_maxima'`` (needs ``growth='geodesic'`` and ``h``, in pixels; ``core_radius`` is ignored): only step 2 changes.  With
+    T = the largest integer with T^2 <= 64 dist2 (the distance to the background in eighths of a pixel) and h8 = the largest integer
+    with h8 / 8 <= h (at least 1: ValueError otherwise), the cores are label_instances(h_maxima(T, h8, connectivity) & mask,
+    connectivity): the summit plateaus of those maxima of the distance map that stand at least ``h`` above the saddle towards any
+    higher one (``& mask`` only matters for an image without foreground, whose flat distance map is one plateau).  What this buys:
+    one core, hence one node, per nucleus whatever its size -- a global ``core_radius`` large enough to cut the neck between two
+    large nuclei erases the cores of the small ones, and one small enough to keep those does not cut the neck -- and ``h`` only asks
+    how deep the neck is compared with the lower summit.  What it does not: summit plateaus are a few pixels wide, so growing them
+    back by a Euclidean radius has no meaning (hence the geodesic growth), and the cut between two nuclei falls on the geodesic
+    midline between the two summits, which for very unequal nuclei is not the neck.
+
     Host syncs: three, the reads of n of the three labelling calls; with ``growth='geodesic'`` plus those of the convergence loop of
-    geodesic_distance_transform (one when the longest path inside a nucleus crosses at most six tile edges, two up to 22)."""
+    geodesic_distance_transform (one when the longest path inside a nucleus crosses at most six tile edges, two up to 22); with
+    ``markers='h_maxima'`` plus those of reconstruct (one when no nucleus spans more than six tile edges)."""
     _check_image('split_touching', 'mask', mask)
     if growth not in ('euclidean', 'geodesic'):
         raise ValueError("growth must be 'euclidean' or 'geodesic', got %r" % (growth,))
-    radius2 = _d2max(core_radius, 'core_radius')
+    if markers not in ('core', 'h_maxima'):
+        raise ValueError("markers must be 'core' or 'h_maxima', got %r" % (markers,))
+    if markers == 'h_maxima':
+        if growth != 'geodesic':
+            raise ValueError("markers='h_maxima' needs growth='geodesic': summit plateaus cannot be grown back by a Euclidean radius")
+        if h is None:
+            raise ValueError("markers='h_maxima' needs h, the least dynamic of a marker in pixels")
+        h8 = _bound(h, 'h', lambda d: d * 8, lambda k: k / 8, INT32_MAX)
+        if h8 < 1:
+            raise ValueError('h must be at least 1 / 8 pixel (got %r)' % (h,))
+    else:
+        if h is not None:
+            raise ValueError("h is only used with markers='h_maxima'")
+        radius2 = _d2max(core_radius, 'core_radius')
     _check_connectivity(connectivity)
     _check_min_size(min_size)
     fg = mask != 0                          # an empty image goes through every step as an empty tensor, without a host read
     dist2 = distance_transform(fg)
-    cores, k = label_instances(dist2 > radius2, connectivity)
+    if markers == 'h_maxima':
+        cores, k = label_instances(h_maxima(_eighths(dist2), h8, connectivity) & fg, connectivity)
+    else:
+        cores, k = label_instances(dist2 > radius2, connectivity)
     if growth == 'geodesic':
         grown = expand_labels(cores, None, within=fg, geodesic=True, connectivity=connectivity)
     else:

@@ -59,8 +59,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *  10: connected-component labelling in front of them: cgc_label_ws_bytes, cgc_label_components, cgc_label_sizes
  *  11: exact distance transform with nearest sites: cgc_edt_ws_bytes, cgc_edt, CGC_EDT_INF
  *  12: geodesic distance transform with nearest seeds: cgc_geodesic_ws_bytes, cgc_geodesic_begin, cgc_geodesic_rounds,
- *      cgc_geodesic_finish, CGC_GEO_INF */
-#define CGC_ABI_VERSION 12
+ *      cgc_geodesic_finish, CGC_GEO_INF
+ *  13: grayscale morphological reconstruction: cgc_reconstruct_ws_bytes, cgc_reconstruct_begin, cgc_reconstruct_rounds,
+ *      cgc_reconstruct_finish */
+#define CGC_ABI_VERSION 13
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -195,6 +197,29 @@ int cgc_geodesic_begin(const void* seeds, int seed_bytes, const void* within_or_
 int cgc_geodesic_rounds(int H, int W, int a, int b, int connectivity, int dmax, void* ws, int first_round, int rounds, int* changed,
                         cgc_stream_t stream);
 int cgc_geodesic_finish(int H, int W, const void* ws, int* dist, int* nearest_or_null, cgc_stream_t stream);
+
+/* ---- F8 (beside F7): grayscale morphological reconstruction of a 2-D int32 image (csrc/reconstruct.hip), the primitive under h-maxima
+ * markers and hole filling.  The contract item by item: cgc-net_amd/kernels.py KernelSpec.morph_reconstruct.  marker, mask int32
+ * [H, W], contiguous; connectivity 1 (4 neighbours) or 2 (8 neighbours); H * W < 2^31; otherwise CGC_EINVAL and nothing is launched.
+ * By dilation (by_erosion = 0): R0 = min(marker, mask) pointwise -- a marker above the mask is clamped, not refused -- and R is the
+ * fixed point of R[p] = min(mask[p], max(R[p], max over the neighbours q of R[q])): R[p] = the largest, over pixels q and
+ * `connectivity`-paths from q to p, of min(R0[q], the smallest mask value on the path).  By erosion (by_erosion != 0): the dual,
+ * ~dilation(~marker, ~mask) with bitwise NOT, which reverses the order of all of int32 and cannot overflow.
+ * ws = cgc_reconstruct_ws_bytes(H, W) bytes (0: H * W is out of range).
+ *   cgc_reconstruct_begin: the clamped marker and the mask into ws (one launch).
+ *   cgc_reconstruct_rounds: rounds number first_round .. first_round + rounds - 1 of the relaxation, one launch each (plus one 4-byte
+ *     fill); the first call after begin passes first_round = 0, every later one the number of rounds already launched.  *changed
+ *     (device) = the number of tiles whose values moved in the LAST of these rounds: 0 means the values are final (further rounds are
+ *     harmless).  connectivity as described above; by_erosion is begin's and finish's business only.
+ *   cgc_reconstruct_finish: out int32 [H, W] = the reconstruction (one launch); by_erosion as given to begin.  H * W = 0: nothing is
+ *     written.
+ * No workgroup waits for another one in any launch, nothing allocates or synchronises: the caller reads *changed between batches of
+ * rounds.  The result is exact and a pure function of the input.  Worst case: the number of rounds needed is 2 + the number of 64 x 64
+ * tile edges that the longest path along which a value has to travel crosses -- a serpentine plateau over a whole image needs hundreds. */
+int64_t cgc_reconstruct_ws_bytes(int H, int W);
+int cgc_reconstruct_begin(const int* marker, const int* mask, int H, int W, int by_erosion, void* ws, cgc_stream_t stream);
+int cgc_reconstruct_rounds(int H, int W, int connectivity, void* ws, int first_round, int rounds, int* changed, cgc_stream_t stream);
+int cgc_reconstruct_finish(int H, int W, int by_erosion, const void* ws, int* out, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
