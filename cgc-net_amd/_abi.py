@@ -3,7 +3,7 @@ import ctypes as C
 
 P, I, F, D, L = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_int64
 
-ABI_VERSION = 13    # = CGC_ABI_VERSION of include/cgc_hip.h these prototypes were written against (tests compare the two)
+ABI_VERSION = 14    # = CGC_ABI_VERSION of include/cgc_hip.h these prototypes were written against (tests compare the two)
 
 PROTOTYPES = {
     'cgc_abi_version': [],
@@ -34,6 +34,12 @@ PROTOTYPES = {
     'cgc_reconstruct_begin': [P, P, I, I, I, P, P],
     'cgc_reconstruct_rounds': [I, I, I, P, I, I, P, P],
     'cgc_reconstruct_finish': [I, I, I, P, P, P],
+    'cgc_watershed_ws_bytes': [I, I],
+    'cgc_watershed_begin': [P, P, I, P, I, I, I, I, I, P, P],
+    'cgc_watershed_rounds': [I, I, I, I, I, P, I, I, P, P],
+    'cgc_watershed_parents': [I, I, I, I, I, P, P],
+    'cgc_watershed_jumps': [I, I, P, I, P, P],
+    'cgc_watershed_finish': [I, I, P, P, P, P],
     'cgc_edge_renorm': [P, P, I, F, P, P],
     'cgc_csr_transpose_vals': [P, P, P, I, P, P],
     'cgc_csr_invdeg': [P, P, I, P, P],

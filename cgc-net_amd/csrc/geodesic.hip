@@ -42,10 +42,6 @@ constexpr geo_key GEO_NONE = ((geo_key)CGC_GEO_INF << 32) | 0xffffffffull;
 constexpr geo_key GEO_REACHED = (geo_key)CGC_GEO_INF << 32;      // a key below this one carries a seed
 
 static inline int geo_tiles(int n) { return ceil_div(n, GEO_TILE); }
-static inline bool geo_bad_steps(int H, int W, int a, int b) {       // 1 <= a <= b <= 2a or b == 0; no path cost overflows int32
-  if (a < 1 || (b != 0 && (b < a || (int64_t)b > 2 * (int64_t)a))) return true;
-  return (int64_t)(b != 0 ? b : a) * H * W >= ((int64_t)1 << 31);
-}
 
 struct GeoWs {
   geo_key* key;          // [H*W]
@@ -60,15 +56,6 @@ static inline GeoWs geo_layout(Carver&& c, int H, int W) {      // the one defin
   return w;
 }
 
-__device__ __forceinline__ bool geo_nonzero(const void* img, int bytes, int64_t i) {     // `bytes` is uniform
-  switch (bytes) {
-    case 1: return static_cast<const uint8_t*>(img)[i] != 0;
-    case 2: return static_cast<const uint16_t*>(img)[i] != 0;
-    case 4: return static_cast<const uint32_t*>(img)[i] != 0;
-    default: return static_cast<const uint64_t*>(img)[i] != 0;
-  }
-}
-
 // (a) keys, domain, stamps.  Consecutive threads take consecutive pixels of a tile row.
 __global__ void __launch_bounds__(CGC_BLOCK) k_geo_begin(const void* __restrict__ seeds, int seed_bytes, const void* __restrict__ within,
                                                          int within_bytes, int H, int W, int tiles_x, geo_key* __restrict__ key,
@@ -81,8 +68,8 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_geo_begin(const void* __restrict_
     const int y = y0 + (p >> 6), x = x0 + (p & 63);
     if (y >= H || x >= W) continue;
     const int64_t i = (int64_t)y * W + x;
-    const bool seed = geo_nonzero(seeds, seed_bytes, i);
-    const bool in = seed || within == nullptr || geo_nonzero(within, within_bytes, i);
+    const bool seed = image_nonzero(seeds, seed_bytes, i);
+    const bool in = seed || within == nullptr || image_nonzero(within, within_bytes, i);
     key[i] = seed ? (geo_key)(unsigned)i : GEO_NONE;
     dom[i] = in ? 1 : 0;
     any |= in ? 1 : 0;
@@ -199,7 +186,7 @@ extern "C" int64_t cgc_geodesic_ws_bytes(int H, int W) {
 
 extern "C" int cgc_geodesic_begin(const void* seeds, int seed_bytes, const void* within, int within_bytes, int H, int W, int a, int b,
                                   void* ws, cgc_stream_t stream) {
-  if (bad_image_dims(H, W) || geo_bad_steps(H, W, a, b)) return CGC_EINVAL;
+  if (bad_image_dims(H, W) || bad_step_costs(H, W, a, b)) return CGC_EINVAL;
   if (bad_elem_bytes(seed_bytes) || (within != nullptr && bad_elem_bytes(within_bytes))) return CGC_EINVAL;
   if ((int64_t)H * W == 0) return 0;
   if (seeds == nullptr || ws == nullptr) return CGC_EINVAL;
@@ -213,7 +200,7 @@ extern "C" int cgc_geodesic_begin(const void* seeds, int seed_bytes, const void*
 
 extern "C" int cgc_geodesic_rounds(int H, int W, int a, int b, int connectivity, int dmax, void* ws, int first_round, int rounds,
                                    int* changed, cgc_stream_t stream) {
-  if (bad_image_dims(H, W) || geo_bad_steps(H, W, a, b)) return CGC_EINVAL;
+  if (bad_image_dims(H, W) || bad_step_costs(H, W, a, b)) return CGC_EINVAL;
   if ((connectivity != 1 && connectivity != 2) || first_round < 0 || rounds < 1 || first_round > 0x7fffffff - rounds - 1) return CGC_EINVAL;
   if (changed == nullptr) return CGC_EINVAL;
   hipStream_t st = as_stream(stream);

@@ -21,6 +21,7 @@ EDT_INF = 2 ** 31 - 1      # CGC_EDT_INF: dist2 of a pixel without a site (withi
 EDT_MAX_SIDE = 32767       # 2 * 32766^2 < 2^31 - 1: squared distances fit int32
 GEO_INF = 2 ** 31 - 1      # CGC_GEO_INF: dist of a pixel that no seed reaches (within the bound)
 GEO_FIRST_BATCH, GEO_MAX_BATCH = 8, 64      # rounds of geodesic_transform per host read: 8, 16, 32, 64, 64, ...
+WS_JUMP_BATCH = 8          # pointer jumps of watershed_flood per host read: resolves parent chains of up to 2^7 pixels in one read
 
 
 class KernelSpec(object):
@@ -186,6 +187,43 @@ class KernelSpec(object):
         value has to travel rounds are needed (the last one moves nothing).  Worst case: a serpentine plateau over a whole image
         crosses a tile edge per turn and needs hundreds of rounds.  ``reconstruct_rounds`` holds the rounds launched by the last
         call."""
+        raise NotImplementedError
+
+    def watershed_flood(self, height, seeds, within, a, b, connectivity):
+        """Seeded watershed flood of one height image (F9, beside morph_reconstruct; csrc/watershed.hip): water rises from the seeds,
+        and every pixel learns the level at which it is first wetted and the seed whose water wets it, so that the cut between two
+        seeds falls on the pass (the neck) between their basins.  Returns (level int32 [H, W], source int32 [H, W]).  The result is
+        defined without reference to any processing order, all arithmetic is integer: every result is exact and a pure function of
+        the input.
+
+        1.  height: int32 [H, W], any strides, the whole int32 range allowed.  seeds, within: as items 1 and 2 of geodesic_transform
+            -- [H, W] of a 1-, 2-, 4- or 8-byte integer type or bool, any strides, only "is zero" is read.  The domain is
+            D = {within != 0} u {seeds != 0}; within = None: every pixel.  The steps -- axial and diagonal, their costs a and b
+            (b == 0: no diagonal steps; 1 <= a <= b <= 2a otherwise, ValueError) and the connectivity-1 corner rule -- are exactly
+            geodesic_transform's.  (b or a) * H * W < 2^31 (ValueError otherwise, nothing is launched).
+        2.  The flood key K[p] = (alt, len), compared lexicographically.  A seed has K = (INT32_MIN, 0) and never changes.  Extending
+            a path with key (alt, len) by an allowed step of cost w onto a non-seed pixel p gives (height[p], 0) if height[p] > alt
+            -- the water rises onto p -- and (alt, len + w) otherwise -- it runs level or downhill; len is the way travelled since
+            the last rise.  K[p] is the smallest key over all paths from any seed.  alt is the height image with its unmarked
+            basins filled to their lowest pass.
+        3.  The parent of a reached non-seed pixel p: among the allowed steps q -> p with q reached, the q that minimises the triple
+            (extend_p(K[q]), K[q], raster index of q).  The first component's minimum is K[p], so the parent offers p its key; among
+            those offers the earliest-flooded neighbour wins, then the smallest index.  K[parent] < K[p] strictly, so the parents
+            form a forest rooted at the seeds.  A rim pixel thereby follows the steepest descent inward; it does not tie between all
+            of its lower neighbours.
+        4.  source[p] = the raster index of the root of p; a seed is its own root; -1 outside D and on domain pixels that no seed
+            reaches.  level[p] = alt of K[p] on reached non-seed pixels and height[p] everywhere else.  H * W = 0 gives empty
+            outputs.
+        Why a parallel relaxation gives exactly this: the extension is order-preserving and strictly increasing, so K is the unique
+        fixed point of K[p] = min over steps q -> p of extend_p(K[q]); every key ever stored is the key of a real path and keys only
+        decrease from "not reached", whatever the order of the updates.  Rounds are launches on geodesic_transform's schedule (one
+        64 x 64 tile per workgroup, relaxed to its own fixed point in LDS; the host reads the number of tiles that moved in the last
+        round of a batch of GEO_FIRST_BATCH (8), then twice as many up to GEO_MAX_BATCH (64), rounds).  Then one launch evaluates
+        item 3 and pointer jumping (ptr[p] = ptr[ptr[p]], in place) resolves the roots: the host reads the number of pixels that moved
+        in the last jump of a batch of WS_JUMP_BATCH (8) and stops when it is 0; 31 jumps always suffice.  Host reads: one per batch
+        of rounds and one per batch of jumps -- two when the flood crosses at most six tile edges and no parent chain exceeds 128
+        pixels.  Worst case: a serpentine valley over a whole image crosses a tile edge per turn, needs hundreds of rounds and the
+        logarithm of its length in jumps.  ``watershed_rounds`` and ``watershed_jumps`` hold the launches of the last call."""
         raise NotImplementedError
 
     def bgr_to_gray(self, bgr):
@@ -783,6 +821,49 @@ class HipKernels(KernelSpec):
         self.reconstruct_rounds = done
         self._chk(self.lib.cgc_reconstruct_finish(H, W, int(bool(by_erosion)), _ptr(ws), _ptr(out), st), 'cgc_reconstruct_finish')
         return out
+
+    def watershed_flood(self, height, seeds, within, a, b, connectivity):
+        assert height.dtype == torch.int32 and height.shape == seeds.shape and (within is None or within.shape == seeds.shape)
+        H, W = height.shape
+        a, b = int(a), int(b)
+        if a < 1 or (b != 0 and not a <= b <= 2 * a):
+            raise ValueError('watershed_flood needs steps 1 <= a <= b <= 2a or b == 0 (got a = %d, b = %d)' % (a, b))
+        if connectivity not in (1, 2):
+            raise ValueError('connectivity must be 1 or 2, got %r' % (connectivity,))
+        if (b or a) * H * W >= 2 ** 31:
+            raise ValueError('watershed_flood: %d * %d * %d reaches 2^31: a path length must fit int32' % (b or a, H, W))
+        height, seeds, within = self._image(height), self._image(seeds), self._image(within)      # after the refusals: may copy
+        dev = height.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        level, source = torch.empty(H, W, **i32), torch.empty(H, W, **i32)
+        self.watershed_rounds = self.watershed_jumps = 0      # launches of the last call (tests, tools)
+        if H * W == 0:
+            return level, source
+        ws = torch.empty(int(self.lib.cgc_watershed_ws_bytes(H, W)), dtype=torch.uint8, device=dev)
+        changed = torch.empty(1, **i32)
+        st = self._stream()
+        self._chk(self.lib.cgc_watershed_begin(_ptr(height), _ptr(seeds), seeds.element_size(), _ptr(within),
+                                               within.element_size() if within is not None else 0, H, W, a, b, _ptr(ws), st),
+                  'cgc_watershed_begin')
+        done, batch = 0, GEO_FIRST_BATCH
+        while True:
+            self._chk(self.lib.cgc_watershed_rounds(H, W, a, b, int(connectivity), _ptr(ws), done, batch, _ptr(changed), st),
+                      'cgc_watershed_rounds')
+            done += batch
+            if int(changed.item()) == 0:                # the host sync of the flood, once per batch: did the last round move a key?
+                break
+            batch = min(2 * batch, GEO_MAX_BATCH)
+        self.watershed_rounds = done
+        self._chk(self.lib.cgc_watershed_parents(H, W, a, b, int(connectivity), _ptr(ws), st), 'cgc_watershed_parents')
+        jumps = 0
+        while True:
+            self._chk(self.lib.cgc_watershed_jumps(H, W, _ptr(ws), WS_JUMP_BATCH, _ptr(changed), st), 'cgc_watershed_jumps')
+            jumps += WS_JUMP_BATCH
+            if int(changed.item()) == 0:                # the host sync of the roots, once per batch: did the last jump move a pointer?
+                break
+        self.watershed_jumps = jumps
+        self._chk(self.lib.cgc_watershed_finish(H, W, _ptr(ws), _ptr(level), _ptr(source), st), 'cgc_watershed_finish')
+        return level, source
 
     def bgr_to_gray(self, bgr):
         self._dev(bgr)

@@ -18,6 +18,11 @@ gives every mask pixel that is connected to a core the geodesically nearest core
 before the features are taken, and ``split_touching(..., markers='h_maxima', h=...)`` takes as cores the maxima of the distance map
 whose dynamic is at least ``h``, which finds one core per nucleus whatever its size.
 
+``watershed`` is the marker-controlled watershed (csrc/watershed.hip; kernels.KernelSpec.watershed_flood): water rises from the
+markers over a height image and every pixel takes the marker whose water wets it first.  ``split_touching(..., growth='flood')``
+floods the negated distance map from the cores, which puts the cut between two touching nuclei on the neck between them, however
+unequal they are.
+
 ``nucleus_features(labels, gray)`` returns the reference's ``feature`` / ``coordinate`` arrays of one image (csrc/nuclei.hip; the
 arithmetic item by item: kernels.KernelSpec.nucleus_features), ``graph_item`` turns them into the ``Data`` that
 ``_read_one_raw_graph`` builds, and ``save_reference_files`` writes them where the reference's dataset preparation reads them.
@@ -261,6 +266,42 @@ def reconstruct(marker, mask, method='dilation', connectivity=1):
     return out != 0 if marker.dtype == torch.bool else out.to(marker.dtype)
 
 
+def watershed(height, markers, within=None, metric='chamfer', connectivity=1, return_level=False):
+    """Marker-controlled (seeded) watershed.  height: 2-D bool / uint8 / int8 / int16 / int32 tensor on the GPU, any strides (int64 is
+    a TypeError: values must fit int32, and checking that would cost a host read); markers, within: 2-D bool / integer tensors of the
+    same shape on the same GPU (0 = no marker / outside the domain).  Returns the labels in the markers' dtype and, with
+    ``return_level``, level (int32 [H, W]).
+
+    Water rises from the marker pixels over ``height`` inside the domain {within != 0} u {markers != 0} (``within=None``: the whole
+    image), along the steps of geodesic_distance_transform (``metric``, ``connectivity``: the same names, pairs and corner rule).  A
+    pixel is wetted at level = the lowest, over all paths from any marker pixel, of the highest height on the path after the marker
+    (height with its unmarked basins filled to their lowest pass), and on that level by the path that has travelled the least since
+    it last rose (kernels.KernelSpec.watershed_flood, items 2 and 3: the definition does not depend on any processing order, so the
+    result is a pure function of the input, bit for bit).  Every wetted pixel takes the value of the marker pixel at the root of its
+    chain of parents; marker pixels never change; a pixel outside the domain, or one that no marker reaches, is 0 -- the reached
+    pixels are exactly the ``connectivity``-components of the domain that hold a marker.  Two basins meet on the pass between
+    them: there is no watershed line, every reached pixel has a label.  level is ``height`` on marker and unreached pixels.
+    (b or a) * H * W must stay below 2^31 (ValueError).
+
+    Host syncs: one per batch of relaxation rounds (8, then 16, 32, then 64 rounds each) until a round moves nothing, as
+    geodesic_distance_transform, then one per batch of 8 pointer jumps until a jump moves nothing (one when no chain of parents is
+    longer than 128 pixels): two in all for nuclei-sized basins.  A serpentine valley over a whole image is the case to avoid."""
+    _check_image('watershed', 'height', height, _INT32_DTYPES)
+    _check_image('watershed', 'markers', markers)
+    if tuple(markers.shape) != tuple(height.shape) or markers.device != height.device:
+        raise ValueError('watershed: height and markers must have the same shape and device (got %s on %s and %s on %s)'
+                         % (tuple(height.shape), height.device, tuple(markers.shape), markers.device))
+    _check_within('watershed', within, height)
+    a, b = _geodesic_steps(metric)
+    _check_connectivity(connectivity)
+    with torch.cuda.device(height.device):      # the kernel table refuses path lengths that overflow int32
+        level, source = kernels.get().watershed_flood(height.to(torch.int32), markers, within, a, b, int(connectivity))
+    # a marker pixel is its own root, so the gather returns it unchanged
+    src = markers.reshape(-1)[source.clamp(min=0).reshape(-1).long()].reshape(markers.shape)
+    labels = torch.where(source >= 0, src, torch.zeros_like(src))
+    return (labels, level) if return_level else labels
+
+
 def _check_h(h):
     try:
         h = operator.index(h)
@@ -361,7 +402,18 @@ def split_touching(mask, core_radius, connectivity=1, min_size=0, growth='euclid
     that hold no core.  The Euclidean growth cannot reach parts narrower than the core radius (tapered tips, necks), which become
     instances of their own, and hands pixels to the nearest core across a gap, which step 5 splits off as fragments.
 
-    ``markers='h_maxima'`` (needs ``growth='geodesic'`` and ``h``, in pixels; ``core_radius`` is ignored): only step 2 changes.  With
+    ``growth='flood'``: step 3 is watershed(-T, cores, within=mask, connectivity=connectivity) instead, with T = the largest integer
+    with T^2 <= 64 dist2 (the distance to the background in eighths of a pixel): water rises from the cores over the negated distance
+    map, chamfer (5, 7) steps inside the mask, and two cores' waters meet where the ridge of the distance map between them is lowest
+    -- the neck.  What this buys: the cut no longer moves with the sizes of the two nuclei.  Two touching discs of radius 28 and 16
+    are cut at the neck, within a pixel or two, and the large one keeps its pixels, where the geodesic growth cuts on the midline
+    between the cores, seven columns inside the large disc, and hands 8 % of it to the small one.  Like the geodesic growth it
+    reaches every mask pixel that is connected to a core and never a core of another object, so step 4 is again the components that
+    hold no core.  What it does not: it decides nothing about which cores exist -- a nucleus with two cores is still cut in two, one
+    without a core still merges with its neighbour -- and where there is no neck (two overlapping discs that form a convex blob) the
+    pass is flat and the cut is wherever the two waters meet on it, which is no better than the midline.
+
+    ``markers='h_maxima'`` (needs ``growth='geodesic'`` or ``'flood'`` and ``h``, in pixels; ``core_radius`` is ignored): only step 2 changes.  With
     T = the largest integer with T^2 <= 64 dist2 (the distance to the background in eighths of a pixel) and h8 = the largest integer
     with h8 / 8 <= h (at least 1: ValueError otherwise), the cores are label_instances(h_maxima(T, h8, connectivity) & mask,
     connectivity): the summit plateaus of those maxima of the distance map that stand at least ``h`` above the saddle towards any
@@ -369,20 +421,22 @@ def split_touching(mask, core_radius, connectivity=1, min_size=0, growth='euclid
     one core, hence one node, per nucleus whatever its size -- a global ``core_radius`` large enough to cut the neck between two
     large nuclei erases the cores of the small ones, and one small enough to keep those does not cut the neck -- and ``h`` only asks
     how deep the neck is compared with the lower summit.  What it does not: summit plateaus are a few pixels wide, so growing them
-    back by a Euclidean radius has no meaning (hence the geodesic growth), and the cut between two nuclei falls on the geodesic
-    midline between the two summits, which for very unequal nuclei is not the neck.
+    back by a Euclidean radius has no meaning (hence the geodesic growth), and with ``growth='geodesic'`` the cut between two nuclei
+    falls on the geodesic midline between the two summits, which for very unequal nuclei is not the neck (``growth='flood'`` puts it
+    there).
 
     Host syncs: three, the reads of n of the three labelling calls; with ``growth='geodesic'`` plus those of the convergence loop of
     geodesic_distance_transform (one when the longest path inside a nucleus crosses at most six tile edges, two up to 22); with
-    ``markers='h_maxima'`` plus those of reconstruct (one when no nucleus spans more than six tile edges)."""
+    ``markers='h_maxima'`` plus those of reconstruct (one when no nucleus spans more than six tile edges); with ``growth='flood'``
+    plus those of watershed (two for nuclei-sized basins)."""
     _check_image('split_touching', 'mask', mask)
-    if growth not in ('euclidean', 'geodesic'):
-        raise ValueError("growth must be 'euclidean' or 'geodesic', got %r" % (growth,))
+    if growth not in ('euclidean', 'geodesic', 'flood'):
+        raise ValueError("growth must be 'euclidean', 'geodesic' or 'flood', got %r" % (growth,))
     if markers not in ('core', 'h_maxima'):
         raise ValueError("markers must be 'core' or 'h_maxima', got %r" % (markers,))
     if markers == 'h_maxima':
-        if growth != 'geodesic':
-            raise ValueError("markers='h_maxima' needs growth='geodesic': summit plateaus cannot be grown back by a Euclidean radius")
+        if growth not in ('geodesic', 'flood'):
+            raise ValueError("markers='h_maxima' needs growth='geodesic' or 'flood': summit plateaus cannot be grown back by a Euclidean radius")
         if h is None:
             raise ValueError("markers='h_maxima' needs h, the least dynamic of a marker in pixels")
         h8 = _bound(h, 'h', lambda d: d * 8, lambda k: k / 8, INT32_MAX)
@@ -400,7 +454,9 @@ def split_touching(mask, core_radius, connectivity=1, min_size=0, growth='euclid
         cores, k = label_instances(h_maxima(_eighths(dist2), h8, connectivity) & fg, connectivity)
     else:
         cores, k = label_instances(dist2 > radius2, connectivity)
-    if growth == 'geodesic':
+    if growth == 'flood':
+        grown = watershed(-_eighths(dist2), cores, within=fg, connectivity=connectivity)
+    elif growth == 'geodesic':
         grown = expand_labels(cores, None, within=fg, geodesic=True, connectivity=connectivity)
     else:
         grown = expand_labels(cores, float(core_radius) + 1.0, within=fg)

@@ -61,8 +61,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *  12: geodesic distance transform with nearest seeds: cgc_geodesic_ws_bytes, cgc_geodesic_begin, cgc_geodesic_rounds,
  *      cgc_geodesic_finish, CGC_GEO_INF
  *  13: grayscale morphological reconstruction: cgc_reconstruct_ws_bytes, cgc_reconstruct_begin, cgc_reconstruct_rounds,
- *      cgc_reconstruct_finish */
-#define CGC_ABI_VERSION 13
+ *      cgc_reconstruct_finish
+ *  14: seeded watershed flood: cgc_watershed_ws_bytes, cgc_watershed_begin, cgc_watershed_rounds, cgc_watershed_parents,
+ *      cgc_watershed_jumps, cgc_watershed_finish */
+#define CGC_ABI_VERSION 14
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -220,6 +222,36 @@ int64_t cgc_reconstruct_ws_bytes(int H, int W);
 int cgc_reconstruct_begin(const int* marker, const int* mask, int H, int W, int by_erosion, void* ws, cgc_stream_t stream);
 int cgc_reconstruct_rounds(int H, int W, int connectivity, void* ws, int first_round, int rounds, int* changed, cgc_stream_t stream);
 int cgc_reconstruct_finish(int H, int W, int by_erosion, const void* ws, int* out, cgc_stream_t stream);
+
+/* ---- F9 (beside F8): seeded watershed flood of a 2-D int32 height image (csrc/watershed.hip): the level at which water rising from the
+ * seeds first wets every pixel of a domain, and the seed that wets it.  The contract item by item: cgc-net_amd/kernels.py
+ * KernelSpec.watershed_flood.  height int32 [H, W], contiguous, the whole int32 range; seeds, within_or_null, a, b, connectivity and
+ * the size limit exactly as F7's; otherwise CGC_EINVAL and nothing is launched.  The flood key of a pixel is (alt, len), compared
+ * lexicographically: (INT32_MIN, 0) on seeds; a step of cost w from a pixel with key (alt, len) onto the non-seed pixel p offers
+ * (height[p], 0) if height[p] > alt, else (alt, len + w); a pixel keeps the smallest offer over all paths from any seed.
+ * ws = cgc_watershed_ws_bytes(H, W) bytes (0: H * W is out of range).
+ *   cgc_watershed_begin: keys, domain and a copy of the heights into ws (one launch).
+ *   cgc_watershed_rounds: as cgc_geodesic_rounds (no dmax): *changed (device) = the number of tiles whose keys moved in the LAST of
+ *     these rounds; 0 means the keys are final.
+ *   cgc_watershed_parents: after the keys are final (one launch): the parent of a reached non-seed pixel p is the neighbour q that
+ *     minimises (the offer of q to p, the key of q, the raster index of q) over the allowed steps q -> p from reached pixels; a seed is
+ *     its own parent.  The key of a parent is strictly smaller, so the parents form a forest rooted at the seeds.
+ *   cgc_watershed_jumps: `jumps` >= 1 pointer jumps parent[p] = parent[parent[p]], in place, one launch each (plus one 4-byte fill).
+ *     *changed (device) = the number of pixels whose pointer moved in the LAST of these jumps: 0 means every pointer names its root
+ *     (further jumps are harmless).  31 jumps always suffice.
+ *   cgc_watershed_finish: level int32 [H, W] = alt on reached non-seed pixels, height elsewhere; source int32 [H, W] = the raster
+ *     index of the root (a seed: its own index), -1 outside the domain and where no seed reaches.  H * W = 0: nothing is written.
+ * No workgroup waits for another one in any launch, nothing allocates or synchronises: the caller reads *changed between batches.
+ * The result is exact and a pure function of the input.  Worst case: as F7's for the rounds -- a serpentine valley over a whole image
+ * needs hundreds -- and the logarithm of the longest parent chain for the jumps. */
+int64_t cgc_watershed_ws_bytes(int H, int W);
+int cgc_watershed_begin(const int* height, const void* seeds, int seed_bytes, const void* within_or_null, int within_bytes, int H, int W,
+                        int a, int b, void* ws, cgc_stream_t stream);
+int cgc_watershed_rounds(int H, int W, int a, int b, int connectivity, void* ws, int first_round, int rounds, int* changed,
+                         cgc_stream_t stream);
+int cgc_watershed_parents(int H, int W, int a, int b, int connectivity, void* ws, cgc_stream_t stream);
+int cgc_watershed_jumps(int H, int W, void* ws, int jumps, int* changed, cgc_stream_t stream);
+int cgc_watershed_finish(int H, int W, const void* ws, int* level, int* source, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
