@@ -15,6 +15,9 @@ static inline bool bad_step_costs(int H, int W, int a, int b) {
   if (a < 1 || (b != 0 && (b < a || (int64_t)b > 2 * (int64_t)a))) return true;
   return (int64_t)(b != 0 ? b : a) * H * W >= ((int64_t)1 << 31);
 }
+static inline bool bad_connectivity(int connectivity) { return connectivity != 1 && connectivity != 2; }
+// A batch of launches first .. first + count - 1 (tile_relax.hpp): at least one, and first + count + 1 fits int32 (a round stamps r + 1).
+static inline bool bad_launch_range(int first, int count) { return first < 0 || count < 1 || first > 0x7fffffff - count - 1; }
 
 __device__ __forceinline__ bool image_nonzero(const void* img, int bytes, int64_t i) {     // `bytes` is uniform
   switch (bytes) {

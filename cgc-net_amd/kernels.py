@@ -760,16 +760,39 @@ class HipKernels(KernelSpec):
                                    _ptr(nearest), self._stream()), 'cgc_edt')
         return dist2, nearest
 
+    @staticmethod
+    def _check_connectivity(connectivity):
+        if connectivity not in (1, 2):
+            raise ValueError('connectivity must be 1 or 2, got %r' % (connectivity,))
+
+    @staticmethod
+    def _check_steps(name, a, b, connectivity, H, W, what):
+        """The refusals of a path relaxation, which need shapes only (before any copy): the step costs, the connectivity, and that no
+        path's ``what`` ('cost', 'length') reaches 2^31."""
+        if a < 1 or (b != 0 and not a <= b <= 2 * a):
+            raise ValueError('%s needs steps 1 <= a <= b <= 2a or b == 0 (got a = %d, b = %d)' % (name, a, b))
+        HipKernels._check_connectivity(connectivity)
+        if (b or a) * H * W >= 2 ** 31:
+            raise ValueError('%s: %d * %d * %d reaches 2^31: a path %s must fit int32' % (name, b or a, H, W, what))
+
+    @staticmethod
+    def _relax_until_still(launch, changed, first_batch, max_batch):
+        """launch(first, count) enqueues launches first .. first + count - 1 of a stage of csrc/tile_relax.hpp, the last of which
+        counts into ``changed`` what it moved.  Batches of first_batch, twice that, ... up to max_batch, one host read (the stage's
+        host sync) after each, until a batch ends still.  Returns the launches done."""
+        done, batch = 0, first_batch
+        while True:
+            launch(done, batch)
+            done += batch
+            if int(changed.item()) == 0:
+                return done
+            batch = min(2 * batch, max_batch)
+
     def geodesic_transform(self, seeds, within, a, b, connectivity, dmax, want_nearest=False):
         assert within is None or within.shape == seeds.shape
         H, W = seeds.shape
         a, b = int(a), int(b)
-        if a < 1 or (b != 0 and not a <= b <= 2 * a):
-            raise ValueError('geodesic_transform needs steps 1 <= a <= b <= 2a or b == 0 (got a = %d, b = %d)' % (a, b))
-        if connectivity not in (1, 2):
-            raise ValueError('connectivity must be 1 or 2, got %r' % (connectivity,))
-        if (b or a) * H * W >= 2 ** 31:
-            raise ValueError('geodesic_transform: %d * %d * %d reaches 2^31: a path cost must fit int32' % (b or a, H, W))
+        HipKernels._check_steps('geodesic_transform', a, b, connectivity, H, W, 'cost')
         seeds, within = self._image(seeds), self._image(within)      # after the refusals: may copy
         dev = seeds.device
         i32 = dict(dtype=torch.int32, device=dev)
@@ -782,22 +805,16 @@ class HipKernels(KernelSpec):
         st = self._stream()
         self._chk(self.lib.cgc_geodesic_begin(_ptr(seeds), seeds.element_size(), _ptr(within), within.element_size() if within is not None else 0,
                                               H, W, a, b, _ptr(ws), st), 'cgc_geodesic_begin')
-        done, batch = 0, GEO_FIRST_BATCH
-        while True:
-            self._chk(self.lib.cgc_geodesic_rounds(H, W, a, b, int(connectivity), int(dmax), _ptr(ws), done, batch, _ptr(changed), st),
-                      'cgc_geodesic_rounds')
-            done += batch
-            if int(changed.item()) == 0:                # the host sync of this stage, once per batch: did the last round move a key?
-                break
-            batch = min(2 * batch, GEO_MAX_BATCH)
-        self.geodesic_rounds = done                     # rounds launched by the last call (tests, tools)
+        self.geodesic_rounds = self._relax_until_still(                      # rounds launched by the last call (tests, tools)
+            lambda first, count: self._chk(self.lib.cgc_geodesic_rounds(H, W, a, b, int(connectivity), int(dmax), _ptr(ws), first, count,
+                                                                        _ptr(changed), st), 'cgc_geodesic_rounds'),
+            changed, GEO_FIRST_BATCH, GEO_MAX_BATCH)
         self._chk(self.lib.cgc_geodesic_finish(H, W, _ptr(ws), _ptr(dist), _ptr(nearest), st), 'cgc_geodesic_finish')
         return dist, nearest
 
     def morph_reconstruct(self, marker, mask, connectivity, by_erosion=False):
         assert marker.dtype == torch.int32 and mask.dtype == torch.int32 and marker.shape == mask.shape
-        if connectivity not in (1, 2):
-            raise ValueError('connectivity must be 1 or 2, got %r' % (connectivity,))
+        HipKernels._check_connectivity(connectivity)      # by the class: the refusals need no instance
         marker, mask = self._image(marker), self._image(mask)      # after the refusal: may copy
         H, W = marker.shape
         dev = marker.device
@@ -810,15 +827,10 @@ class HipKernels(KernelSpec):
         st = self._stream()
         self._chk(self.lib.cgc_reconstruct_begin(_ptr(marker), _ptr(mask), H, W, int(bool(by_erosion)), _ptr(ws), st),
                   'cgc_reconstruct_begin')
-        done, batch = 0, GEO_FIRST_BATCH
-        while True:
-            self._chk(self.lib.cgc_reconstruct_rounds(H, W, int(connectivity), _ptr(ws), done, batch, _ptr(changed), st),
-                      'cgc_reconstruct_rounds')
-            done += batch
-            if int(changed.item()) == 0:                # the host sync of this stage, once per batch: did the last round move a value?
-                break
-            batch = min(2 * batch, GEO_MAX_BATCH)
-        self.reconstruct_rounds = done
+        self.reconstruct_rounds = self._relax_until_still(
+            lambda first, count: self._chk(self.lib.cgc_reconstruct_rounds(H, W, int(connectivity), _ptr(ws), first, count, _ptr(changed),
+                                                                           st), 'cgc_reconstruct_rounds'),
+            changed, GEO_FIRST_BATCH, GEO_MAX_BATCH)
         self._chk(self.lib.cgc_reconstruct_finish(H, W, int(bool(by_erosion)), _ptr(ws), _ptr(out), st), 'cgc_reconstruct_finish')
         return out
 
@@ -826,12 +838,7 @@ class HipKernels(KernelSpec):
         assert height.dtype == torch.int32 and height.shape == seeds.shape and (within is None or within.shape == seeds.shape)
         H, W = height.shape
         a, b = int(a), int(b)
-        if a < 1 or (b != 0 and not a <= b <= 2 * a):
-            raise ValueError('watershed_flood needs steps 1 <= a <= b <= 2a or b == 0 (got a = %d, b = %d)' % (a, b))
-        if connectivity not in (1, 2):
-            raise ValueError('connectivity must be 1 or 2, got %r' % (connectivity,))
-        if (b or a) * H * W >= 2 ** 31:
-            raise ValueError('watershed_flood: %d * %d * %d reaches 2^31: a path length must fit int32' % (b or a, H, W))
+        HipKernels._check_steps('watershed_flood', a, b, connectivity, H, W, 'length')
         height, seeds, within = self._image(height), self._image(seeds), self._image(within)      # after the refusals: may copy
         dev = height.device
         i32 = dict(dtype=torch.int32, device=dev)
@@ -845,23 +852,14 @@ class HipKernels(KernelSpec):
         self._chk(self.lib.cgc_watershed_begin(_ptr(height), _ptr(seeds), seeds.element_size(), _ptr(within),
                                                within.element_size() if within is not None else 0, H, W, a, b, _ptr(ws), st),
                   'cgc_watershed_begin')
-        done, batch = 0, GEO_FIRST_BATCH
-        while True:
-            self._chk(self.lib.cgc_watershed_rounds(H, W, a, b, int(connectivity), _ptr(ws), done, batch, _ptr(changed), st),
-                      'cgc_watershed_rounds')
-            done += batch
-            if int(changed.item()) == 0:                # the host sync of the flood, once per batch: did the last round move a key?
-                break
-            batch = min(2 * batch, GEO_MAX_BATCH)
-        self.watershed_rounds = done
+        self.watershed_rounds = self._relax_until_still(
+            lambda first, count: self._chk(self.lib.cgc_watershed_rounds(H, W, a, b, int(connectivity), _ptr(ws), first, count,
+                                                                         _ptr(changed), st), 'cgc_watershed_rounds'),
+            changed, GEO_FIRST_BATCH, GEO_MAX_BATCH)
         self._chk(self.lib.cgc_watershed_parents(H, W, a, b, int(connectivity), _ptr(ws), st), 'cgc_watershed_parents')
-        jumps = 0
-        while True:
-            self._chk(self.lib.cgc_watershed_jumps(H, W, _ptr(ws), WS_JUMP_BATCH, _ptr(changed), st), 'cgc_watershed_jumps')
-            jumps += WS_JUMP_BATCH
-            if int(changed.item()) == 0:                # the host sync of the roots, once per batch: did the last jump move a pointer?
-                break
-        self.watershed_jumps = jumps
+        self.watershed_jumps = self._relax_until_still(                      # a constant batch: the entry takes no first jump
+            lambda first, count: self._chk(self.lib.cgc_watershed_jumps(H, W, _ptr(ws), count, _ptr(changed), st), 'cgc_watershed_jumps'),
+            changed, WS_JUMP_BATCH, WS_JUMP_BATCH)
         self._chk(self.lib.cgc_watershed_finish(H, W, _ptr(ws), _ptr(level), _ptr(source), st), 'cgc_watershed_finish')
         return level, source
 
