@@ -3,7 +3,7 @@ import ctypes as C
 
 P, I, F, D, L = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_int64
 
-ABI_VERSION = 14    # = CGC_ABI_VERSION of include/cgc_hip.h these prototypes were written against (tests compare the two)
+ABI_VERSION = 15   # = CGC_ABI_VERSION of include/cgc_hip.h these prototypes were written against (tests compare the two)
 
 PROTOTYPES = {
     'cgc_abi_version': [],
@@ -40,6 +40,10 @@ PROTOTYPES = {
     'cgc_watershed_parents': [I, I, I, I, I, P, P],
     'cgc_watershed_jumps': [I, I, P, I, P, P],
     'cgc_watershed_finish': [I, I, P, P, P, P],
+    'cgc_stain_separate': [P, L, I, P, P, I, P, P],
+    'cgc_histogram_chunk_pixels': [],
+    'cgc_histogram_u8': [P, L, P, I, P, P],
+    'cgc_binomial_smooth_u8': [P, I, I, I, P, P],
     'cgc_edge_renorm': [P, P, I, F, P, P],
     'cgc_csr_transpose_vals': [P, P, P, I, P, P],
     'cgc_csr_invdeg': [P, P, I, P, P],

@@ -21,6 +21,8 @@ EDT_INF = 2 ** 31 - 1      # CGC_EDT_INF: dist2 of a pixel without a site (withi
 EDT_MAX_SIDE = 32767       # 2 * 32766^2 < 2^31 - 1: squared distances fit int32
 GEO_INF = 2 ** 31 - 1      # CGC_GEO_INF: dist of a pixel that no seed reaches (within the bound)
 GEO_FIRST_BATCH, GEO_MAX_BATCH = 8, 64      # rounds of geodesic_transform per host read: 8, 16, 32, 64, 64, ...
+STAIN_OD_MAX = 5674        # floor(1024 ln 255 + 0.5): the largest optical density of stain_separate's table
+SMOOTH_MAX_RADIUS = 5      # binomial_smooth: 255 * 4^(2 * 5) < 2^31
 WS_JUMP_BATCH = 8          # pointer jumps of watershed_flood per host read: resolves parent chains of up to 2^7 pixels in one read
 
 
@@ -228,6 +230,53 @@ class KernelSpec(object):
 
     def bgr_to_gray(self, bgr):
         """cv2.cvtColor(img, COLOR_BGR2GRAY) on uint8 [H, W, 3]: (1868 B + 9617 G + 4899 R + 8192) >> 14 -> uint8 [H, W]."""
+        raise NotImplementedError
+
+    def stain_separate(self, image, order, lut, m, planes):
+        """Colour deconvolution of one stained tile in fixed point (F10, in front of the foreground map; csrc/stain.hip; Ruifrok and
+        Johnston 2001).  Returns uint8 [popcount(planes), H, W], contiguous; no host read.  All arithmetic is integer: every result is
+        exact and a pure function of the input.
+
+        1.  image: uint8 [H, W, 3], any strides, H * W < 2^31.  order 0: the channels are B, G, R (cv2, bgr_to_gray); 1: R, G, B.
+        2.  lut: 256 integers, the optical density of a channel value in 1/1024 of a natural-log unit:
+            lut[v] = floor(1024 ln(255 / max(v, 1)) + 0.5), from 0 (v = 255) to 5674 (v = 0 or 1).  Entries outside [0, 5674] are
+            refused (ValueError).
+        3.  m: 3 x 3 integers, m[c][s] = rint(4096 inv(S)[c][s]) with c = 0 R, 1 G, 2 B, where the rows of S are the unit-normalised
+            OD vectors of the three stains: OD = C S, so C = OD inv(S).
+        4.  C_s = lut[R] m[0][s] + lut[G] m[1][s] + lut[B] m[2][s] in int32.  sum_c |m[c][s]| * 5674 < 2^31 - 2^15 for every s
+            (ValueError otherwise, nothing is launched): neither the sum nor the rounding term below can overflow.
+        5.  out_s = clamp((C_s + 2^15) >> 16, 0, 255) with an arithmetic shift (round half up, also below zero).  One level is 1 / 64
+            of a unit of natural-log concentration: 2^-16 * 1024 * 4096 = 64 levels per unit.
+        6.  planes: a bit mask, bit s = stain s is wanted, 1..7 (ValueError otherwise); the output holds the wanted planes in ascending
+            stain order.
+        7.  H * W = 0 gives an empty output.
+        Error against the real-number formula 64 ln(255 / max(v, 1)) inv(S): at most 64 (a_s / 2048 + 3 * 5.55 / 8192) + 1/2 levels
+        with a_s = sum_c |inv(S)[c][s]| -- the table's rounding times the matrix, the matrix's rounding times the largest OD (5.55),
+        and the final rounding; 0.76 for a_s = 4."""
+        raise NotImplementedError
+
+    def histogram_u8(self, image, within=None):
+        """256-bin histogram of one uint8 image (F10; csrc/stain.hip).  Returns hist int32 [256] on the device; no host read.
+
+        1.  image: uint8 [H, W], any strides, H * W < 2^31, so every count fits int32.
+        2.  within: None or [H, W] of a 1-, 2-, 4- or 8-byte integer type or bool, any strides; only "is zero" is read.
+        3.  hist[v] = the number of pixels p with image[p] == v and (within is None or within[p] != 0).  sum(hist) = the number of
+            selected pixels.
+        4.  H * W = 0, or a within that selects nothing, gives zeros.
+        Integer counts: the result does not depend on the order of the atomic adds.  A workgroup counts ``histogram_chunk`` (16384)
+        consecutive pixels in LDS and flushes its non-empty bins once."""
+        raise NotImplementedError
+
+    def binomial_smooth(self, image, radius):
+        """Separable binomial smoothing of one uint8 image (F10; csrc/smooth.hip).  Returns uint8 [H, W], contiguous; no host read.
+
+        1.  image: uint8 [H, W], any strides, H * W < 2^31.  radius r: an integer in 0..5 (ValueError otherwise).
+        2.  Weights w_k = C(2 r, k), k = 0..2 r; they sum to 4^r.  The kernel w w^T has standard deviation sqrt(r / 2) per axis
+            (1.58 at r = 5); larger blurs are repeated calls.
+        3.  out[y, x] = (sum_i sum_j w_i w_j image[clamp(y + i - r, 0, H - 1), clamp(x + j - r, 0, W - 1)] + 2^(4 r - 1)) >> 4 r: the
+            border is replicated, and there is ONE rounding (half up), after both passes.  Everything is exact in int32: 255 * 2^20 <
+            2^31.  r = 0 is a copy (no rounding term).
+        4.  H < r or W < r are ordinary shapes: the clamp covers them.  H * W = 0 gives an empty output."""
         raise NotImplementedError
 
     def edge_renorm(self, rowptr, col, n, p, val_out):
@@ -574,6 +623,7 @@ class HipKernels(KernelSpec):
         _abi.declare(self.lib)
         self._ws_cache = {}
         self._graph_local_max = int(self.lib.cgc_graph_local_max_nodes())
+        self.histogram_chunk = int(self.lib.cgc_histogram_chunk_pixels())      # pixels one workgroup of histogram_u8 counts (tests)
 
     # -- helpers
     @staticmethod
@@ -869,6 +919,54 @@ class HipKernels(KernelSpec):
         bgr = bgr.contiguous()
         out = torch.empty(bgr.shape[0], bgr.shape[1], dtype=torch.uint8, device=bgr.device)
         self._chk(self.lib.cgc_bgr_to_gray(_ptr(bgr), ctypes.c_int64(out.numel()), _ptr(out), self._stream()), 'cgc_bgr_to_gray')
+        return out
+
+    @staticmethod
+    def _check_stain_tables(order, lut, m, planes):
+        """The refusals of stain_separate, which need no tensor: returns (lut, m) as flat lists of Python integers."""
+        if order not in (0, 1):
+            raise ValueError('stain_separate: order must be 0 (BGR) or 1 (RGB), got %r' % (order,))
+        if planes not in range(1, 8):
+            raise ValueError('stain_separate: planes must be a bit mask in 1..7, got %r' % (planes,))
+        lut = [int(v) for v in lut]
+        m = [int(v) for row in m for v in row]
+        if len(lut) != 256 or min(lut) < 0 or max(lut) > STAIN_OD_MAX:
+            raise ValueError('stain_separate: the optical-density table must hold 256 integers in [0, %d]' % STAIN_OD_MAX)
+        if len(m) != 9:
+            raise ValueError('stain_separate: the matrix must be 3 x 3')
+        for s in range(3):
+            if sum(abs(m[3 * c + s]) for c in range(3)) * STAIN_OD_MAX >= 2 ** 31 - 2 ** 15:
+                raise ValueError('stain_separate: column %d of the matrix lets the int32 sum overflow (near-singular stains)' % s)
+        return lut, m
+
+    def stain_separate(self, image, order, lut, m, planes):
+        lut, m = HipKernels._check_stain_tables(order, lut, m, planes)      # by the class: the refusals need no instance
+        self._dev(image)
+        assert image.dtype == torch.uint8 and image.dim() == 3 and image.shape[2] == 3
+        image = image.contiguous()
+        H, W = image.shape[:2]
+        out = torch.empty(bin(planes).count('1'), H, W, dtype=torch.uint8, device=image.device)
+        self._chk(self.lib.cgc_stain_separate(_ptr(image), ctypes.c_int64(H * W), int(order), (ctypes.c_int * 256)(*lut),
+                                              (ctypes.c_int * 9)(*m), int(planes), _ptr(out), self._stream()), 'cgc_stain_separate')
+        return out
+
+    def histogram_u8(self, image, within=None):
+        assert image.dtype == torch.uint8 and (within is None or within.shape == image.shape)
+        image, within = self._image(image), self._image(within)
+        hist = torch.empty(256, dtype=torch.int32, device=image.device)
+        self._chk(self.lib.cgc_histogram_u8(_ptr(image), ctypes.c_int64(image.numel()), _ptr(within),
+                                            within.element_size() if within is not None else 0, _ptr(hist), self._stream()),
+                  'cgc_histogram_u8')
+        return hist
+
+    def binomial_smooth(self, image, radius):
+        if radius not in range(0, SMOOTH_MAX_RADIUS + 1):
+            raise ValueError('binomial_smooth: radius must be an integer in 0..%d, got %r' % (SMOOTH_MAX_RADIUS, radius))
+        assert image.dtype == torch.uint8
+        image = self._image(image)
+        H, W = image.shape
+        out = torch.empty(H, W, dtype=torch.uint8, device=image.device)
+        self._chk(self.lib.cgc_binomial_smooth_u8(_ptr(image), H, W, int(radius), _ptr(out), self._stream()), 'cgc_binomial_smooth_u8')
         return out
 
     def edge_renorm(self, rowptr, col, n, p, val_out):

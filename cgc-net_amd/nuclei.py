@@ -23,6 +23,12 @@ markers over a height image and every pixel takes the marker whose water wets it
 floods the negated distance map from the cores, which puts the cut between two touching nuclei on the neck between them, however
 unequal they are.
 
+``stain_foreground`` is the step in front of all of them, for a user who holds only the H&E tile: colour deconvolution into a
+haematoxylin plane (``separate_stains``; csrc/stain.hip, kernels.KernelSpec.stain_separate), a little binomial smoothing (``smooth``;
+csrc/smooth.hip) and Otsu's threshold of the plane's histogram (``histogram``, ``otsu_threshold``) -- all in integer arithmetic with a
+stated contract, so that the foreground map is a pure function of the tile.  Its output goes into ``fill_holes`` and
+``split_touching``.
+
 ``nucleus_features(labels, gray)`` returns the reference's ``feature`` / ``coordinate`` arrays of one image (csrc/nuclei.hip; the
 arithmetic item by item: kernels.KernelSpec.nucleus_features), ``graph_item`` turns them into the ``Data`` that
 ``_read_one_raw_graph`` builds, and ``save_reference_files`` writes them where the reference's dataset preparation reads them.
@@ -510,6 +516,180 @@ def bgr_to_gray(bgr):
     if not torch.is_tensor(bgr) or bgr.dtype != torch.uint8 or bgr.dim() != 3 or bgr.shape[2] != 3:
         raise ValueError('bgr_to_gray takes a uint8 [H, W, 3] tensor')
     return kernels.get().bgr_to_gray(bgr)
+
+
+def _od_lut():
+    """The optical density of every channel value in 1/1024 of a natural-log unit: floor(1024 ln(255 / max(v, 1)) + 0.5).  No entry
+    lies within 1e-3 of a rounding boundary (tests/test_stain_ref_cpu.py), so every libm gives the same table."""
+    return tuple(int(math.floor(1024.0 * math.log(255.0 / max(v, 1)) + 0.5)) for v in range(256))
+
+
+OD_LUT = _od_lut()
+# unit OD vectors (R, G, B) of haematoxylin, eosin and a residual (Ruifrok and Johnston 2001; rows are normalised by stain_matrix)
+DEFAULT_STAINS = ((0.65, 0.70, 0.29), (0.07, 0.99, 0.11), (0.27, 0.57, 0.78))
+STAIN_ORDERS = {'bgr': 0, 'rgb': 1}
+
+
+def stain_matrix(stains=None):
+    """The fixed-point deconvolution matrix of three stains: numpy int32 [3, 3], m[c][s] = rint(4096 inv(S)[c][s]), c = 0 R, 1 G, 2 B.
+    ``stains``: 3 x 3 numbers, row s = the optical-density vector (R, G, B) of stain s, any positive length (None: DEFAULT_STAINS --
+    haematoxylin, eosin, residual).  The rows are normalised to unit length and S is inverted in float64.  ValueError: a shape other
+    than 3 x 3, a non-finite entry, a zero row, a singular matrix, or a column with sum_c |m[c][s]| * 5674 >= 2^31 - 2^15 (stains so
+    nearly dependent that the int32 arithmetic of separate_stains could overflow)."""
+    try:
+        S = np.array(DEFAULT_STAINS if stains is None else stains, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('stains must be 3 x 3 numbers')
+    if S.shape != (3, 3):
+        raise ValueError('stains must be 3 x 3 (got shape %s)' % (S.shape,))
+    if not np.isfinite(S).all():
+        raise ValueError('stains must be finite')
+    norm = np.sqrt((S * S).sum(axis=1))
+    if not (norm > 0).all() or not np.isfinite(norm).all():
+        raise ValueError('every stain needs a non-zero optical-density vector')
+    S = S / norm[:, None]
+    try:
+        inv = np.linalg.inv(S)
+    except np.linalg.LinAlgError:
+        raise ValueError('the stain vectors are linearly dependent')
+    if not np.isfinite(inv).all() or np.linalg.matrix_rank(S) < 3:
+        raise ValueError('the stain vectors are linearly dependent')
+    q = np.rint(4096.0 * inv)
+    if (np.abs(q).sum(axis=0) * kernels.STAIN_OD_MAX >= 2 ** 31 - 2 ** 15).any():
+        raise ValueError('the stain vectors are too nearly dependent: the int32 sum of separate_stains could overflow')
+    return q.astype(np.int32)
+
+
+def _check_color(fn, image):
+    """A colour image: a uint8 [H, W, 3] tensor on the GPU of fewer than 2^31 pixels (_check_image on one channel)."""
+    if not torch.is_tensor(image):
+        raise TypeError('%s takes torch tensors on the GPU (image)' % fn)
+    if image.dim() != 3 or image.shape[2] != 3:
+        raise ValueError('%s: image must be [H, W, 3] (got %s)' % (fn, tuple(image.shape)))
+    _check_image(fn, 'image', image[:, :, 0], (torch.uint8,))
+
+
+def _check_planes(planes):
+    """The bit mask of a sequence of distinct stain indices in ascending order."""
+    try:
+        idx = [operator.index(s) for s in planes]
+    except TypeError:
+        raise ValueError('planes must be a sequence of stain indices 0..2 (got %r)' % (planes,))
+    if not idx or any(s not in (0, 1, 2) for s in idx) or any(a >= b for a, b in zip(idx, idx[1:])):
+        raise ValueError('planes must be distinct stain indices 0..2 in ascending order, at least one (got %r)' % (planes,))
+    return sum(1 << s for s in idx)
+
+
+def _check_radius(radius):
+    try:
+        radius = operator.index(radius)
+    except TypeError:
+        raise ValueError('radius must be an integer in 0..%d (got %r)' % (kernels.SMOOTH_MAX_RADIUS, radius))
+    if not 0 <= radius <= kernels.SMOOTH_MAX_RADIUS:
+        raise ValueError('radius must be an integer in 0..%d (got %r)' % (kernels.SMOOTH_MAX_RADIUS, radius))
+    return radius
+
+
+def separate_stains(image, stains=None, order='bgr', planes=(0, 1, 2)):
+    """Colour deconvolution (Ruifrok and Johnston 2001) of a stained tile.  image: uint8 [H, W, 3] tensor on the GPU, any strides;
+    ``order``: 'bgr' (cv2, bgr_to_gray) or 'rgb'; ``stains``: as stain_matrix (None: haematoxylin, eosin, residual); ``planes``: the
+    wanted stains, distinct indices in ascending order.  Returns uint8 [len(planes), H, W]: the concentration of each wanted stain in
+    levels of 1 / 64 of a natural-log unit, clamped to [0, 255] -- a dark nucleus of concentration 2.1 lands at 134.  Fixed-point
+    arithmetic with a stated contract (kernels.KernelSpec.stain_separate): the result is exact, a pure function of the input, and
+    within one level of the float64 formula.
+
+    Host syncs: none."""
+    _check_color('separate_stains', image)
+    if order not in STAIN_ORDERS:
+        raise ValueError("order must be 'bgr' or 'rgb', got %r" % (order,))
+    mask = _check_planes(planes)
+    m = stain_matrix(stains)
+    with torch.cuda.device(image.device):
+        return kernels.get().stain_separate(image, STAIN_ORDERS[order], OD_LUT, m.tolist(), mask)
+
+
+def _check_gray(fn, image, within):
+    _check_image(fn, 'image', image, (torch.uint8,))
+    _check_within(fn, within, image)
+
+
+def histogram(image, within=None):
+    """The 256-bin histogram of a uint8 [H, W] tensor on the GPU (any strides; other dtypes are a TypeError): int64 [256] on the
+    device, hist[v] = the number of pixels of value v -- with ``within`` (bool / integer, same shape and device) only those where
+    ``within`` is non-zero.
+
+    Host syncs: none."""
+    _check_gray('histogram', image, within)
+    with torch.cuda.device(image.device):
+        return kernels.get().histogram_u8(image, within).to(torch.int64)
+
+
+def _otsu(counts):
+    """Otsu's threshold of 256 counts, in Python integers: the t in 0..254 with 0 < w0(t) < N that maximises the between-class
+    variance (w0 S - N s0)^2 / (w0 (N - w0)), compared as exact fractions; ties go to the smallest t."""
+    h = [int(c) for c in counts]
+    N = sum(h)
+    if N == 0:
+        return 0
+    S = sum(v * c for v, c in enumerate(h))
+    best, bn, bd = None, 0, 1
+    w0 = s0 = 0
+    for t in range(255):
+        w0 += h[t]
+        s0 += t * h[t]
+        if 0 < w0 < N:
+            num, den = (w0 * S - N * s0) ** 2, w0 * (N - w0)
+            if best is None or num * bd > bn * den:
+                best, bn, bd = t, num, den
+    if best is None:                        # one value only: no t separates anything
+        return max(v for v, c in enumerate(h) if c)
+    return best
+
+
+def otsu_threshold(image, within=None):
+    """Otsu's global threshold of a uint8 [H, W] tensor on the GPU (``within``: as histogram): the integer t for which ``image > t``
+    is the foreground.  With h the histogram, N = sum h, S = sum v h[v], w0(t) = sum_{v <= t} h[v] and s0(t) = sum_{v <= t} v h[v], it
+    is the t in 0..254 with 0 < w0 < N that maximises (w0 S - N s0)^2 / (w0 (N - w0)) -- N^2 times the between-class variance.  The
+    comparison is made in Python integers as exact fractions (the numerator reaches 2^140: float64 would not define the result); ties
+    go to the smallest t, as skimage's first argmax.  A selection of one value returns that value (nothing is foreground), an empty
+    selection 0.
+
+    Host syncs: one, the read of the 256 counts."""
+    return _otsu(histogram(image, within).tolist())
+
+
+def smooth(image, radius):
+    """Binomial smoothing of a uint8 [H, W] tensor on the GPU (any strides): weights C(2 r, k) along each axis, the border replicated,
+    one rounding at the end (kernels.KernelSpec.binomial_smooth).  ``radius`` r: an integer in 0..5; 0 copies, 5 has standard deviation
+    1.58; larger blurs are repeated calls.  Returns uint8 [H, W].
+
+    Host syncs: none."""
+    _check_image('smooth', 'image', image, (torch.uint8,))
+    radius = _check_radius(radius)
+    with torch.cuda.device(image.device):
+        return kernels.get().binomial_smooth(image, radius)
+
+
+def stain_foreground(image, stain=0, radius=2, stains=None, order='bgr', within=None):
+    """From a stained tile to a foreground map: plane = smooth(separate_stains(image, stains, order, (stain,))[0], radius),
+    t = otsu_threshold(plane, within), fg = plane > t.  image: uint8 [H, W, 3] on the GPU; ``stain``: 0 haematoxylin (the nuclei),
+    1 eosin, 2 residual, of ``stains``; ``within`` (bool / integer [H, W]): the pixels the threshold is taken over, e.g. a tissue
+    mask -- fg is still defined everywhere.  Returns (fg bool [H, W], t, plane uint8 [H, W]).
+
+    The stage behind it:
+        L, n = split_touching(fill_holes(fg), None, markers='h_maxima', growth='flood', h=2.0)
+        features, centroids, kept = nucleus_features(L, bgr_to_gray(image), max_label=n)
+
+    Host syncs: one, that of otsu_threshold."""
+    _check_color('stain_foreground', image)
+    _check_planes((stain,))
+    if order not in STAIN_ORDERS:
+        raise ValueError("order must be 'bgr' or 'rgb', got %r" % (order,))
+    radius = _check_radius(radius)
+    _check_within('stain_foreground', within, image[:, :, 0])
+    plane = smooth(separate_stains(image, stains, order, (int(stain),))[0], radius)
+    t = otsu_threshold(plane, within)
+    return plane > t, t, plane
 
 
 def graph_item(features, centroids, y):

@@ -63,8 +63,9 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *  13: grayscale morphological reconstruction: cgc_reconstruct_ws_bytes, cgc_reconstruct_begin, cgc_reconstruct_rounds,
  *      cgc_reconstruct_finish
  *  14: seeded watershed flood: cgc_watershed_ws_bytes, cgc_watershed_begin, cgc_watershed_rounds, cgc_watershed_parents,
- *      cgc_watershed_jumps, cgc_watershed_finish */
-#define CGC_ABI_VERSION 14
+ *      cgc_watershed_jumps, cgc_watershed_finish
+ *  15: from an H&E tile to a foreground map: cgc_stain_separate, cgc_histogram_chunk_pixels, cgc_histogram_u8, cgc_binomial_smooth_u8 */
+#define CGC_ABI_VERSION 15
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -252,6 +253,33 @@ int cgc_watershed_rounds(int H, int W, int a, int b, int connectivity, void* ws,
 int cgc_watershed_parents(int H, int W, int a, int b, int connectivity, void* ws, cgc_stream_t stream);
 int cgc_watershed_jumps(int H, int W, void* ws, int jumps, int* changed, cgc_stream_t stream);
 int cgc_watershed_finish(int H, int W, const void* ws, int* level, int* source, cgc_stream_t stream);
+
+/* ---- F10 (in front of everything above): from a stained tile to the plane that is thresholded (csrc/stain.hip, csrc/smooth.hip).
+ * Replaces skimage.color.separate_stains / rgb2hed, a Gaussian blur and skimage.filters.threshold_otsu's histogram on the host; the
+ * contracts item by item: cgc-net_amd/kernels.py KernelSpec.stain_separate, histogram_u8, binomial_smooth.  All arithmetic is integer:
+ * every result is exact and a pure function of the input.  No workspace; pixel counts obey H * W < 2^31 (npix < 2^31).
+ *   cgc_stain_separate: colour deconvolution (Ruifrok and Johnston) in fixed point.  pix uint8 [npix, 3], interleaved; order 0: B, G, R
+ *     (what cgc_bgr_to_gray reads), 1: R, G, B.  lut (HOST, 256 int32): optical density in 1/1024 of a natural-log unit,
+ *     lut[v] = floor(1024 ln(255 / max(v, 1)) + 0.5), every entry in [0, 5674].  m (HOST, 9 int32, m[3 c + s], c = 0 R, 1 G, 2 B):
+ *     rint(4096 inv(S)[c][s]) for the stain matrix S whose rows are the unit OD vectors of the stains.  Both travel as kernel
+ *     arguments.  planes: bit s set = stain s is wanted (1..7); out uint8 [popcount(planes), npix], planar, ascending stain order:
+ *       C_s = lut[R] m[0][s] + lut[G] m[1][s] + lut[B] m[2][s] (int32);  out_s = clamp((C_s + 2^15) >> 16, 0, 255), arithmetic shift:
+ *     one level = 1 / 64 of a unit of natural-log concentration.  CGC_EINVAL, nothing launched: a NULL table, an order other than 0 / 1,
+ *     planes outside 1..7, a table entry outside [0, 5674], or a matrix with sum_c |m[c][s]| * 5674 >= 2^31 - 2^15 for some s (the
+ *     int32 sum could overflow: near-singular stains).  npix = 0: nothing is written.
+ *   cgc_histogram_u8: hist int32 [256] (device) = the number of pixels i with img[i] = v and within[i] != 0; within_or_null [npix] of
+ *     within_bytes = 1, 2, 4 or 8 bytes per pixel (only "is zero" is used), NULL: every pixel counts.  The entry zeroes hist itself
+ *     (an asynchronous fill), then one launch: a workgroup counts cgc_histogram_chunk_pixels() (16384) consecutive pixels in LDS and
+ *     adds its non-empty bins to hist with one atomic each.  npix = 0: hist is zeroed.
+ *   cgc_binomial_smooth_u8: img, out uint8 [H, W], radius r in 0..5, weights w_k = C(2 r, k), k = 0..2 r:
+ *       out[y, x] = (sum_i sum_j w_i w_j img[clamp(y + i - r, 0, H - 1), clamp(x + j - r, 0, W - 1)] + 2^(4 r - 1)) >> 4 r
+ *     (border replicated; one rounding; exact in int32 since 255 * 2^20 < 2^31; r = 0 copies).  The standard deviation is sqrt(r / 2):
+ *     1.58 at r = 5; larger blurs are repeated calls.  One launch; img and out must not overlap.  H * W = 0: nothing is written. */
+int cgc_stain_separate(const uint8_t* pix, int64_t npix, int order, const int* lut, const int* m, int planes, uint8_t* out,
+                       cgc_stream_t stream);
+int cgc_histogram_chunk_pixels(void);
+int cgc_histogram_u8(const uint8_t* img, int64_t npix, const void* within_or_null, int within_bytes, int* hist, cgc_stream_t stream);
+int cgc_binomial_smooth_u8(const uint8_t* img, int H, int W, int radius, uint8_t* out, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
