@@ -10,6 +10,7 @@ All float tensors are fp32, all index tensors int32 unless stated; "ld" = leadin
 elements of a row-major matrix.  Kernels never allocate and never synchronise.
 """
 import ctypes
+import functools
 import os
 
 import torch
@@ -22,8 +23,29 @@ EDT_MAX_SIDE = 32767       # 2 * 32766^2 < 2^31 - 1: squared distances fit int32
 GEO_INF = 2 ** 31 - 1      # CGC_GEO_INF: dist of a pixel that no seed reaches (within the bound)
 GEO_FIRST_BATCH, GEO_MAX_BATCH = 8, 64      # rounds of geodesic_transform per host read: 8, 16, 32, 64, 64, ...
 STAIN_OD_MAX = 5674        # floor(1024 ln 255 + 0.5): the largest optical density of stain_separate's table
+ANGLE_BINS = 1024          # K of angle_histogram: bins of the half turn (-pi/2, pi/2), separated by K - 1 directions
+ANGLE_E_MAX, ANGLE_E_REACH = 4096, 7095      # angle_histogram's basis: |E[j][c]| and sum_c |E[j][c]| (ceil(4096 sqrt 3))
+ANGLE_DIR_MAX = 16384      # angle_histogram's directions: |c_k|, |s_k|
 SMOOTH_MAX_RADIUS = 5      # binomial_smooth: 255 * 4^(2 * 5) < 2^31
 WS_JUMP_BATCH = 8          # pointer jumps of watershed_flood per host read: resolves parent chains of up to 2^7 pixels in one read
+
+
+@functools.lru_cache(maxsize=4)
+def _checked_dirs(dirs):
+    """angle_histogram's refusals of a direction table (a tuple of tuples: the check of nuclei.ANGLE_DIRS is made once): the flat
+    tuple c_1, s_1, c_2, s_2, ... of Python integers."""
+    try:
+        dirs = [[int(v) for v in d] for d in dirs]
+    except (TypeError, ValueError):
+        raise ValueError('angle_histogram: dirs must be %d x 2 integers' % (ANGLE_BINS - 1))
+    if len(dirs) != ANGLE_BINS - 1 or any(len(d) != 2 for d in dirs):
+        raise ValueError('angle_histogram: dirs must be %d x 2' % (ANGLE_BINS - 1))
+    if any(abs(c) > ANGLE_DIR_MAX or abs(s) > ANGLE_DIR_MAX for c, s in dirs):
+        raise ValueError('angle_histogram: every direction must lie in [-%d, %d]' % (ANGLE_DIR_MAX, ANGLE_DIR_MAX))
+    if any(c <= 0 for c, _ in dirs) or any(c0 * s1 - s0 * c1 <= 0 for (c0, s0), (c1, s1) in zip(dirs, dirs[1:])):
+        raise ValueError('angle_histogram: the directions must lie in the open right half plane (c > 0) with strictly increasing '
+                         'angles (c_k s_{k+1} - s_k c_{k+1} > 0): the bin is found by binary search')
+    return tuple(v for d in dirs for v in d)
 
 
 class KernelSpec(object):
@@ -265,6 +287,52 @@ class KernelSpec(object):
         4.  H * W = 0, or a within that selects nothing, gives zeros.
         Integer counts: the result does not depend on the order of the atomic adds.  A workgroup counts ``histogram_chunk`` (16384)
         consecutive pixels in LDS and flushes its non-empty bins once."""
+        raise NotImplementedError
+
+    def od_moments(self, image, order, lut, od_min, within=None):
+        """The first and second moments of the optical densities of a tile's stained pixels (stain estimation, Macenko et al. 2009;
+        csrc/stain.hip).  Returns int64 [10] on the device; no host read.  All arithmetic is integer: the result is exact and does not
+        depend on the order of accumulation.
+
+        1.  image, order, lut: as stain_separate -- uint8 [H, W, 3], any strides, H * W < 2^31; order 0: B, G, R, 1: R, G, B; lut: 256
+            integers in [0, 5674] (ValueError otherwise).
+        2.  within: as histogram_u8 -- None or [H, W] of a 1-, 2-, 4- or 8-byte integer type or bool, any strides; only "is zero" is
+            read.
+        3.  od_min: an integer in 0..5674 (ValueError otherwise, before any launch).
+        4.  With o = (lut[R], lut[G], lut[B]) a pixel is *selected* iff (within is None or within is non-zero there) and
+            lut[R] >= od_min and lut[G] >= od_min and lut[B] >= od_min.
+        5.  out = [n, sum oR, sum oG, sum oB, sum oR^2, sum oR oG, sum oR oB, sum oG^2, sum oG oB, sum oB^2] over the selected pixels.
+            Everything fits int64: 5674^2 * 2^31 < 2^63.
+        6.  H * W = 0, or nothing selected, gives zeros.
+        A lane adds at most 64 pixels in uint32 (64 * 5674^2 < 2^32); from the wave's reduction on the sums are 64 bits wide, and a
+        workgroup (``scan_chunk`` = 16384 consecutive pixels) adds its ten sums to the result with one 64-bit global atomic each."""
+        raise NotImplementedError
+
+    def angle_histogram(self, image, order, lut, od_min, basis, dirs, within=None):
+        """The histogram of the angles of a tile's stained pixels in a plane of optical-density space (stain estimation; csrc/stain.hip).
+        Returns int32 [K + 1] on the device, K = ANGLE_BINS = 1024; no host read.  All arithmetic is int32 and exact; no transcendental
+        function runs on the device.
+
+        1.  image, order, lut, od_min, within and the selection: exactly as od_moments.
+        2.  basis: 2 x 3 integers E[j][c], c = 0 R, 1 G, 2 B, |E[j][c]| <= 4096 and sum_c |E[j][c]| <= 7095 (= ceil(4096 sqrt 3)) for
+            each j (ValueError otherwise): 4096 times two unit vectors.
+        3.  For a selected pixel p_j = (sum_c o_c E[j][c] + 2^11) >> 12, an arithmetic shift in int32: |sum| <= 5674 * 7095 < 2^26,
+            so |p_j| <= 9829.
+        4.  dirs: (K - 1) x 2 integers (c_k, s_k), k = 1..K-1, each in [-16384, 16384] (ValueError otherwise); the host's table
+            (nuclei.ANGLE_DIRS) is (rint(16384 cos t_k), rint(16384 sin t_k)) with t_k = -pi/2 + k pi / K.
+        5.  A selected pixel with p_1 <= 0 is not binned: it adds one to out[K], the *skipped* counter.
+        6.  Every other selected pixel adds one to out[b], b = #{k : c_k p_2 - s_k p_1 >= 0}, 0 <= b <= K - 1.
+            |c_k p_2 - s_k p_1| <= 16384 * 2 * 9829 < 2^31.
+        7.  The refusal that makes a binary search equal the count: c_k > 0 for every k and c_k s_{k+1} - s_k c_{k+1} > 0 for
+            consecutive k (ValueError otherwise, before any launch; the library repeats it) -- the directions lie in the open right
+            half plane and their angles increase strictly.  For p_1 > 0 the sign of c_k p_2 - s_k p_1 is that of
+            sin(angle(p) - angle(d_k)) with both angles in (-pi/2, pi/2), so {k : ... >= 0} = {k : angle(d_k) <= angle(p)} is a prefix
+            and b is its size; the kernel finds it in 10 steps over the table in LDS.  A table that is not of this kind is refused, not
+            counted.
+        8.  H * W = 0, or nothing selected, gives zeros.
+        A workgroup counts ``scan_chunk`` consecutive pixels into 8 copies of the K + 1 counters in LDS (lane l on copy l mod 8,
+        bin-major; a run of equal bins among the 16 pixels a lane takes at a time is one add) and adds its non-empty bins to the result with one global atomic
+        each."""
         raise NotImplementedError
 
     def binomial_smooth(self, image, radius):
@@ -624,6 +692,9 @@ class HipKernels(KernelSpec):
         self._ws_cache = {}
         self._graph_local_max = int(self.lib.cgc_graph_local_max_nodes())
         self.histogram_chunk = int(self.lib.cgc_histogram_chunk_pixels())      # pixels one workgroup of histogram_u8 counts (tests)
+        self.scan_chunk = int(self.lib.cgc_scan_chunk_pixels())                # ... and of od_moments / angle_histogram
+        self._dirs_checked = (None, None)                                      # angle_histogram's last direction table and its C array
+        assert int(self.lib.cgc_angle_bins()) == ANGLE_BINS
 
     # -- helpers
     @staticmethod
@@ -958,6 +1029,76 @@ class HipKernels(KernelSpec):
                                             within.element_size() if within is not None else 0, _ptr(hist), self._stream()),
                   'cgc_histogram_u8')
         return hist
+
+    @staticmethod
+    def _check_scan_tables(fn, order, lut, od_min):
+        """The refusals od_moments and angle_histogram share, which need no tensor: returns lut as a list of Python integers."""
+        if order not in (0, 1):
+            raise ValueError('%s: order must be 0 (BGR) or 1 (RGB), got %r' % (fn, order))
+        lut = [int(v) for v in lut]
+        if len(lut) != 256 or min(lut) < 0 or max(lut) > STAIN_OD_MAX:
+            raise ValueError('%s: the optical-density table must hold 256 integers in [0, %d]' % (fn, STAIN_OD_MAX))
+        if isinstance(od_min, bool) or od_min not in range(0, STAIN_OD_MAX + 1):
+            raise ValueError('%s: od_min must be an integer in 0..%d, got %r' % (fn, STAIN_OD_MAX, od_min))
+        return lut
+
+    @staticmethod
+    def _check_basis(basis):
+        """The refusals of angle_histogram's basis: returns it as a flat list of Python integers."""
+        try:
+            basis = [[int(v) for v in row] for row in basis]
+        except (TypeError, ValueError):
+            raise ValueError('angle_histogram: the basis must be 2 x 3 integers')
+        if len(basis) != 2 or any(len(row) != 3 for row in basis):
+            raise ValueError('angle_histogram: the basis must be 2 x 3')
+        for row in basis:
+            if max(abs(v) for v in row) > ANGLE_E_MAX or sum(abs(v) for v in row) > ANGLE_E_REACH:
+                raise ValueError('angle_histogram: a basis row needs |E| <= %d and sum |E| <= %d (got %r)' % (ANGLE_E_MAX, ANGLE_E_REACH, row))
+        return [v for row in basis for v in row]
+
+    @staticmethod
+    def _check_angle_tables(basis, dirs):
+        """The refusals of angle_histogram's basis and directions, which need no tensor: returns both as flat lists of integers."""
+        basis = HipKernels._check_basis(basis)
+        try:
+            key = tuple(tuple(d) for d in dirs)
+        except TypeError:
+            raise ValueError('angle_histogram: dirs must be %d x 2 integers' % (ANGLE_BINS - 1))
+        return basis, list(_checked_dirs(key))
+
+    def _scan_images(self, image, within):
+        self._dev(image)
+        assert image.dtype == torch.uint8 and image.dim() == 3 and image.shape[2] == 3
+        assert within is None or tuple(within.shape) == tuple(image.shape[:2])
+        return image.contiguous(), self._image(within)
+
+    def od_moments(self, image, order, lut, od_min, within=None):
+        lut = HipKernels._check_scan_tables('od_moments', order, lut, od_min)
+        image, within = self._scan_images(image, within)
+        out = torch.empty(10, dtype=torch.int64, device=image.device)
+        self._chk(self.lib.cgc_od_moments(_ptr(image), ctypes.c_int64(image.shape[0] * image.shape[1]), int(order),
+                                          (ctypes.c_int * 256)(*lut), int(od_min), _ptr(within),
+                                          within.element_size() if within is not None else 0, _ptr(out), self._stream()), 'cgc_od_moments')
+        return out
+
+    def angle_histogram(self, image, order, lut, od_min, basis, dirs, within=None):
+        lut = HipKernels._check_scan_tables('angle_histogram', order, lut, od_min)
+        if self is not None and dirs is self._dirs_checked[0]:      # the same deeply immutable table as last time: checked, marshalled
+            basis, dirs_c = HipKernels._check_basis(basis), self._dirs_checked[1]
+        else:
+            basis, flat = HipKernels._check_angle_tables(basis, dirs)
+            dirs_c = (ctypes.c_int * len(flat))(*flat)
+            if self is not None and type(dirs) is tuple and all(type(d) is tuple and type(d[0]) is int and type(d[1]) is int for d in dirs):
+                self._dirs_checked = (dirs, dirs_c)
+        image, within = self._scan_images(image, within)
+        out = torch.empty(ANGLE_BINS + 1, dtype=torch.int32, device=image.device)
+        ws = torch.empty(int(self.lib.cgc_angle_histogram_ws_bytes()), dtype=torch.uint8, device=image.device)
+        self._chk(self.lib.cgc_angle_histogram(_ptr(image), ctypes.c_int64(image.shape[0] * image.shape[1]), int(order),
+                                               (ctypes.c_int * 256)(*lut), int(od_min), (ctypes.c_int * 6)(*basis),
+                                               dirs_c, _ptr(within),
+                                               within.element_size() if within is not None else 0, _ptr(ws), _ptr(out), self._stream()),
+                  'cgc_angle_histogram')
+        return out
 
     def binomial_smooth(self, image, radius):
         if radius not in range(0, SMOOTH_MAX_RADIUS + 1):

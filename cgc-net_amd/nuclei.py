@@ -27,7 +27,9 @@ unequal they are.
 haematoxylin plane (``separate_stains``; csrc/stain.hip, kernels.KernelSpec.stain_separate), a little binomial smoothing (``smooth``;
 csrc/smooth.hip) and Otsu's threshold of the plane's histogram (``histogram``, ``otsu_threshold``) -- all in integer arithmetic with a
 stated contract, so that the foreground map is a pure function of the tile.  Its output goes into ``fill_holes`` and
-``split_touching``.
+``split_touching``.  ``estimate_stains`` (Macenko et al. 2009) takes the stain vectors from the tile itself instead of the fixed
+``DEFAULT_STAINS`` -- two integer reductions on the device (kernels.KernelSpec.od_moments, angle_histogram), a 3 x 3 eigenproblem and
+two exact percentiles on the host: ``stain_foreground(tile, stains=estimate_stains(tile))``.
 
 ``nucleus_features(labels, gray)`` returns the reference's ``feature`` / ``coordinate`` arrays of one image (csrc/nuclei.hip; the
 arithmetic item by item: kernels.KernelSpec.nucleus_features), ``graph_item`` turns them into the ``Data`` that
@@ -39,8 +41,10 @@ Differences from the reference, all stated: an image without a surviving nucleus
 documented behaviour, not linked: see DESIGN.md, "Nucleus features".
 """
 import math
+import numbers
 import operator
 import os
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -528,6 +532,19 @@ OD_LUT = _od_lut()
 # unit OD vectors (R, G, B) of haematoxylin, eosin and a residual (Ruifrok and Johnston 2001; rows are normalised by stain_matrix)
 DEFAULT_STAINS = ((0.65, 0.70, 0.29), (0.07, 0.99, 0.11), (0.27, 0.57, 0.78))
 STAIN_ORDERS = {'bgr': 0, 'rgb': 1}
+ANGLE_BINS = kernels.ANGLE_BINS
+
+
+def _angle_dirs():
+    """The K - 1 directions that separate the K angle bins of estimate_stains: (rint(16384 cos t_k), rint(16384 sin t_k)) with
+    t_k = -pi/2 + k pi / K in float64, k = 1..K-1.  No entry lies within 1e-6 of a rounding boundary (the nearest is 4.0e-4 away) and
+    the angles of the rounded directions increase strictly (tests/test_macenko_ref_cpu.py), so every libm gives the same table."""
+    K = ANGLE_BINS
+    return tuple((int(round(16384.0 * math.cos(-0.5 * math.pi + k * math.pi / K))),
+                  int(round(16384.0 * math.sin(-0.5 * math.pi + k * math.pi / K)))) for k in range(1, K))
+
+
+ANGLE_DIRS = _angle_dirs()
 
 
 def stain_matrix(stains=None):
@@ -674,7 +691,8 @@ def stain_foreground(image, stain=0, radius=2, stains=None, order='bgr', within=
     """From a stained tile to a foreground map: plane = smooth(separate_stains(image, stains, order, (stain,))[0], radius),
     t = otsu_threshold(plane, within), fg = plane > t.  image: uint8 [H, W, 3] on the GPU; ``stain``: 0 haematoxylin (the nuclei),
     1 eosin, 2 residual, of ``stains``; ``within`` (bool / integer [H, W]): the pixels the threshold is taken over, e.g. a tissue
-    mask -- fg is still defined everywhere.  Returns (fg bool [H, W], t, plane uint8 [H, W]).
+    mask -- fg is still defined everywhere.  Returns (fg bool [H, W], t, plane uint8 [H, W]).  ``stains``: as stain_matrix -- None
+    for the fixed DEFAULT_STAINS, or the tile's own vectors: stain_foreground(image, stains=estimate_stains(image)).
 
     The stage behind it:
         L, n = split_touching(fill_holes(fg), None, markers='h_maxima', growth='flood', h=2.0)
@@ -690,6 +708,116 @@ def stain_foreground(image, stain=0, radius=2, stains=None, order='bgr', within=
     plane = smooth(separate_stains(image, stains, order, (int(stain),))[0], radius)
     t = otsu_threshold(plane, within)
     return plane > t, t, plane
+
+
+def _od_min(beta):
+    """The smallest integer k with k / 1024 >= beta (exact: beta as a Fraction)."""
+    if isinstance(beta, bool) or not isinstance(beta, numbers.Real) or not 0 <= beta <= Fraction(kernels.STAIN_OD_MAX, 1024):
+        raise ValueError('beta must be a number with 0 <= beta <= %d/1024 (got %r)' % (kernels.STAIN_OD_MAX, beta))
+    return int(math.ceil(Fraction(beta) * 1024))
+
+
+def _percentile_bins(bins, alpha):
+    """(b_lo, b_hi) of item 4 of estimate_stains, in exact arithmetic; sum(bins) > 0."""
+    a, M = Fraction(alpha), sum(bins)
+    b_lo = b_hi = None
+    cum = 0
+    for b, c in enumerate(bins):
+        cum += c
+        if b_lo is None and cum >= 1 and 100 * cum >= a * M:
+            b_lo = b
+        if b_hi is None and 100 * cum >= (100 - a) * M:
+            b_hi = b
+            break
+    return b_lo, b_hi
+
+
+def _plane_of_moments(mom):
+    """Item 2 of estimate_stains: (n, eigenvalues ascending, e_1, e_2) of the ten integer moments."""
+    n, s, q = mom[0], mom[1:4], mom[4:]
+    if n < 2:
+        raise ValueError('estimate_stains: too few stained pixels (%d): lower beta or widen within' % n)
+    q = ((q[0], q[1], q[2]), (q[1], q[3], q[4]), (q[2], q[4], q[5]))
+    C = np.array([[float(n * q[i][j] - s[i] * s[j]) for j in range(3)] for i in range(3)], np.float64)      # exact integers, then rounded once
+    lam, vec = np.linalg.eigh(C)
+    if not np.isfinite(lam[1]) or not lam[1] > 0:
+        raise ValueError('estimate_stains: the optical densities of the stained pixels lie on one line (one stain only): no plane')
+    e1, e2 = vec[:, 2].copy(), vec[:, 1].copy()
+    if e1.sum() < 0:
+        e1 = -e1
+    if e2[int(np.argmax(np.abs(e2)))] < 0:
+        e2 = -e2
+    return n, lam, e1, e2
+
+
+def _stains_of_bins(e1, e2, b_lo, b_hi):
+    """Item 5 of estimate_stains: the unit vectors of haematoxylin, eosin and the residual from the two percentile bins."""
+    v = []
+    for b in (b_lo, b_hi):
+        phi = -0.5 * math.pi + (b + 0.5) * math.pi / ANGLE_BINS
+        v.append(e1 * math.cos(phi) + e2 * math.sin(phi))
+    h, e = (v[0], v[1]) if v[0][0] > v[1][0] else (v[1], v[0])
+    S = np.stack([h, e, np.cross(h, e)])
+    norm = np.sqrt((S * S).sum(axis=1))
+    if not (norm > 0).all():
+        stain_matrix(S)                    # both percentiles in one bin: no residual; stain_matrix words the refusal
+    return S / norm[:, None]
+
+
+def estimate_stains(image, order='bgr', beta=0.15, alpha=1.0, within=None, return_info=False):
+    """A tile's own stain vectors by Macenko's method (Macenko et al. 2009), for stain_matrix, separate_stains and stain_foreground:
+    numpy float64 [3, 3], the rows the unit optical-density vectors (R, G, B) of haematoxylin, eosin and a residual.  image: uint8
+    [H, W, 3] on the GPU, any strides; ``order``: 'bgr' or 'rgb'; ``within`` (bool / integer [H, W]): the pixels that may be used, e.g.
+    a tissue mask.  The two passes over the tile are integer reductions with a stated contract (kernels.KernelSpec.od_moments,
+    angle_histogram), so the result is a pure function of the tile, of numpy's ``eigh`` and of the platform's cos and sin.
+
+    1.  od_min = the smallest integer k with k / 1024 >= beta (154 for 0.15): a pixel counts as stained when the optical densities
+        OD_LUT[.] of all three channels reach od_min.  ``beta`` must be a number with 0 <= beta <= 5674/1024 and ``alpha`` one with
+        0 <= alpha < 50 (ValueError otherwise).
+    2.  The ten moments n, s_i, q_ij of the stained pixels are read (host sync 1).  n < 2 raises ValueError ("too few stained
+        pixels").  In Python integers C[i][j] = n q_ij - s_i s_j, exactly n (n - 1) times the covariance; C goes to float64 and to
+        numpy.linalg.eigh.  e_1 = the eigenvector of the largest eigenvalue, its sign such that its components sum to a positive
+        number; e_2 = that of the second largest, its sign such that its component of largest magnitude is positive.  A second
+        eigenvalue <= 0 or not finite raises ValueError: one stain only, no plane.
+    3.  E[j][c] = rint(4096 e_j[c]); angle_histogram bins every stained pixel by the angle of its projection (p_1, p_2) on that plane
+        into K = 1024 bins of (-pi/2, pi/2), and the K + 1 counts are read (host sync 2).  M = the sum of the K bins; M = 0 raises
+        ValueError.  Pixels with p_1 <= 0 are not binned but counted (``skipped``).
+    4.  With a = Fraction(alpha) and cum(b) the running sum of the bins, in exact arithmetic: b_lo = the smallest b with cum(b) >= 1
+        and 100 cum(b) >= a M; b_hi = the smallest b with 100 cum(b) >= (100 - a) M.  phi = -pi/2 + (b + 1/2) pi / K, the bin's centre.
+    5.  v_lo = e_1 cos phi_lo + e_2 sin phi_lo and v_hi likewise, from the float64 eigenvectors.  The one with the larger R component
+        is haematoxylin, the other eosin, their cross product the residual; all three are normalised.  If stain_matrix would refuse
+        the result its ValueError is raised.
+    6.  ``return_info``: also a dict with n, skipped, od_min, bins = (b_lo, b_hi) and eigenvalues = the three eigenvalues of C in
+        ascending order, each divided by n (n - 1) -- those of the covariance of the optical densities in units of 1/1024.
+
+        S = estimate_stains(tile)
+        fg, t, plane = stain_foreground(tile, stains=S)
+
+    Host syncs: two, the read of the ten moments and the read of the K + 1 counts."""
+    _check_color('estimate_stains', image)
+    if order not in STAIN_ORDERS:
+        raise ValueError("order must be 'bgr' or 'rgb', got %r" % (order,))
+    od_min = _od_min(beta)
+    if isinstance(alpha, bool) or not isinstance(alpha, numbers.Real) or not 0 <= alpha < 50:
+        raise ValueError('alpha must be a number with 0 <= alpha < 50 (got %r)' % (alpha,))
+    _check_within('estimate_stains', within, image[:, :, 0])
+    if image.shape[0] * image.shape[1] == 0:
+        raise ValueError('estimate_stains: too few stained pixels (0): the image is empty')
+    with torch.cuda.device(image.device):
+        table = kernels.get()
+        mom = table.od_moments(image, STAIN_ORDERS[order], OD_LUT, od_min, within).tolist()
+        n, lam, e1, e2 = _plane_of_moments(mom)
+        basis = [[int(v) for v in np.rint(4096.0 * e)] for e in (e1, e2)]
+        counts = table.angle_histogram(image, STAIN_ORDERS[order], OD_LUT, od_min, basis, ANGLE_DIRS, within).tolist()
+    bins, skipped = counts[:ANGLE_BINS], counts[ANGLE_BINS]
+    if sum(bins) == 0:
+        raise ValueError('estimate_stains: no stained pixel lies on the positive side of the first principal direction')
+    b_lo, b_hi = _percentile_bins(bins, alpha)
+    S = _stains_of_bins(e1, e2, b_lo, b_hi)
+    stain_matrix(S)                        # its refusals are this function's
+    if return_info:
+        return S, dict(n=n, skipped=skipped, od_min=od_min, bins=(b_lo, b_hi), eigenvalues=tuple(float(v) / (n * (n - 1)) for v in lam))
+    return S
 
 
 def graph_item(features, centroids, y):

@@ -64,8 +64,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *      cgc_reconstruct_finish
  *  14: seeded watershed flood: cgc_watershed_ws_bytes, cgc_watershed_begin, cgc_watershed_rounds, cgc_watershed_parents,
  *      cgc_watershed_jumps, cgc_watershed_finish
- *  15: from an H&E tile to a foreground map: cgc_stain_separate, cgc_histogram_chunk_pixels, cgc_histogram_u8, cgc_binomial_smooth_u8 */
-#define CGC_ABI_VERSION 15
+ *  15: from an H&E tile to a foreground map: cgc_stain_separate, cgc_histogram_chunk_pixels, cgc_histogram_u8, cgc_binomial_smooth_u8
+ *  16: a tile's own stain vectors (Macenko): cgc_scan_chunk_pixels, cgc_od_moments, cgc_angle_bins, cgc_angle_histogram_ws_bytes,
+ *      cgc_angle_histogram */
+#define CGC_ABI_VERSION 16
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -280,6 +282,35 @@ int cgc_stain_separate(const uint8_t* pix, int64_t npix, int order, const int* l
 int cgc_histogram_chunk_pixels(void);
 int cgc_histogram_u8(const uint8_t* img, int64_t npix, const void* within_or_null, int within_bytes, int* hist, cgc_stream_t stream);
 int cgc_binomial_smooth_u8(const uint8_t* img, int H, int W, int radius, uint8_t* out, cgc_stream_t stream);
+
+/* ---- F11 (beside F10): the two reductions behind an estimate of a tile's own stain vectors (Macenko et al. 2009; csrc/stain.hip;
+ * cgc-net_amd/nuclei.py estimate_stains).  The contracts item by item: cgc-net_amd/kernels.py KernelSpec.od_moments, angle_histogram.
+ * pix, npix, order and lut (HOST) are those of cgc_stain_separate, within_or_null and within_bytes those of cgc_histogram_u8.  With
+ * o = (lut[R], lut[G], lut[B]) a pixel is SELECTED iff within is NULL or non-zero there and o_R, o_G, o_B >= od_min (0..5674).  All
+ * arithmetic is integer; every result is exact and independent of the order of the adds.  A workgroup takes cgc_scan_chunk_pixels()
+ * (16384) consecutive pixels and adds to the result once.  Each entry zeroes its result itself (an asynchronous fill); npix = 0 or an
+ * empty selection leaves zeros.
+ *   cgc_od_moments: out int64 [10] (device) = n, sum o_R, sum o_G, sum o_B, sum o_R^2, sum o_R o_G, sum o_R o_B, sum o_G^2, sum o_G o_B,
+ *     sum o_B^2 over the selected pixels (5674^2 * 2^31 < 2^63).  One launch.
+ *   cgc_angle_histogram: out int32 [K + 1] (device), K = cgc_angle_bins() = 1024.  basis (HOST, 6 int32, E[j][c] = basis[3 j + c],
+ *     c = 0 R, 1 G, 2 B): |E[j][c]| <= 4096 and sum_c |E[j][c]| <= 7095 for j = 0, 1.  p_j = (sum_c o_c E[j][c] + 2^11) >> 12 (int32,
+ *     arithmetic shift), so |p_j| <= 9829.  dirs (HOST, (K - 1) x 2 int32: c_k, s_k for k = 1 .. K - 1): 0 < c_k <= 16384,
+ *     |s_k| <= 16384 and c_k s_{k+1} - s_k c_{k+1} > 0 -- directions in the open right half plane whose angles increase strictly.  A
+ *     selected pixel with p_1 <= 0 adds one to out[K] (skipped); every other selected pixel adds one to out[b],
+ *     b = #{k : c_k p_2 - s_k p_1 >= 0} (|c_k p_2 - s_k p_1| <= 2 * 16384 * 9829 < 2^31).  For a table that passes the check that set is
+ *     a prefix of 1 .. K - 1 and the kernel finds b by binary search; any other table is refused.  ws: cgc_angle_histogram_ws_bytes()
+ *     (4096) bytes on the device, 256-byte aligned: the entry puts the packed table there (two small launches whose kernel arguments
+ *     carry it), then one launch.
+ * CGC_EINVAL, nothing launched: npix outside [0, 2^31), an order other than 0 / 1, a NULL table, basis, dirs or out, a table entry
+ * outside [0, 5674], od_min outside [0, 5674], within_bytes other than 1, 2, 4, 8 with a within, a basis or a direction outside the
+ * bounds above, directions that do not turn left; with npix > 0 also a NULL pix or ws. */
+int cgc_scan_chunk_pixels(void);
+int cgc_od_moments(const uint8_t* pix, int64_t npix, int order, const int* lut, int od_min, const void* within_or_null, int within_bytes,
+                   int64_t* out, cgc_stream_t stream);
+int cgc_angle_bins(void);
+int64_t cgc_angle_histogram_ws_bytes(void);
+int cgc_angle_histogram(const uint8_t* pix, int64_t npix, int order, const int* lut, int od_min, const int* basis, const int* dirs,
+                        const void* within_or_null, int within_bytes, void* ws, int* out, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
