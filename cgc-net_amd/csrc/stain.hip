@@ -7,16 +7,23 @@
 //      lane on one bin -- is the worst case, so (a) a lane reads 16 consecutive pixels and adds a run of equal values with ONE LDS atomic,
 //      and (b) every wave owns HIST_COPIES copies of the table, lane l using copy l % HIST_COPIES, laid out bin-major so that the
 //      copies of one bin sit on different banks.  A flat tile then costs one atomic per 16 pixels and 8 lanes per address.
-//   3. k_od_scan<ANGLE>: the two reductions of stain estimation (Macenko) over the pixels whose optical densities all reach od_min.
-//      One template, two bodies, the same loads as kernel 1 and the same OD table in LDS; a workgroup takes SCAN_CHUNK consecutive
-//      pixels, 4 per lane and step, and flushes once.  ANGLE = false: the ten moments n, sum o_c, sum o_c o_d.  A lane meets at most
+//   3. k_od_scan<MODE>: the reductions of stain estimation and normalisation (Macenko) over the pixels whose optical densities all
+//      reach od_min.  One template, three bodies, the same loads as kernel 1 and the same OD table in LDS; a workgroup takes
+//      SCAN_CHUNK consecutive pixels, 4 per lane and step, and flushes once.  SCAN_MOMENTS: the ten moments n, sum o_c, sum o_c o_d.  A lane meets at most
 //      64 pixels, so its sums fit uint32 (64 * 5674^2 < 2^32); they are widened to 64 bits before the wave's shuffles, and ten lanes
-//      add the workgroup's sums to the result with one vector 64-bit global atomic each.  ANGLE = true: every pixel is projected on
+//      add the workgroup's sums to the result with one vector 64-bit global atomic each.  SCAN_ANGLE: every pixel is projected on
 //      a plane (two int32 dot products, rounded) and binned by the side of ANGLE_BINS - 1 directions it lies on -- ten steps of a
 //      binary search over the table in LDS, integer cross products only.  Counters as in kernel 2: ANGLE_COPIES copies per
 //      workgroup, bin-major, lane l on copy l % ANGLE_COPIES, and a lane adds a run of equal bins among the 16 pixels of a batch with
-//      one atomic.  The loads of SCAN_BATCH steps are issued together and their 16 searches run side by side.
-// The arithmetic, item by item: kernels.py KernelSpec.stain_separate / histogram_u8 / od_moments / angle_histogram.
+//      one atomic.  The loads of SCAN_BATCH steps are issued together and their 16 searches run side by side.  SCAN_CONC: the
+//      concentrations of the first two stains (two int32 dot products each, rounded to 1/128 of a unit and clamped to CONC_BINS
+//      levels) into 2 * CONC_BINS counters kept exactly as SCAN_ANGLE keeps its own, one open run per stain.
+//   4. k_od_recolor: a 3 x 3 map in optical-density space and back to bytes.  Loads as kernel 1, stores their mirror image (three
+//      dwords per lane, bytes on the tail); the OD table and the 6386-entry exponential table (as bytes, 6.4 KB) sit in LDS, the
+//      matrix in scalar registers.  The exponential table is too large for kernel arguments: k_put_words carries it, as it carries
+//      SCAN_ANGLE's directions, in two pieces of 3.2 KB into the caller's workspace, from where every workgroup copies it to LDS.
+// The arithmetic, item by item: kernels.py KernelSpec.stain_separate / histogram_u8 / od_moments / angle_histogram /
+// concentration_histogram / od_recolor.
 #include <stdint.h>
 
 #include "common.hpp"
@@ -38,7 +45,17 @@
 #define ANGLE_E_MAX 4096              // |E[j][c]|
 #define ANGLE_E_REACH 7095            // sum_c |E[j][c]|: ceil(4096 sqrt 3)
 #define ANGLE_DIR_MAX 16384           // |c_k|, |s_k|
-#define ANGLE_PUT 512                 // directions one k_put_dirs launch carries as kernel arguments
+#define PUT_WORDS 800                 // dwords one k_put_words launch carries as kernel arguments: 3.2 KB of the 4 KB there are
+#define CONC_BINS 512                 // levels of one stain's concentration: 1/128 of a natural-log unit each, the last one open
+#define EXP_LEN 6386                  // entries of the exponential table: floor(255 exp(-k / 1024) + 0.5) first reaches 0 at k = 6385
+#define EXP_WORDS 1600                // the table as bytes, four to a dword, padded with zeros to whole 256-byte rows
+#define RECOLOR_THREADS 256
+#define RECOLOR_MAX_BLOCKS 2048       // 8 workgroups per CU: each copies 7.4 KB of tables to LDS once and strides over the tile
+enum { SCAN_MOMENTS = 0, SCAN_ANGLE = 1, SCAN_CONC = 2 };
+static_assert(4 * EXP_WORDS >= EXP_LEN && EXP_WORDS % 64 == 0, "the padded table holds every entry");
+static_assert(PUT_WORDS <= 1024 && 4 * PUT_WORDS + 64 <= 4096 && EXP_WORDS <= 2 * PUT_WORDS && ANGLE_BINS - 1 <= 2 * PUT_WORDS,
+              "a piece is one workgroup and fits the kernel arguments; either table is two pieces");
+static_assert(2 * CONC_BINS <= ANGLE_BINS + 1, "the concentration counters fit the LDS the angle counters take");
 static_assert(SCAN_STEPS % SCAN_BATCH == 0, "whole batches");
 static_assert((uint64_t)SCAN_STEPS * 4 * STAIN_OD_MAX * STAIN_OD_MAX < ((uint64_t)1 << 32), "a lane's sums of products fit uint32");
 static_assert((int64_t)STAIN_OD_MAX * ANGLE_E_REACH + 2048 < ((int64_t)1 << 26), "a projection fits 26 bits before the shift");
@@ -164,12 +181,12 @@ struct ScanTables {                    // passed by value: 1052 bytes of kernel 
   int e[6];                            // e[3 * j + c]: channel c (0 R, 1 G, 2 B) -> axis j of the plane (ANGLE only)
 };
 
-struct DirsPiece {                     // ANGLE_PUT packed directions: (c & 0xffff) | (s << 16)
-  uint32_t d[ANGLE_PUT];
+struct WordsPiece {                    // PUT_WORDS dwords of a table: packed directions (c & 0xffff) | (s << 16), or four bytes of exp_lut
+  uint32_t d[PUT_WORDS];
 };
 
-// table[first + i] = piece.d[i]: the direction table travels as kernel arguments, in pieces of 2 KB, into the caller's workspace.
-__global__ __launch_bounds__(ANGLE_PUT) void k_put_dirs(const DirsPiece piece, int first, int count, uint32_t* __restrict__ table) {
+// table[first + i] = piece.d[i]: a host table travels as kernel arguments, in pieces of 3.2 KB, into the caller's workspace.
+__global__ __launch_bounds__(PUT_WORDS) void k_put_words(const WordsPiece piece, int first, int count, uint32_t* __restrict__ table) {
   if ((int)threadIdx.x < count) table[first + threadIdx.x] = piece.d[threadIdx.x];
 }
 
@@ -196,23 +213,26 @@ __device__ __forceinline__ int dot2_i16(uint32_t a, uint32_t b, int c) {
   return __builtin_amdgcn_sdot2(x, y, c, false);
 }
 
-// One workgroup reduces the pixels [blockIdx.x * SCAN_CHUNK, + SCAN_CHUNK) and adds what it found to `out`: ANGLE ? int32
-// [ANGLE_BINS + 1] (bins, then the skipped counter) : int64 [10] (moments).  dirs: ANGLE_BINS packed directions, entry 0 unused.
-template <bool ANGLE>
+// One workgroup reduces the pixels [blockIdx.x * SCAN_CHUNK, + SCAN_CHUNK) and adds what it found to `out`: SCAN_MOMENTS int64 [10];
+// SCAN_ANGLE int32 [ANGLE_BINS + 1] (bins, then the skipped counter); SCAN_CONC int32 [2 * CONC_BINS] (stain 0, then stain 1).
+// dirs: ANGLE_BINS packed directions, entry 0 unused (SCAN_ANGLE only).  t.e: SCAN_ANGLE the basis, SCAN_CONC two columns of m.
+template <int MODE>
 __global__ __launch_bounds__(SCAN_THREADS) void k_od_scan(const uint8_t* __restrict__ pix, int64_t npix, int order, const ScanTables t,
                                                           const void* __restrict__ within, int within_bytes,
                                                           const uint32_t* __restrict__ dirs, void* __restrict__ out) {
+  constexpr bool ANGLE = MODE == SCAN_ANGLE, CONC = MODE == SCAN_CONC;
+  constexpr int COUNTERS = ANGLE ? ANGLE_BINS + 1 : (CONC ? 2 * CONC_BINS : 0);      // 0: sums, no counters
   __shared__ int lut[256];
   __shared__ uint32_t dir[ANGLE ? ANGLE_BINS : 1];
-  __shared__ int tab[ANGLE ? (ANGLE_BINS + 1) * ANGLE_COPIES : 1];
-  __shared__ unsigned long long part[ANGLE ? 1 : SCAN_THREADS / 64][10];
+  __shared__ int tab[COUNTERS > 0 ? COUNTERS * ANGLE_COPIES : 1];
+  __shared__ unsigned long long part[COUNTERS > 0 ? 1 : SCAN_THREADS / 64][10];
   for (int i = threadIdx.x; i < 256; i += SCAN_THREADS) lut[i] = t.lut[i];
-  if constexpr (ANGLE) {
+  if constexpr (ANGLE)
     for (int i = threadIdx.x; i < ANGLE_BINS; i += SCAN_THREADS) dir[i] = i > 0 ? dirs[i] : 0u;
-    for (int i = threadIdx.x; i < (ANGLE_BINS + 1) * ANGLE_COPIES; i += SCAN_THREADS) tab[i] = 0;
-  }
+  if constexpr (COUNTERS > 0)
+    for (int i = threadIdx.x; i < COUNTERS * ANGLE_COPIES; i += SCAN_THREADS) tab[i] = 0;
   __syncthreads();
-  int* mine = &tab[ANGLE ? threadIdx.x & (ANGLE_COPIES - 1) : 0];      // bin b of this lane's copy: mine[b * ANGLE_COPIES]
+  int* mine = &tab[COUNTERS > 0 ? threadIdx.x & (ANGLE_COPIES - 1) : 0];      // bin b of this lane's copy: mine[b * ANGLE_COPIES]
   uint32_t acc[10] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};          // moments: n, sR, sG, sB, RR, RG, RB, GG, GB, BB of this lane
   int skipped = 0;
   const bool in_dwords = (reinterpret_cast<uintptr_t>(pix) & 3u) == 0;
@@ -229,7 +249,33 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_od_scan(const uint8_t* __restr
       load_pixels4(pix, npix, i0, n == 4 && in_dwords, w[u]);
       live[u] = ((1u << n) - 1u) & (within == nullptr ? 15u : nonzero4(within, within_bytes, i0, n));
     }
-    if constexpr (!ANGLE) {
+    if constexpr (CONC) {
+      int cur[2] = {-1, -1}, run[2] = {0, 0};      // the open run of equal bins, per stain
+#pragma unroll
+      for (int q = 0; q < 4 * SCAN_BATCH; ++q) {
+        const uint32_t* wq = w[q >> 2];
+        const int j = q & 3;
+        const int c0 = pixel_byte(wq, 3 * j), c1 = pixel_byte(wq, 3 * j + 1), c2 = pixel_byte(wq, 3 * j + 2);
+        const int odr = lut[order == 0 ? c2 : c0], odg = lut[c1], odb = lut[order == 0 ? c0 : c2];
+        const bool sel = ((live[q >> 2] >> j) & 1u) != 0 && min(min(odr, odg), odb) >= t.od_min;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          // |m| < 2^23 and every product and sum fits int32 (the entry's refusal): the 24-bit multiplies are exact
+          const int c = __mul24(odr, t.e[3 * s]) + __mul24(odg, t.e[3 * s + 1]) + __mul24(odb, t.e[3 * s + 2]);
+          const int v = sel ? CONC_BINS * s + min(max((c + 16384) >> 15, 0), CONC_BINS - 1) : -1;
+          if (v == cur[s]) {
+            ++run[s];
+          } else {
+            if (cur[s] >= 0) atomicAdd(&mine[cur[s] * ANGLE_COPIES], run[s]);
+            cur[s] = v;
+            run[s] = 1;
+          }
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+        if (cur[s] >= 0) atomicAdd(&mine[cur[s] * ANGLE_COPIES], run[s]);
+    } else if constexpr (!ANGLE) {
 #pragma unroll
       for (int q = 0; q < 4 * SCAN_BATCH; ++q) {
         const uint32_t* wq = w[q >> 2];
@@ -293,11 +339,12 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_od_scan(const uint8_t* __restr
       if (cur >= 0) atomicAdd(&mine[cur * ANGLE_COPIES], run);
     }
   }
-  if constexpr (ANGLE) {
-    if (skipped != 0) atomicAdd(&mine[ANGLE_BINS * ANGLE_COPIES], skipped);
+  if constexpr (COUNTERS > 0) {
+    if constexpr (ANGLE)
+      if (skipped != 0) atomicAdd(&mine[ANGLE_BINS * ANGLE_COPIES], skipped);
     __syncthreads();
     int* hist = static_cast<int*>(out);
-    for (int b = threadIdx.x; b <= ANGLE_BINS; b += SCAN_THREADS) {
+    for (int b = threadIdx.x; b < COUNTERS; b += SCAN_THREADS) {
       int total = 0;
       for (int c = 0; c < ANGLE_COPIES; ++c) total += tab[b * ANGLE_COPIES + c];
       if (total != 0) atomicAdd(&hist[b], total);
@@ -318,9 +365,83 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_od_scan(const uint8_t* __restr
   }
 }
 
+// out[i][d] = exp_lut[clamp((sum_c lut[v_c] a[c][d] + 2^11) >> 12, 0, EXP_LEN - 1)], in the channel order of the input.  t.m holds a.
+// exp_words: the table as bytes, EXP_WORDS dwords (k_put_words wrote them).
+__global__ __launch_bounds__(RECOLOR_THREADS) void k_od_recolor(const uint8_t* __restrict__ pix, int64_t npix, int order, const StainTables t,
+                                                                const uint32_t* __restrict__ exp_words, uint8_t* __restrict__ out) {
+  __shared__ int lut[256];
+  __shared__ uint32_t exp_tab[EXP_WORDS];
+  for (int i = threadIdx.x; i < 256; i += RECOLOR_THREADS) lut[i] = t.lut[i];
+  for (int i = threadIdx.x; i < EXP_WORDS; i += RECOLOR_THREADS) exp_tab[i] = exp_words[i];
+  __syncthreads();
+  const uint8_t* exp_lut = reinterpret_cast<const uint8_t*>(exp_tab);
+  const bool in_dwords = (reinterpret_cast<uintptr_t>(pix) & 3u) == 0, out_dwords = (reinterpret_cast<uintptr_t>(out) & 3u) == 0;
+  const int64_t groups = (npix + 3) >> 2;
+  for (int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; g < groups; g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i0 = 4 * g;
+    const bool full = i0 + 4 <= npix;
+    uint32_t w[3];
+    load_pixels4(pix, npix, i0, full && in_dwords, w);
+    uint32_t packed[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      int ch[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) ch[k] = pixel_byte(w, 3 * j + k);
+      const int odr = lut[order == 0 ? ch[2] : ch[0]], odg = lut[ch[1]], odb = lut[order == 0 ? ch[0] : ch[2]];
+      uint32_t lev[3];                 // the output channels R, G, B
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        // |a| < 2^23 and every product and sum fits int32 (the entry's refusal): the 24-bit multiplies are exact
+        const int o = __mul24(odr, t.m[d]) + __mul24(odg, t.m[3 + d]) + __mul24(odb, t.m[6 + d]);
+        lev[d] = exp_lut[min(max((o + 2048) >> 12, 0), EXP_LEN - 1)];
+      }
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int b = 3 * j + k;       // byte b of the 12: channel k of pixel j, R and B swapped for the BGR order
+        packed[b >> 2] |= (order == 0 ? lev[2 - k] : lev[k]) << (8 * (b & 3));
+      }
+    }
+    uint8_t* o = out + 3 * i0;
+    if (full && out_dwords) {
+      uint32_t* p = reinterpret_cast<uint32_t*>(o);
+      p[0] = packed[0];
+      p[1] = packed[1];
+      p[2] = packed[2];
+    } else {
+      const int64_t nbytes = 3 * (npix - i0) < 12 ? 3 * (npix - i0) : 12;
+      for (int k = 0; k < 12; ++k)
+        if (k < nbytes) o[k] = (uint8_t)(packed[k >> 2] >> (8 * (k & 3)));
+    }
+  }
+}
+
 }  // namespace
 
 static inline bool bad_pixel_count(int64_t npix) { return npix < 0 || npix >= ((int64_t)1 << 31); }      // bad_image_dims, for a flat count
+
+// No int32 sum over a column of a 3 x 3 matrix of optical densities may overflow, its rounding term included:
+// sum_c |m[c][s]| * 5674 < 2^31 - slack for every column s.
+static bool bad_od_matrix(const int* m, int64_t slack) {
+  for (int s = 0; s < 3; ++s) {
+    int64_t reach = 0;
+    for (int c = 0; c < 3; ++c) reach += (m[3 * c + s] < 0 ? -(int64_t)m[3 * c + s] : (int64_t)m[3 * c + s]) * STAIN_OD_MAX;
+    if (reach >= ((int64_t)1 << 31) - slack) return true;
+  }
+  return false;
+}
+
+// table[first + i] = words[i], i < n, on the stream: ceil(n / PUT_WORDS) launches of k_put_words.
+static int put_words(const uint32_t* words, int first, int n, uint32_t* table, hipStream_t st) {
+  for (int at = 0; at < n; at += PUT_WORDS) {
+    WordsPiece piece;
+    const int count = n - at < PUT_WORDS ? n - at : PUT_WORDS;
+    for (int i = 0; i < PUT_WORDS; ++i) piece.d[i] = i < count ? words[at + i] : 0u;
+    hipLaunchKernelGGL(k_put_words, dim3(1), dim3(PUT_WORDS), 0, st, piece, first + at, count, table);
+    CGC_RETURN_IF_LAUNCH_FAILED();
+  }
+  return 0;
+}
 
 extern "C" int cgc_stain_separate(const uint8_t* pix, int64_t npix, int order, const int* lut, const int* m, int planes, uint8_t* out,
                                   cgc_stream_t stream) {
@@ -331,11 +452,7 @@ extern "C" int cgc_stain_separate(const uint8_t* pix, int64_t npix, int order, c
     if (lut[v] < 0 || lut[v] > STAIN_OD_MAX) return CGC_EINVAL;
     t.lut[v] = lut[v];
   }
-  for (int s = 0; s < 3; ++s) {        // no int32 sum may overflow: sum_c |m[c][s]| * 5674 < 2^31 - 2^15
-    int64_t reach = 0;
-    for (int c = 0; c < 3; ++c) reach += (m[3 * c + s] < 0 ? -(int64_t)m[3 * c + s] : (int64_t)m[3 * c + s]) * STAIN_OD_MAX;
-    if (reach >= ((int64_t)1 << 31) - 32768) return CGC_EINVAL;
-  }
+  if (bad_od_matrix(m, 32768)) return CGC_EINVAL;
   for (int k = 0; k < 9; ++k) t.m[k] = m[k];
   if (npix == 0) return 0;
   if (pix == nullptr || out == nullptr) return CGC_EINVAL;
@@ -388,7 +505,7 @@ extern "C" int cgc_od_moments(const uint8_t* pix, int64_t npix, int order, const
   const hipError_t e = hipMemsetAsync(out, 0, 10 * sizeof(int64_t), st);
   if (e != hipSuccess) return (int)e;
   if (npix == 0) return 0;
-  hipLaunchKernelGGL(k_od_scan<false>, dim3((int)ceil_div64(npix, SCAN_CHUNK)), dim3(SCAN_THREADS), 0, st, pix, npix, order, t,
+  hipLaunchKernelGGL(k_od_scan<SCAN_MOMENTS>, dim3((int)ceil_div64(npix, SCAN_CHUNK)), dim3(SCAN_THREADS), 0, st, pix, npix, order, t,
                      within_or_null, within_bytes, (const uint32_t*)nullptr, (void*)out);
   CGC_RETURN_IF_LAUNCH_FAILED();
   return 0;
@@ -426,16 +543,66 @@ extern "C" int cgc_angle_histogram(const uint8_t* pix, int64_t npix, int order, 
   if (e != hipSuccess) return (int)e;
   if (npix == 0) return 0;
   uint32_t* table = static_cast<uint32_t*>(ws);      // entry k = direction k; entry 0 is never read
-  for (int first = 1; first < ANGLE_BINS; first += ANGLE_PUT) {
-    DirsPiece piece;
-    const int count = ANGLE_BINS - first < ANGLE_PUT ? ANGLE_BINS - first : ANGLE_PUT;
-    for (int i = 0; i < ANGLE_PUT; ++i)
-      piece.d[i] = i < count ? ((uint32_t)dirs[2 * (first - 1 + i)] & 0xffffu) | (uint32_t)dirs[2 * (first - 1 + i) + 1] << 16 : 0u;
-    hipLaunchKernelGGL(k_put_dirs, dim3(1), dim3(ANGLE_PUT), 0, st, piece, first, count, table);
-    CGC_RETURN_IF_LAUNCH_FAILED();
-  }
-  hipLaunchKernelGGL(k_od_scan<true>, dim3((int)ceil_div64(npix, SCAN_CHUNK)), dim3(SCAN_THREADS), 0, st, pix, npix, order, t,
+  uint32_t packed[ANGLE_BINS - 1];
+  for (int k = 0; k < ANGLE_BINS - 1; ++k) packed[k] = ((uint32_t)dirs[2 * k] & 0xffffu) | (uint32_t)dirs[2 * k + 1] << 16;
+  const int put = put_words(packed, 1, ANGLE_BINS - 1, table, st);
+  if (put != 0) return put;
+  hipLaunchKernelGGL(k_od_scan<SCAN_ANGLE>, dim3((int)ceil_div64(npix, SCAN_CHUNK)), dim3(SCAN_THREADS), 0, st, pix, npix, order, t,
                      within_or_null, within_bytes, (const uint32_t*)table, (void*)out);
+  CGC_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}
+
+extern "C" int cgc_concentration_bins(void) { return CONC_BINS; }
+
+extern "C" int cgc_concentration_histogram(const uint8_t* pix, int64_t npix, int order, const int* lut, int od_min, const int* m,
+                                           const void* within_or_null, int within_bytes, int* out, cgc_stream_t stream) {
+  ScanTables t;
+  if (bad_scan_args(npix, order, lut, od_min, within_or_null, within_bytes, out, t) || m == nullptr || bad_od_matrix(m, 32768))
+    return CGC_EINVAL;
+  for (int s = 0; s < 2; ++s)
+    for (int c = 0; c < 3; ++c) t.e[3 * s + c] = m[3 * c + s];
+  if (npix > 0 && pix == nullptr) return CGC_EINVAL;
+  hipStream_t st = as_stream(stream);
+  const hipError_t e = hipMemsetAsync(out, 0, 2 * CONC_BINS * sizeof(int), st);
+  if (e != hipSuccess) return (int)e;
+  if (npix == 0) return 0;
+  hipLaunchKernelGGL(k_od_scan<SCAN_CONC>, dim3((int)ceil_div64(npix, SCAN_CHUNK)), dim3(SCAN_THREADS), 0, st, pix, npix, order, t,
+                     within_or_null, within_bytes, (const uint32_t*)nullptr, (void*)out);
+  CGC_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}
+
+extern "C" int cgc_exp_lut_len(void) { return EXP_LEN; }
+extern "C" int64_t cgc_od_recolor_ws_bytes(void) { return EXP_WORDS * (int64_t)sizeof(uint32_t); }
+
+extern "C" int cgc_od_recolor(const uint8_t* pix, int64_t npix, int order, const int* lut, const int* a, const int* exp_lut, int exp_len,
+                              void* ws, uint8_t* out, cgc_stream_t stream) {
+  if (bad_pixel_count(npix) || (order != 0 && order != 1) || lut == nullptr || a == nullptr || exp_lut == nullptr || exp_len != EXP_LEN)
+    return CGC_EINVAL;
+  StainTables t;
+  for (int v = 0; v < 256; ++v) {
+    if (lut[v] < 0 || lut[v] > STAIN_OD_MAX) return CGC_EINVAL;
+    t.lut[v] = lut[v];
+  }
+  if (bad_od_matrix(a, 2048)) return CGC_EINVAL;
+  for (int k = 0; k < 9; ++k) t.m[k] = a[k];
+  // 255 first, 0 last, never rising: a byte for every k the kernel's clamp can reach
+  if (exp_lut[0] != 255 || exp_lut[EXP_LEN - 1] != 0) return CGC_EINVAL;
+  uint32_t words[EXP_WORDS] = {0u};
+  for (int k = 0; k < EXP_LEN; ++k) {
+    if (exp_lut[k] < 0 || exp_lut[k] > 255 || (k > 0 && exp_lut[k] > exp_lut[k - 1])) return CGC_EINVAL;
+    words[k >> 2] |= (uint32_t)exp_lut[k] << (8 * (k & 3));
+  }
+  if (npix == 0) return 0;
+  if (pix == nullptr || ws == nullptr || out == nullptr) return CGC_EINVAL;
+  hipStream_t st = as_stream(stream);
+  uint32_t* table = static_cast<uint32_t*>(ws);
+  const int put = put_words(words, 0, EXP_WORDS, table, st);
+  if (put != 0) return put;
+  const int64_t nb = ceil_div64(ceil_div64(npix, 4), RECOLOR_THREADS);
+  hipLaunchKernelGGL(k_od_recolor, dim3((int)(nb < RECOLOR_MAX_BLOCKS ? nb : RECOLOR_MAX_BLOCKS)), dim3(RECOLOR_THREADS), 0, st, pix, npix,
+                     order, t, (const uint32_t*)table, out);
   CGC_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }

@@ -11,6 +11,7 @@ elements of a row-major matrix.  Kernels never allocate and never synchronise.
 """
 import ctypes
 import functools
+import operator
 import os
 
 import torch
@@ -26,6 +27,8 @@ STAIN_OD_MAX = 5674        # floor(1024 ln 255 + 0.5): the largest optical densi
 ANGLE_BINS = 1024          # K of angle_histogram: bins of the half turn (-pi/2, pi/2), separated by K - 1 directions
 ANGLE_E_MAX, ANGLE_E_REACH = 4096, 7095      # angle_histogram's basis: |E[j][c]| and sum_c |E[j][c]| (ceil(4096 sqrt 3))
 ANGLE_DIR_MAX = 16384      # angle_histogram's directions: |c_k|, |s_k|
+CONC_BINS = 512            # concentration_histogram: levels of 1/128 of a natural-log unit per stain, the last one open (3.99 and up)
+EXP_LUT_LEN = 6386         # od_recolor's exponential table: floor(255 exp(-k / 1024) + 0.5) is 255 at k = 0 and first 0 at k = 6385
 SMOOTH_MAX_RADIUS = 5      # binomial_smooth: 255 * 4^(2 * 5) < 2^31
 WS_JUMP_BATCH = 8          # pointer jumps of watershed_flood per host read: resolves parent chains of up to 2^7 pixels in one read
 
@@ -333,6 +336,51 @@ class KernelSpec(object):
         A workgroup counts ``scan_chunk`` consecutive pixels into 8 copies of the K + 1 counters in LDS (lane l on copy l mod 8,
         bin-major; a run of equal bins among the 16 pixels a lane takes at a time is one add) and adds its non-empty bins to the result with one global atomic
         each."""
+        raise NotImplementedError
+
+    def concentration_histogram(self, image, order, lut, od_min, m, within=None):
+        """The histograms of the concentrations of the first two stains over a tile's stained pixels (stain normalisation, Macenko et
+        al. 2009; csrc/stain.hip), without writing any plane.  Returns int32 [2 B] on the device, B = CONC_BINS = 512; no host read.
+        All arithmetic is int32 and exact; the counts do not depend on the order of the adds.
+
+        1.  image, order, lut, od_min, within and the selection: exactly as od_moments.
+        2.  m: exactly as stain_separate, items 3-4 -- 3 x 3 integers, m[c][s] = rint(4096 inv(S)[c][s]), c = 0 R, 1 G, 2 B, with
+            sum_c |m[c][s]| * 5674 < 2^31 - 2^15 for every s (ValueError otherwise, before any launch; the library repeats it).
+        3.  For a selected pixel and s = 0, 1: C_s = lut[R] m[0][s] + lut[G] m[1][s] + lut[B] m[2][s] in int32.
+        4.  b_s = clamp((C_s + 2^14) >> 15, 0, B - 1) with an arithmetic shift (round half up, also below zero).  One level is 1 / 128
+            of a unit of natural-log concentration: 2^-15 * 1024 * 4096 = 128 levels per unit; bin B - 1 = 511 collects everything
+            from 3.99 units up, bin 0 everything below 1 / 256.
+        5.  Every selected pixel adds one to out[b_0] and one to out[B + b_1]: both halves sum to n, the number of selected pixels.
+        6.  H * W = 0, or nothing selected, gives zeros.
+        The third body of the scan that od_moments and angle_histogram share: a workgroup counts ``scan_chunk`` consecutive pixels into
+        8 copies of the 2 B counters in LDS (lane l on copy l mod 8, bin-major; a run of equal bins of one stain among the 16 pixels a
+        lane takes at a time is one add) and adds its non-empty bins to the result with one global atomic each."""
+        raise NotImplementedError
+
+    def od_recolor(self, image, order, lut, a, exp_lut):
+        """A linear map in optical-density space, from a colour tile to a colour tile (stain normalisation; csrc/stain.hip).  Returns
+        uint8 [H, W, 3], contiguous, in the channel order of the input; no host read.  All arithmetic is int32 and exact; no
+        transcendental function runs on the device.
+
+        1.  image, order, lut: as stain_separate -- uint8 [H, W, 3], any strides, H * W < 2^31; order 0: B, G, R, 1: R, G, B; lut: 256
+            integers in [0, 5674] (ValueError otherwise).
+        2.  a: 3 x 3 integers, a[c][d] = rint(4096 A[c][d]) with c the input and d the output channel (0 R, 1 G, 2 B): OD_out = OD_in A.
+            sum_c |a[c][d]| * 5674 < 2^31 - 2^11 for every d (ValueError otherwise, before any launch; the library repeats it):
+            neither the sum nor the rounding term below can overflow.
+        3.  exp_lut: EXP_LUT_LEN = 6386 integers, exp_lut[k] = floor(255 exp(-k / 1024) + 0.5) (nuclei.EXP_LUT): 255 at k = 0, first 0
+            at k = 6385.  A table of another length, with an entry outside [0, 255], that rises anywhere, or that does not start at
+            255 and end at 0 is refused (ValueError, before any launch; the library repeats it).
+        4.  O_d = lut[v_R] a[0][d] + lut[v_G] a[1][d] + lut[v_B] a[2][d] in int32, in 1 / (1024 * 4096) of a natural-log unit.
+        5.  k_d = clamp((O_d + 2^11) >> 12, 0, 6385) with an arithmetic shift: the optical density in 1/1024, rounded half up.
+        6.  out_d = exp_lut[k_d]; the output pixel holds (out_B, out_G, out_R) for order 0 and (out_R, out_G, out_B) for order 1.
+        7.  H * W = 0 gives an empty output.
+        With a = 4096 I the map is the identity except 0 -> 1: exp_lut[lut[v]] = v for v = 1..255, and lut[0] = lut[1].
+        Error against the real-number formula 255 exp(-(ln(255 / max(v, 1)) A)_d): with delta_d = (sum_c |A[c][d]| / 2 + sum_c o_c
+        / 8192 + 1 / 2) / 1024 -- the table's rounding through the column, the matrix's rounding times the pixel's densities o_c (in
+        natural-log units), the rounding of k -- at most 255 exp(-O_d) (exp(delta_d) - 1) + 1/2 levels.
+        A lane takes 4 pixels as three dwords and stores three dwords (bytes on an unaligned base and on the last 1-3 pixels); both
+        tables sit in LDS, the exponential one as bytes; the matrix stays in scalar registers.  The exponential table reaches the
+        device as angle_histogram's directions do: small launches carry it as kernel arguments into a workspace."""
         raise NotImplementedError
 
     def binomial_smooth(self, image, radius):
@@ -694,6 +742,7 @@ class HipKernels(KernelSpec):
         self.histogram_chunk = int(self.lib.cgc_histogram_chunk_pixels())      # pixels one workgroup of histogram_u8 counts (tests)
         self.scan_chunk = int(self.lib.cgc_scan_chunk_pixels())                # ... and of od_moments / angle_histogram
         self._dirs_checked = (None, None)                                      # angle_histogram's last direction table and its C array
+        self._exp_checked = (None, None)                                       # od_recolor's last exponential table and its C array
         assert int(self.lib.cgc_angle_bins()) == ANGLE_BINS
 
     # -- helpers
@@ -1098,6 +1147,87 @@ class HipKernels(KernelSpec):
                                                dirs_c, _ptr(within),
                                                within.element_size() if within is not None else 0, _ptr(ws), _ptr(out), self._stream()),
                   'cgc_angle_histogram')
+        return out
+
+    @staticmethod
+    def _check_od_matrix(fn, m, slack):
+        """A 3 x 3 integer matrix no column of which lets an int32 sum of optical densities overflow: sum_c |m[c][s]| * 5674 <
+        2^31 - slack.  Returns it as a flat list of Python integers."""
+        try:
+            m = [[operator.index(v) for v in row] for row in m]      # no float, however integral: int() would truncate 0.9 to 0
+        except TypeError:
+            raise ValueError('%s: the matrix must be 3 x 3 integers' % fn)
+        if len(m) != 3 or any(len(row) != 3 for row in m):
+            raise ValueError('%s: the matrix must be 3 x 3' % fn)
+        for s in range(3):
+            if sum(abs(m[c][s]) for c in range(3)) * STAIN_OD_MAX >= 2 ** 31 - slack:
+                raise ValueError('%s: column %d of the matrix lets the int32 sum overflow' % (fn, s))
+        return [v for row in m for v in row]
+
+    @staticmethod
+    def _check_concentration_tables(order, lut, od_min, m):
+        """The refusals of concentration_histogram, which need no tensor: returns (lut, m) as flat lists of Python integers."""
+        lut = HipKernels._check_scan_tables('concentration_histogram', order, lut, od_min)
+        return lut, HipKernels._check_od_matrix('concentration_histogram', m, 2 ** 15)
+
+    @staticmethod
+    def _check_exp_lut(exp_lut):
+        """The refusals of od_recolor's exponential table: returns it as a list of Python integers."""
+        try:
+            e = [operator.index(v) for v in exp_lut]
+        except TypeError:
+            raise ValueError('od_recolor: the exponential table must hold %d integers' % EXP_LUT_LEN)
+        if len(e) != EXP_LUT_LEN or min(e) < 0 or max(e) > 255:
+            raise ValueError('od_recolor: the exponential table must hold %d integers in [0, 255]' % EXP_LUT_LEN)
+        if e[0] != 255 or e[-1] != 0 or any(x < y for x, y in zip(e, e[1:])):
+            raise ValueError('od_recolor: the exponential table must start at 255, end at 0 and never rise')
+        return e
+
+    @staticmethod
+    def _check_recolor_map(order, lut, a):
+        """The refusals of od_recolor's order, optical-density table and matrix: returns (lut, a) as flat lists of Python integers."""
+        if order not in (0, 1):
+            raise ValueError('od_recolor: order must be 0 (BGR) or 1 (RGB), got %r' % (order,))
+        try:
+            lut = [operator.index(v) for v in lut]
+        except TypeError:
+            raise ValueError('od_recolor: the optical-density table must hold 256 integers in [0, %d]' % STAIN_OD_MAX)
+        if len(lut) != 256 or min(lut) < 0 or max(lut) > STAIN_OD_MAX:
+            raise ValueError('od_recolor: the optical-density table must hold 256 integers in [0, %d]' % STAIN_OD_MAX)
+        return lut, HipKernels._check_od_matrix('od_recolor', a, 2 ** 11)
+
+    @staticmethod
+    def _check_recolor_tables(order, lut, a, exp_lut):
+        """The refusals of od_recolor, which need no tensor: returns (lut, a, exp_lut) as flat lists of Python integers."""
+        return HipKernels._check_recolor_map(order, lut, a) + (HipKernels._check_exp_lut(exp_lut),)
+
+    def concentration_histogram(self, image, order, lut, od_min, m, within=None):
+        lut, m = HipKernels._check_concentration_tables(order, lut, od_min, m)
+        image, within = self._scan_images(image, within)
+        out = torch.empty(2 * CONC_BINS, dtype=torch.int32, device=image.device)
+        self._chk(self.lib.cgc_concentration_histogram(_ptr(image), ctypes.c_int64(image.shape[0] * image.shape[1]), int(order),
+                                                       (ctypes.c_int * 256)(*lut), int(od_min), (ctypes.c_int * 9)(*m), _ptr(within),
+                                                       within.element_size() if within is not None else 0, _ptr(out), self._stream()),
+                  'cgc_concentration_histogram')
+        return out
+
+    def od_recolor(self, image, order, lut, a, exp_lut):
+        if self is not None and exp_lut is self._exp_checked[0]:      # the same deeply immutable table as last time: checked, marshalled
+            (lut, a), exp_c = HipKernels._check_recolor_map(order, lut, a), self._exp_checked[1]
+        else:
+            lut, a, e = HipKernels._check_recolor_tables(order, lut, a, exp_lut)
+            exp_c = (ctypes.c_int * EXP_LUT_LEN)(*e)
+            if self is not None and type(exp_lut) is tuple and all(type(v) is int for v in exp_lut):
+                self._exp_checked = (exp_lut, exp_c)
+        self._dev(image)
+        assert image.dtype == torch.uint8 and image.dim() == 3 and image.shape[2] == 3
+        image = image.contiguous()
+        H, W = image.shape[:2]
+        out = torch.empty(H, W, 3, dtype=torch.uint8, device=image.device)
+        ws = torch.empty(int(self.lib.cgc_od_recolor_ws_bytes()), dtype=torch.uint8, device=image.device)
+        self._chk(self.lib.cgc_od_recolor(_ptr(image), ctypes.c_int64(H * W), int(order), (ctypes.c_int * 256)(*lut),
+                                          (ctypes.c_int * 9)(*a), exp_c, EXP_LUT_LEN, _ptr(ws), _ptr(out), self._stream()),
+                  'cgc_od_recolor')
         return out
 
     def binomial_smooth(self, image, radius):

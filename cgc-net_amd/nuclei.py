@@ -30,6 +30,15 @@ stated contract, so that the foreground map is a pure function of the tile.  Its
 ``split_touching``.  ``estimate_stains`` (Macenko et al. 2009) takes the stain vectors from the tile itself instead of the fixed
 ``DEFAULT_STAINS`` -- two integer reductions on the device (kernels.KernelSpec.od_moments, angle_histogram), a 3 x 3 eigenproblem and
 two exact percentiles on the host: ``stain_foreground(tile, stains=estimate_stains(tile))``.
+``normalize_stains`` is the other half of Macenko's method and makes tiles of different slides comparable: it deconvolves with the
+tile's own vectors, scales each stain so that its robust maximum matches a reference (``stain_maxima``; one more integer reduction,
+kernels.KernelSpec.concentration_histogram) and re-composes the tile with reference vectors (``recolor_matrix``, ``recolor``;
+kernels.KernelSpec.od_recolor).  With normalisation in front, the stage reads
+    norm = normalize_stains(tile)
+    fg, t, plane = stain_foreground(norm, stains=TARGET_STAINS + residual)
+    ...
+    nucleus_features(L, bgr_to_gray(norm), max_label=n)
+where ``TARGET_STAINS + residual`` stands for the 3 x 3 vectors made of the two target rows plus their cross product.
 
 ``nucleus_features(labels, gray)`` returns the reference's ``feature`` / ``coordinate`` arrays of one image (csrc/nuclei.hip; the
 arithmetic item by item: kernels.KernelSpec.nucleus_features), ``graph_item`` turns them into the ``Data`` that
@@ -533,6 +542,21 @@ OD_LUT = _od_lut()
 DEFAULT_STAINS = ((0.65, 0.70, 0.29), (0.07, 0.99, 0.11), (0.27, 0.57, 0.78))
 STAIN_ORDERS = {'bgr': 0, 'rgb': 1}
 ANGLE_BINS = kernels.ANGLE_BINS
+CONC_BINS = kernels.CONC_BINS
+# the reference stains and their robust maxima of Macenko's published implementation: unit OD vectors (R, G, B) of haematoxylin and
+# eosin, and the 99th percentiles of their concentrations in natural-log units
+TARGET_STAINS = ((0.5626, 0.7201, 0.4062), (0.2159, 0.8012, 0.5581))
+TARGET_MAX = (1.9705, 1.0308)
+
+
+def _exp_lut():
+    """The channel value of every optical density in 1/1024 of a natural-log unit: floor(255 exp(-k / 1024) + 0.5) for k = 0..6385,
+    from 255 down to the first 0.  No 255 exp(-k / 1024) + 0.5 lies within 1e-6 of an integer (the nearest is 1.79e-5 away, at
+    k = 6384; tests/test_normalize_ref_cpu.py), so every libm gives the same table.  EXP_LUT[OD_LUT[v]] = v for v = 1..255."""
+    return tuple(int(math.floor(255.0 * math.exp(-k / 1024.0) + 0.5)) for k in range(kernels.EXP_LUT_LEN))
+
+
+EXP_LUT = _exp_lut()
 
 
 def _angle_dirs():
@@ -698,6 +722,13 @@ def stain_foreground(image, stain=0, radius=2, stains=None, order='bgr', within=
         L, n = split_touching(fill_holes(fg), None, markers='h_maxima', growth='flood', h=2.0)
         features, centroids, kept = nucleus_features(L, bgr_to_gray(image), max_label=n)
 
+    With normalisation in front (normalize_stains), ``TARGET_STAINS + residual`` standing for the two target rows plus their cross
+    product:
+        norm = normalize_stains(tile)
+        fg, t, plane = stain_foreground(norm, stains=TARGET_STAINS + residual)
+        ...
+        nucleus_features(L, bgr_to_gray(norm), max_label=n)
+
     Host syncs: one, that of otsu_threshold."""
     _check_color('stain_foreground', image)
     _check_planes((stain,))
@@ -798,8 +829,7 @@ def estimate_stains(image, order='bgr', beta=0.15, alpha=1.0, within=None, retur
     if order not in STAIN_ORDERS:
         raise ValueError("order must be 'bgr' or 'rgb', got %r" % (order,))
     od_min = _od_min(beta)
-    if isinstance(alpha, bool) or not isinstance(alpha, numbers.Real) or not 0 <= alpha < 50:
-        raise ValueError('alpha must be a number with 0 <= alpha < 50 (got %r)' % (alpha,))
+    _check_alpha(alpha)
     _check_within('estimate_stains', within, image[:, :, 0])
     if image.shape[0] * image.shape[1] == 0:
         raise ValueError('estimate_stains: too few stained pixels (0): the image is empty')
@@ -818,6 +848,181 @@ def estimate_stains(image, order='bgr', beta=0.15, alpha=1.0, within=None, retur
     if return_info:
         return S, dict(n=n, skipped=skipped, od_min=od_min, bins=(b_lo, b_hi), eigenvalues=tuple(float(v) / (n * (n - 1)) for v in lam))
     return S
+
+
+def _check_alpha(alpha):
+    if isinstance(alpha, bool) or not isinstance(alpha, numbers.Real) or not 0 <= alpha < 50:
+        raise ValueError('alpha must be a number with 0 <= alpha < 50 (got %r)' % (alpha,))
+
+
+def _top_bin(bins, alpha):
+    """The bin of stain_maxima's rule, in exact arithmetic as _percentile_bins: the smallest b with cum(b) >= 1 and
+    100 cum(b) >= (100 - alpha) n; sum(bins) = n > 0."""
+    a, n = Fraction(alpha), sum(bins)
+    cum = 0
+    for b, c in enumerate(bins):
+        cum += c
+        if cum >= 1 and 100 * cum >= (100 - a) * n:
+            return b
+
+
+def _stain_maxima(image, stains, order, alpha, beta, within):
+    """stain_maxima behind its checks: (maxima, bins, n)."""
+    _check_color('stain_maxima', image)
+    if order not in STAIN_ORDERS:
+        raise ValueError("order must be 'bgr' or 'rgb', got %r" % (order,))
+    _check_alpha(alpha)
+    od_min = _od_min(beta)
+    _check_within('stain_maxima', within, image[:, :, 0])
+    m = stain_matrix(stains)
+    if image.shape[0] * image.shape[1] == 0:
+        raise ValueError('stain_maxima: no stained pixel (0): the image is empty')
+    with torch.cuda.device(image.device):
+        counts = kernels.get().concentration_histogram(image, STAIN_ORDERS[order], OD_LUT, od_min, m.tolist(), within).tolist()
+    halves = counts[:CONC_BINS], counts[CONC_BINS:]
+    n = sum(halves[0])
+    if n == 0:
+        raise ValueError('stain_maxima: no stained pixel (0): lower beta or widen within')
+    bins = tuple(_top_bin(h, alpha) for h in halves)
+    for s, b in enumerate(bins):
+        if b == 0:
+            raise ValueError('stain_maxima: the tile has none of stain %d (its robust maximum lies in bin 0)' % s)
+        if b == CONC_BINS - 1:
+            raise ValueError('stain_maxima: the histogram of stain %d is saturated (its robust maximum lies in the last bin, '
+                             '%d/128 and up)' % (s, CONC_BINS - 1))
+    return tuple(Fraction(b, 128) for b in bins), bins, n
+
+
+def stain_maxima(image, stains=None, order='bgr', alpha=1.0, beta=0.15, within=None):
+    """The robust maxima of a tile's haematoxylin and eosin concentrations (Macenko et al. 2009), for recolor_matrix: two
+    ``Fraction``s in natural-log units.  image: uint8 [H, W, 3] on the GPU, any strides; ``stains``: as stain_matrix (None:
+    DEFAULT_STAINS), usually estimate_stains(image); ``order``: 'bgr' or 'rgb'; ``within`` (bool / integer [H, W]): the pixels that
+    may be used.  One integer reduction with a stated contract (kernels.KernelSpec.concentration_histogram): the result is a pure
+    function of the tile and of stain_matrix(stains).
+
+    1.  od_min from ``beta`` and the selection of the stained pixels: item 1 of estimate_stains.  ``beta`` = 0 selects every pixel
+        (of ``within``), which is what the published code does; the default selects the stained pixels, as estimate_stains does.
+        0 <= alpha < 50 (ValueError otherwise).
+    2.  The concentrations C_0, C_1 of every stained pixel are binned in levels of 1/128 of a unit, 512 bins per stain, the last one
+        open, and the 1024 counts are read (the host sync).  n = the sum of either half.  n = 0 raises ValueError.
+    3.  In exact arithmetic: b_s = the smallest bin with cum(b) >= 1 and 100 cum(b) >= (100 - alpha) n -- the bin of the
+        ceil((100 - alpha) n / 100)-th smallest concentration.  The maximum of stain s is b_s / 128.
+    4.  b_s = 0 raises ValueError (the tile has none of that stain), and so does b_s = 511 (the histogram is saturated: 3.99 units
+        and up).
+
+    Host syncs: one, the read of the 1024 counts."""
+    return _stain_maxima(image, stains, order, alpha, beta, within)[0]
+
+
+def _unit_rows(fn, name, rows, shapes):
+    try:
+        R = np.array(rows, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('%s: %s must be numbers' % (fn, name))
+    if R.shape not in shapes:
+        raise ValueError('%s: %s must be %s (got shape %s)' % (fn, name, ' or '.join('%d x %d' % sh for sh in shapes), R.shape))
+    if not np.isfinite(R).all():
+        raise ValueError('%s: %s must be finite' % (fn, name))
+    norm = np.sqrt((R * R).sum(axis=1))
+    if not (norm > 0).all() or not np.isfinite(norm).all():
+        raise ValueError('%s: every row of %s needs a non-zero optical-density vector' % (fn, name))
+    return R / norm[:, None]
+
+
+def _positive_pair(fn, name, pair):
+    try:
+        v = [float(x) for x in pair]
+    except (TypeError, ValueError):
+        raise ValueError('%s: %s must be two positive numbers' % (fn, name))
+    if len(v) != 2 or not all(math.isfinite(x) and x > 0 for x in v):
+        raise ValueError('%s: %s must be two positive finite numbers (got %r)' % (fn, name, pair))
+    return v
+
+
+def recolor_matrix(stains, maxima, target_stains=None, target_max=None):
+    """The fixed-point matrix that takes a tile's optical densities to those of the normalised tile: numpy int32 [3, 3],
+    a[c][d] = rint(4096 A[c][d]) with c the input and d the output channel (0 R, 1 G, 2 B) and, in float64,
+        A = inv(S)[:, :2] diag(target_max_s / maxima_s) T[:2].
+    S: the unit-normalised rows of ``stains`` (3 x 3, as stain_matrix); T: the first two unit-normalised rows of ``target_stains``
+    (2 x 3 or 3 x 3; None: TARGET_STAINS); ``maxima``: two positive numbers, e.g. stain_maxima's Fractions; ``target_max``: two positive
+    numbers (None: TARGET_MAX).  The residual is dropped, as Macenko does: because the residual row of estimate_stains is orthogonal
+    to the other two, the first two columns of inv(S) are the least-squares concentrations on the two stains alone.
+    ValueError: bad shapes, non-finite or zero rows, dependent stains, non-positive or non-finite maxima or targets, or a matrix
+    with sum_c |a[c][d]| * 5674 >= 2^31 - 2^11 for some d (recolor's int32 sum could overflow)."""
+    S = _unit_rows('recolor_matrix', 'stains', stains, ((3, 3),))
+    stain_matrix(S)                        # its refusals of dependent stains are this function's
+    T = _unit_rows('recolor_matrix', 'target_stains', TARGET_STAINS if target_stains is None else target_stains, ((2, 3), (3, 3)))[:2]
+    mx = _positive_pair('recolor_matrix', 'maxima', maxima)
+    tm = _positive_pair('recolor_matrix', 'target_max', TARGET_MAX if target_max is None else target_max)
+    A = np.linalg.inv(S)[:, :2] @ np.diag([tm[0] / mx[0], tm[1] / mx[1]]) @ T
+    q = np.rint(4096.0 * A)
+    if not np.isfinite(q).all() or (np.abs(q).sum(axis=0) * kernels.STAIN_OD_MAX >= 2 ** 31 - 2 ** 11).any():
+        raise ValueError('recolor_matrix: the matrix is too large: the int32 sum of recolor could overflow')
+    return q.astype(np.int32)
+
+
+def recolor(image, a, order='bgr'):
+    """A linear map in optical-density space: image uint8 [H, W, 3] on the GPU (any strides) -> uint8 [H, W, 3] in the same channel
+    order, out_d = EXP_LUT[clamp((sum_c OD_LUT[v_c] a[c][d] + 2^11) >> 12, 0, 6385)] (kernels.KernelSpec.od_recolor).  ``a``: 3 x 3
+    integers, 4096 times the matrix, c the input and d the output channel (0 R, 1 G, 2 B): recolor_matrix's, or
+    rint(4096 inv(S)[:, s] T[s]) to render stain s alone.  ValueError: a matrix that is not 3 x 3 integers or that fails
+    sum_c |a[c][d]| * 5674 < 2^31 - 2^11.  With a = 4096 I the result is the input except that 0 becomes 1.
+
+    Host syncs: none."""
+    _check_color('recolor', image)
+    if order not in STAIN_ORDERS:
+        raise ValueError("order must be 'bgr' or 'rgb', got %r" % (order,))
+    if isinstance(a, np.ndarray):
+        if a.dtype.kind not in 'iu':
+            raise ValueError('recolor: the matrix must hold integers (got %s)' % a.dtype)
+        a = a.tolist()
+    kernels.HipKernels._check_od_matrix('recolor', a, 2 ** 11)
+    with torch.cuda.device(image.device):
+        return kernels.get().od_recolor(image, STAIN_ORDERS[order], OD_LUT, a, EXP_LUT)
+
+
+def normalize_stains(image, stains=None, order='bgr', target_stains=None, target_max=None, alpha=1.0, beta=0.15, within=None,
+                     return_info=False):
+    """Stain normalisation by Macenko's method (Macenko et al. 2009): the tile as it would look with the reference stains at the
+    reference strength.  image: uint8 [H, W, 3] on the GPU, any strides; returns uint8 [H, W, 3], contiguous, in the input's channel
+    order (``order``: 'bgr' or 'rgb').  ``within`` (bool / integer [H, W]): the pixels the statistics are taken over, e.g. a tissue
+    mask -- every pixel is recoloured.  All device arithmetic is integer with a stated contract, so the result is a pure function of
+    the tile (and, with ``stains`` = None, of what estimate_stains depends on).
+
+    1.  S = ``stains`` (as stain_matrix), or with None the tile's own vectors estimate_stains(image, order, beta, alpha, within).
+    2.  maxima = stain_maxima(image, S, order, alpha, beta, within): the robust maxima b_s / 128 of the two concentrations.
+    3.  a = recolor_matrix(S, maxima, target_stains, target_max): rint(4096 inv(S)[:, :2] diag(target_max_s / maxima_s) T[:2]),
+        T the reference vectors (None: TARGET_STAINS, TARGET_MAX); the residual is dropped.
+    4.  The result is recolor(image, a, order): out_d = EXP_LUT[clamp((sum_c OD_LUT[v_c] a[c][d] + 2^11) >> 12, 0, 6385)].
+    5.  Every ValueError of the four steps is this function's: too few stained pixels, one stain only, none of a stain, a saturated
+        histogram, bad targets, a matrix that could overflow.
+    6.  ``return_info``: also a dict with stains (S as float64 [3, 3], as given or as estimated), maxima (two Fractions), bins = (b_0, b_1), n (the stained
+        pixels) and matrix (a, int32 [3, 3]).
+
+        norm = normalize_stains(tile)
+        fg, t, plane = stain_foreground(norm, stains=TARGET_STAINS + residual)
+        ...
+        nucleus_features(L, bgr_to_gray(norm), max_label=n)
+    (``TARGET_STAINS + residual``: the two target rows plus their cross product.)
+
+    Host syncs: three -- the two of estimate_stains and the read of the 1024 counts -- or one with given stains."""
+    _check_color('normalize_stains', image)
+    if order not in STAIN_ORDERS:
+        raise ValueError("order must be 'bgr' or 'rgb', got %r" % (order,))
+    _check_alpha(alpha)
+    _od_min(beta)
+    _check_within('normalize_stains', within, image[:, :, 0])
+    T = TARGET_STAINS if target_stains is None else target_stains
+    tm = TARGET_MAX if target_max is None else target_max
+    _unit_rows('normalize_stains', 'target_stains', T, ((2, 3), (3, 3)))      # bad targets are refused before any launch
+    _positive_pair('normalize_stains', 'target_max', tm)
+    S = estimate_stains(image, order, beta, alpha, within) if stains is None else stains
+    maxima, bins, n = _stain_maxima(image, S, order, alpha, beta, within)
+    a = recolor_matrix(S, maxima, T, tm)
+    out = recolor(image, a, order)
+    if return_info:
+        return out, dict(stains=np.array(S, dtype=np.float64), maxima=maxima, bins=bins, n=n, matrix=a)
+    return out
 
 
 def graph_item(features, centroids, y):

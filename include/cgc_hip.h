@@ -66,8 +66,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *      cgc_watershed_jumps, cgc_watershed_finish
  *  15: from an H&E tile to a foreground map: cgc_stain_separate, cgc_histogram_chunk_pixels, cgc_histogram_u8, cgc_binomial_smooth_u8
  *  16: a tile's own stain vectors (Macenko): cgc_scan_chunk_pixels, cgc_od_moments, cgc_angle_bins, cgc_angle_histogram_ws_bytes,
- *      cgc_angle_histogram */
-#define CGC_ABI_VERSION 16
+ *      cgc_angle_histogram
+ *  17: stain normalisation: cgc_concentration_bins, cgc_concentration_histogram, cgc_exp_lut_len, cgc_od_recolor_ws_bytes,
+ *      cgc_od_recolor */
+#define CGC_ABI_VERSION 17
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -311,6 +313,36 @@ int cgc_angle_bins(void);
 int64_t cgc_angle_histogram_ws_bytes(void);
 int cgc_angle_histogram(const uint8_t* pix, int64_t npix, int order, const int* lut, int od_min, const int* basis, const int* dirs,
                         const void* within_or_null, int within_bytes, void* ws, int* out, cgc_stream_t stream);
+
+/* ---- F12 (beside F11): the two kernels behind stain normalisation (Macenko et al. 2009; csrc/stain.hip; cgc-net_amd/nuclei.py
+ * normalize_stains).  The contracts item by item: cgc-net_amd/kernels.py KernelSpec.concentration_histogram, od_recolor.  All arithmetic
+ * is int32 and exact; no transcendental function runs on the device.
+ *   cgc_concentration_histogram: pix, npix, order, lut, od_min, within_or_null, within_bytes and the selection are those of
+ *     cgc_od_moments; m (HOST, 9 int32, m[3 c + s]) is that of cgc_stain_separate, with its refusal for all three columns.  For a
+ *     selected pixel and s = 0, 1: C_s = lut[R] m[0][s] + lut[G] m[1][s] + lut[B] m[2][s], b_s = clamp((C_s + 2^14) >> 15, 0, B - 1)
+ *     (arithmetic shift), B = cgc_concentration_bins() = 512: one level = 1 / 128 of a natural-log unit, the last bin open.  out int32
+ *     [2 B] (device): one is added to out[b_0] and to out[B + b_1].  The entry zeroes out itself (an asynchronous fill), then one
+ *     launch: the third body of the scan of F11, a workgroup per cgc_scan_chunk_pixels() pixels.  No workspace.
+ *   cgc_od_recolor: out uint8 [npix, 3] (device, interleaved in the order of pix; must not overlap pix).  a (HOST, 9 int32,
+ *     a[3 c + d] = rint(4096 A[c][d]), c the input and d the output channel, 0 R, 1 G, 2 B): sum_c |a[c][d]| * 5674 < 2^31 - 2^11 for
+ *     every d.  exp_lut (HOST, exp_len = cgc_exp_lut_len() = 6386 int32): exp_lut[k] = floor(255 exp(-k / 1024) + 0.5); the library
+ *     accepts any table of that length with entries in [0, 255] that starts at 255, ends at 0 and never rises.  Per pixel
+ *       O_d = sum_c lut[v_c] a[c][d] (int32);  k_d = clamp((O_d + 2^11) >> 12, 0, 6385);  out_d = exp_lut[k_d].
+ *     ws: cgc_od_recolor_ws_bytes() (6400) bytes on the device, 256-byte aligned: the entry puts the table there as bytes (two
+ *     small launches whose kernel arguments carry it -- the helper that carries cgc_angle_histogram's directions), then one launch.
+ * CGC_EINVAL, nothing launched.  cgc_concentration_histogram: what cgc_od_moments refuses (a NULL out included, also at npix = 0,
+ * since the entry zeroes it), a NULL m, a matrix beyond its bound; with npix > 0 also a NULL pix.  cgc_od_recolor: what
+ * cgc_stain_separate refuses for pix, npix, order and lut, a NULL a or exp_lut, a matrix beyond its bound, exp_len other than 6386, a
+ * table of another kind; with npix > 0 also a NULL pix, ws or out -- at npix = 0 the tables are still checked, then the entry
+ * returns 0 and touches neither ws nor out, which may be NULL.  out of cgc_od_recolor may start at any byte: three dwords per lane
+ * where its base is a multiple of 4, bytes otherwise. */
+int cgc_concentration_bins(void);
+int cgc_concentration_histogram(const uint8_t* pix, int64_t npix, int order, const int* lut, int od_min, const int* m,
+                                const void* within_or_null, int within_bytes, int* out, cgc_stream_t stream);
+int cgc_exp_lut_len(void);
+int64_t cgc_od_recolor_ws_bytes(void);
+int cgc_od_recolor(const uint8_t* pix, int64_t npix, int order, const int* lut, const int* a, const int* exp_lut, int exp_len, void* ws,
+                   uint8_t* out, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */

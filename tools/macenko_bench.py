@@ -35,8 +35,8 @@ import macenko_ref  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
 TRACE_CALLS = 40
-KERNELS = {r'k_od_scan<false>|k_od_scanILb0': 'od_moments', r'k_od_scan<true>|k_od_scanILb1': 'angle_histogram', 'k_put_dirs': 'put_dirs',
-           'k_stain_separate': 'stain_separate'}
+KERNELS = {r'k_od_scan<(false|0)>|k_od_scanIL[bi]0': 'od_moments', r'k_od_scan<(true|1)>|k_od_scanIL[bi]1': 'angle_histogram',
+           'k_put_dirs|k_put_words': 'put_dirs', 'k_stain_separate': 'stain_separate'}
 
 
 def torch_moments(image, beta):
