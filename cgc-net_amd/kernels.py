@@ -30,7 +30,8 @@ ANGLE_DIR_MAX = 16384      # angle_histogram's directions: |c_k|, |s_k|
 CONC_BINS = 512            # concentration_histogram: levels of 1/128 of a natural-log unit per stain, the last one open (3.99 and up)
 EXP_LUT_LEN = 6386         # od_recolor's exponential table: floor(255 exp(-k / 1024) + 0.5) is 255 at k = 0 and first 0 at k = 6385
 SMOOTH_MAX_RADIUS = 5      # binomial_smooth: 255 * 4^(2 * 5) < 2^31
-WS_JUMP_BATCH = 8          # pointer jumps of watershed_flood per host read: resolves parent chains of up to 2^7 pixels in one read
+ADJ_MAX_PIXELS = 2 ** 29   # region_adjacency: a pair's count can reach 4 H W and must fit int32
+WS_JUMP_BATCH = 8         # pointer jumps of watershed_flood per host read: resolves parent chains of up to 2^7 pixels in one read
 
 
 @functools.lru_cache(maxsize=4)
@@ -395,6 +396,31 @@ class KernelSpec(object):
         4.  H < r or W < r are ordinary shapes: the clamp covers them.  H * W = 0 gives an empty output."""
         raise NotImplementedError
 
+    def region_adjacency(self, labels, connectivity, value=None):
+        """Region adjacency of one label image (F13, behind label_components / distance_transform; csrc/adjacency.hip): which
+        regions touch, along how many pixel pairs, and how near they come.  Returns (pairs int32 [P, 2], count int32 [P], min_sum int32
+        [P] or None); two host reads, the number of per-tile records and P.
+
+        1.  labels: int32 [H, W], contiguous, H * W < 2^29 (ValueError otherwise; the library returns CGC_EINVAL and launches nothing): a
+            pair's count can reach 4 H W and must fit int32.
+        2.  0 is background.  Every other value is a region, negative values included.  Regions need not be connected.
+        3.  A contact is an unordered pair of neighbouring pixels p, q with labels[p] != labels[q] and both non-zero.  connectivity 1:
+            the horizontal and the vertical neighbour; connectivity 2: also the two diagonals.  Each pixel pair is counted once.
+        4.  pairs: each row is (a, b) with a < b as signed integers; rows are sorted lexicographically and each pair appears once.
+            count: the number of contacts of that pair.
+        5.  value (int32 [H, W]): min_sum = the smallest value[p] + value[q] over the pair's contacts, the sum taken in 64 bits and clamped
+            to the int32 range, so it is defined for every input.  Without value, min_sum is None.
+        6.  H * W = 0, or no contact at all, gives empty outputs.
+        7.  The outputs are a pure function of the inputs, bit for bit from call to call: internal tables are filled in any order, and
+            the sort and the integer sums and minima make the outputs independent of it.
+        8.  No input overflows a table silently.  The per-tile table in LDS has a fallback that is exact: a tile with more distinct
+            pairs than the table folds writes one record per contact instead, and which tiles do so depends on their pixels alone.  The
+            record buffers are sized from a count launch, the outputs from a count of the sorted records' distinct keys.  An image in
+            which every pixel has its own label (2 H (W - 1) + ... distinct pairs, one per contact) is an ordinary input.
+        The records are ordered by ``torch.sort`` of their 64-bit keys between two library calls; the scan, the per-tile folding and the
+        merge of equal keys are library kernels."""
+        raise NotImplementedError
+
     def edge_renorm(self, rowptr, col, n, p, val_out):
         """Level-1 ``_re_norm_adj`` (model/network.py:183-191) on a 0/1 CSR that holds its diagonal:
         val[k] = p if col[k]==row else (1/(c+1e-15))*(1-p), c = number of off-diagonal entries of the row."""
@@ -740,6 +766,7 @@ class HipKernels(KernelSpec):
         self._ws_cache = {}
         self._graph_local_max = int(self.lib.cgc_graph_local_max_nodes())
         self.histogram_chunk = int(self.lib.cgc_histogram_chunk_pixels())      # pixels one workgroup of histogram_u8 counts (tests)
+        self.adjacency_tile = int(self.lib.cgc_adjacency_tile_side())          # side of the tiles region_adjacency folds in LDS (tests)
         self.scan_chunk = int(self.lib.cgc_scan_chunk_pixels())                # ... and of od_moments / angle_histogram
         self._dirs_checked = (None, None)                                      # angle_histogram's last direction table and its C array
         self._exp_checked = (None, None)                                       # od_recolor's last exponential table and its C array
@@ -1239,6 +1266,40 @@ class HipKernels(KernelSpec):
         out = torch.empty(H, W, dtype=torch.uint8, device=image.device)
         self._chk(self.lib.cgc_binomial_smooth_u8(_ptr(image), H, W, int(radius), _ptr(out), self._stream()), 'cgc_binomial_smooth_u8')
         return out
+
+    def region_adjacency(self, labels, connectivity, value=None):
+        HipKernels._check_connectivity(connectivity)
+        labels, value = self._image(labels), self._image(value)
+        assert labels.dtype == torch.int32 and (value is None or (value.dtype == torch.int32 and value.shape == labels.shape))
+        H, W = labels.shape
+        if H * W >= ADJ_MAX_PIXELS:
+            raise ValueError('region_adjacency takes images of fewer than 2^29 pixels (got %d x %d): a count must fit int32' % (H, W))
+        dev = labels.device
+        u8, i32, i64 = (dict(dtype=d, device=dev) for d in (torch.uint8, torch.int32, torch.int64))
+        empty = (torch.empty(0, 2, **i32), torch.empty(0, **i32), None if value is None else torch.empty(0, **i32))
+        if H * W == 0:
+            return empty
+        ws = torch.empty(int(self.lib.cgc_adjacency_ws_bytes(H, W)), **u8)
+        nbuf = torch.empty(2, **i32)
+        self._chk(self.lib.cgc_adjacency_count(_ptr(labels), H, W, int(connectivity), _ptr(ws), _ptr(nbuf), self._stream()),
+                  'cgc_adjacency_count')
+        nrec = int(nbuf[0].item())                      # host sync 1 of this stage: the records the tiles will write
+        if nrec == 0:
+            return empty
+        keys, cnts = torch.empty(nrec, **i64), torch.empty(nrec, **i32)
+        sums = None if value is None else torch.empty(nrec, **i32)
+        self._chk(self.lib.cgc_adjacency_records(_ptr(labels), _ptr(value), H, W, int(connectivity), _ptr(ws), ctypes.c_int64(nrec),
+                                                 _ptr(keys), _ptr(cnts), _ptr(sums), self._stream()), 'cgc_adjacency_records')
+        keys, perm = torch.sort(keys)                   # the order of equal keys does not matter: their records are summed
+        mws = torch.empty(int(self.lib.cgc_adjacency_merge_ws_bytes(ctypes.c_int64(nrec))), **u8)
+        self._chk(self.lib.cgc_adjacency_heads(_ptr(keys), ctypes.c_int64(nrec), _ptr(mws), _ptr(nbuf[1:]), self._stream()),
+                  'cgc_adjacency_heads')
+        npairs = int(nbuf[1].item())                    # host sync 2: the distinct pairs
+        pairs, count = torch.empty(npairs, 2, **i32), torch.empty(npairs, **i32)
+        min_sum = None if value is None else torch.empty(npairs, **i32)
+        self._chk(self.lib.cgc_adjacency_merge(_ptr(keys), _ptr(perm), _ptr(cnts), _ptr(sums), ctypes.c_int64(nrec), _ptr(mws), npairs,
+                                               _ptr(pairs), _ptr(count), _ptr(min_sum), self._stream()), 'cgc_adjacency_merge')
+        return pairs, count, min_sum
 
     def edge_renorm(self, rowptr, col, n, p, val_out):
         self._dev(rowptr, col, val_out)

@@ -40,6 +40,11 @@ kernels.KernelSpec.od_recolor).  With normalisation in front, the stage reads
     nucleus_features(L, bgr_to_gray(norm), max_label=n)
 where ``TARGET_STAINS + residual`` stands for the 3 x 3 vectors made of the two target rows plus their cross product.
 
+``region_adjacency`` reads off a label image which regions touch and along how many pixels (csrc/adjacency.hip;
+kernels.KernelSpec.region_adjacency), and ``voronoi_graph`` builds on it the other standard cell graph of the literature: the cells of
+``expand_labels`` are the discrete Voronoi partition of the instance mask, and two nuclei are joined iff their cells share a border.
+Its ``edge_index`` goes into ``graph_item(..., edge_index=...)`` in place of the radius graph on centroids.
+
 ``nucleus_features(labels, gray)`` returns the reference's ``feature`` / ``coordinate`` arrays of one image (csrc/nuclei.hip; the
 arithmetic item by item: kernels.KernelSpec.nucleus_features), ``graph_item`` turns them into the ``Data`` that
 ``_read_one_raw_graph`` builds, and ``save_reference_files`` writes them where the reference's dataset preparation reads them.
@@ -244,15 +249,25 @@ def expand_labels(labels, distance, within=None, geodesic=False, metric='chamfer
     else:
         if distance is None:
             raise ValueError('distance=None (unbounded growth) needs geodesic=True')
-        d2max = _d2max(distance, 'distance')
-        with torch.cuda.device(labels.device):
-            _, nearest = kernels.get().distance_transform(labels, True, d2max, True)
-        fill = nearest >= 0                     # -1: nothing within reach
-        if within is not None:
-            fill &= (labels != 0) | (within != 0)
+        return _grow_euclidean(labels, _d2max(distance, 'distance'), within)[0]
+    return _take_nearest(labels, nearest, fill)
+
+
+def _take_nearest(labels, nearest, fill):
     # a labelled pixel is its own nearest site, so the gather returns it unchanged
     src = labels.reshape(-1)[nearest.clamp_(min=0).reshape(-1).long()].reshape(labels.shape)
     return torch.where(fill, src, labels)
+
+
+def _grow_euclidean(labels, d2max, within=None):
+    """(grown, dist2) of expand_labels' Euclidean growth: one distance transform gives both the cells and every pixel's squared
+    distance to its nearest labelled pixel (EDT_INF beyond the bound)."""
+    with torch.cuda.device(labels.device):
+        dist2, nearest = kernels.get().distance_transform(labels, True, d2max, True)
+    fill = nearest >= 0                         # -1: nothing within reach
+    if within is not None:
+        fill &= (labels != 0) | (within != 0)
+    return _take_nearest(labels, nearest, fill), dist2
 
 
 def reconstruct(marker, mask, method='dilation', connectivity=1):
@@ -482,6 +497,123 @@ def split_touching(mask, core_radius, connectivity=1, min_size=0, growth='euclid
     rest, _ = label_instances(fg & (grown == 0), connectivity)
     combined = torch.where(rest > 0, rest + k, grown)
     return label_instances(combined, connectivity, min_size)
+
+
+def _check_labels32(fn, name, labels):
+    """A label image whose values are themselves output: int64 is refused instead of narrowed."""
+    _check_image(fn, name, labels)
+    if labels.dtype == torch.int64:
+        raise TypeError('%s: %s must fit int32, whose values are output: pass %s.to(torch.int32)' % (fn, name, name))
+
+
+def region_adjacency(labels, connectivity=1, value=None):
+    """Which regions of a label image touch, and along how many pixel pairs (csrc/adjacency.hip; the contract item by item:
+    kernels.KernelSpec.region_adjacency).  labels: 2-D bool / uint8 / int8 / int16 / int32 tensor on the GPU, any strides, fewer than
+    2^29 pixels; 0 = background, every other value (negative ones too) a region, connected or not.  int64 is a TypeError (``labels.to(
+    torch.int32)``): the values themselves are output and must fit.  A contact is an unordered pair of neighbouring pixels
+    (``connectivity`` 1: horizontal and vertical neighbours, 2: also diagonal ones) that carry two different non-zero values.  Returns
+    (pairs int32 [P, 2], count int32 [P]): rows (a, b) with a < b, sorted lexicographically, each pair once, and its number of
+    contacts -- e.g. which instances of ``split_touching`` still touch, and along how many pixels.  ``value`` (bool / uint8 / int8 /
+    int16 / int32, same shape and device: ValueError otherwise, TypeError for another dtype, as for ``within`` elsewhere): a third
+    output min_sum int32 [P], the smallest value[p] + value[q] over the pair's contacts (summed in 64 bits, clamped to int32).  The
+    outputs are a pure function of the inputs.  An empty image gives empty tensors without a launch.
+
+    Host syncs: two, the reads of the number of per-tile records and of P; none for an empty image."""
+    _check_labels32('region_adjacency', 'labels', labels)
+    _check_connectivity(connectivity)
+    if value is not None:
+        _check_image('region_adjacency', 'value', value, _INT32_DTYPES)
+        if tuple(value.shape) != tuple(labels.shape) or value.device != labels.device:
+            raise ValueError('region_adjacency: value must have the shape and device of labels (got %s on %s and %s on %s)'
+                             % (tuple(value.shape), value.device, tuple(labels.shape), labels.device))
+    H, W = labels.shape
+    if H * W >= kernels.ADJ_MAX_PIXELS:
+        raise ValueError('region_adjacency: images of 2^29 pixels or more are not supported (%d x %d)' % (H, W))
+    i32 = dict(dtype=torch.int32, device=labels.device)
+    if H * W == 0:
+        out = (torch.empty(0, 2, **i32), torch.empty(0, **i32), torch.empty(0, **i32))
+    else:
+        with torch.cuda.device(labels.device):
+            out = kernels.get().region_adjacency(labels.to(torch.int32), int(connectivity), None if value is None else value.to(torch.int32))
+    return out[:2] if value is None else out
+
+
+def voronoi_graph(labels, max_distance, kept_labels=None, connectivity=1, loop=True, max_gap=None, return_attr=False):
+    """The cell graph whose edges join nuclei with neighbouring Voronoi cells (the Delaunay / Voronoi construction of the cell-graph
+    literature, on the nuclei's shapes instead of their centroids): symmetric, no degree cap, measured from the nuclei's outlines, and
+    never across a third nucleus that lies between two.  labels: 2-D bool / uint8 / int8 / int16 / int32 instance mask on the GPU (0 =
+    background; int64 is a TypeError), non-negative (ValueError).  Returns edge_index int64 [2, E] and, with ``return_attr``, (edge_index,
+    border int32 [E], gap float32 [E]).
+      1. Nodes.  Node i is label kept_labels[i]: int32, strictly ascending, positive, on the labels' device, as ``nucleus_features``
+         returns it -- edge ends are then row numbers of its feature table.  ``None``: the distinct non-zero labels in ascending order.
+         Pixels of labels that are not kept become background before growing: a nucleus that ``min_size`` removed claims no cell.
+      2. Cells.  cells = expand_labels(kept, max_distance): Euclidean growth, ties to the smallest raster index; dist2 comes from the
+         same distance transform.
+      3. Distance plane.  T = the largest integer with T^2 <= 64 dist2 (eighths of a pixel), 0 where no nucleus is within reach.
+      4. Adjacency.  pairs, count, min_sum = region_adjacency(cells, connectivity, value=T).
+      5. Gap.  gap8 = min_sum + 8: the length, in eighths of a pixel, of the shortest path from one nucleus to the other that crosses
+         their common border in one axial step.  It is NOT the true gap between the two outlines: it is at least the true gap minus
+         1/4 pixel (two floors) and usually equal to it, but where a third nucleus hides the two closest points from the shared border
+         it is larger (on a 300 x 300 synthetic tissue at max_distance 50: median excess 0.05 px, largest 18.9 px), and a purely
+         diagonal contact (connectivity 2) is short by 3/8 px.  ``max_gap`` (pixels, float >= 0) keeps the pairs with gap8 <= the
+         largest integer k with k / 8 <= max_gap.
+      6. Output.  edge_index in ``radius_knn``'s convention: rows are centres in ascending order, then columns in ascending order.
+         Both directions of every pair are present; (i, i) is present for every node iff ``loop``.  border = the pair's contacts (0
+         on loops), gap = gap8 / 8 (0 on loops).
+
+    Host syncs: one read that checks the labels' sign (and kept_labels' order), one for the distinct labels when kept_labels is None,
+    the two of region_adjacency, and one for the pairs ``max_gap`` keeps."""
+    _check_labels32('voronoi_graph', 'labels', labels)
+    _check_connectivity(connectivity)
+    d2max = _d2max(max_distance, 'max_distance')
+    g8max = None if max_gap is None else _bound(max_gap, 'max_gap', lambda d: d * 8, lambda k: k / 8, INT32_MAX)
+    dev = labels.device
+    if kept_labels is not None:
+        if not torch.is_tensor(kept_labels) or kept_labels.dtype != torch.int32 or kept_labels.dim() != 1 or kept_labels.device != dev:
+            raise ValueError('voronoi_graph: kept_labels must be a 1-D int32 tensor on the device of labels')
+    labels = labels.to(torch.int32)
+    checks = [labels.min() < 0 if labels.numel() else torch.zeros((), dtype=torch.bool, device=dev)]
+    if kept_labels is not None:
+        checks.append((kept_labels[:1] <= 0).any() | (kept_labels[1:] <= kept_labels[:-1]).any())
+    checks = torch.stack(checks).tolist()            # host sync: the labels' sign, the order of kept_labels
+    if checks[0]:
+        raise ValueError('voronoi_graph: negative labels in the instance mask')
+    if kept_labels is None:
+        kept_labels = torch.unique(labels[labels != 0])      # host sync: the distinct labels, ascending
+        kept = labels
+    else:
+        if checks[1]:
+            raise ValueError('voronoi_graph: kept_labels must be positive and strictly ascending')
+        if kept_labels.numel() == 0:
+            kept = torch.zeros_like(labels)
+        else:
+            slot = torch.searchsorted(kept_labels, labels).clamp_(max=kept_labels.numel() - 1)
+            kept = torch.where(kept_labels[slot] == labels, labels, 0)
+    n = int(kept_labels.numel())
+    i64 = dict(dtype=torch.int64, device=dev)
+    src = dst = torch.empty(0, **i64)
+    border, gap8 = torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, **i64)
+    if n > 0 and labels.numel() > 0:
+        cells, dist2 = _grow_euclidean(kept, d2max)
+        t = torch.where(dist2 == EDT_INF, 0, _eighths(dist2))
+        pairs, border, min_sum = region_adjacency(cells, connectivity, value=t)
+        gap8 = min_sum.to(torch.int64) + 8
+        if g8max is not None:
+            keep = gap8 <= g8max
+            pairs, border, gap8 = pairs[keep], border[keep], gap8[keep]      # host sync: how many pairs are kept
+        ends = torch.searchsorted(kept_labels, pairs).to(torch.int64)       # every cell's label is a kept one
+        src, dst = ends[:, 0], ends[:, 1]
+    rows, cols = torch.cat([src, dst]), torch.cat([dst, src])
+    border, gap8 = torch.cat([border, border]), torch.cat([gap8, gap8])
+    if loop:
+        nodes = torch.arange(n, **i64)
+        rows, cols = torch.cat([rows, nodes]), torch.cat([cols, nodes])
+        border, gap8 = torch.cat([border, torch.zeros(n, dtype=torch.int32, device=dev)]), torch.cat([gap8, torch.zeros(n, **i64)])
+    order = torch.argsort(rows * max(n, 1) + cols)       # (row, col) pairs are distinct
+    edge_index = torch.stack([rows[order], cols[order]])
+    if return_attr:
+        return edge_index, border[order], (gap8[order].to(torch.float64) / 8).to(torch.float32)
+    return edge_index
 
 
 def nucleus_features(labels, gray, min_size=10, return_info=False, max_label=None):
@@ -1025,13 +1157,21 @@ def normalize_stains(image, stains=None, order='bgr', target_stains=None, target
     return out
 
 
-def graph_item(features, centroids, y):
+def graph_item(features, centroids, y, edge_index=None):
     """The ``Data`` of prepare_cv_dataset.py:57-72 (_read_one_raw_graph): x = cat(features, centroids) [n, 18], pos = centroids,
-    y = [label], on the host -- ready for ``Batch.from_data_list(items, device=..., knn=(100, 8), mean=..., std=...)``."""
+    y = [label], on the host -- ready for ``Batch.from_data_list(items, device=..., knn=(100, 8), mean=..., std=...)``.  With
+    ``edge_index`` ([2, E], e.g. ``voronoi_graph``'s) the ``Data`` carries it on the host as int64, and
+    ``Batch.from_data_list(items, device=...)`` without ``knn=`` uses it."""
     from .data import Data
     f = torch.as_tensor(features).detach().to('cpu', torch.float32)
     c = torch.as_tensor(centroids).detach().to('cpu', torch.float32)
-    return Data(x=torch.cat([f, c], dim=1), pos=c.clone(), y=torch.tensor([int(y)], dtype=torch.long))
+    item = Data(x=torch.cat([f, c], dim=1), pos=c.clone(), y=torch.tensor([int(y)], dtype=torch.long))
+    if edge_index is not None:
+        e = torch.as_tensor(edge_index).detach().to('cpu', torch.int64)
+        if e.dim() != 2 or e.shape[0] != 2:
+            raise ValueError('edge_index must be [2, E] (got %s)' % (tuple(e.shape),))
+        item.edge_index = e.contiguous()
+    return item
 
 
 def save_reference_files(root, dataset, label_dir, name, features, centroids):

@@ -68,8 +68,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *  16: a tile's own stain vectors (Macenko): cgc_scan_chunk_pixels, cgc_od_moments, cgc_angle_bins, cgc_angle_histogram_ws_bytes,
  *      cgc_angle_histogram
  *  17: stain normalisation: cgc_concentration_bins, cgc_concentration_histogram, cgc_exp_lut_len, cgc_od_recolor_ws_bytes,
- *      cgc_od_recolor */
-#define CGC_ABI_VERSION 17
+ *      cgc_od_recolor
+ *  18: region adjacency of a label image: cgc_adjacency_tile_side, cgc_adjacency_ws_bytes, cgc_adjacency_count,
+ *      cgc_adjacency_records, cgc_adjacency_merge_ws_bytes, cgc_adjacency_heads, cgc_adjacency_merge */
+#define CGC_ABI_VERSION 18
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -343,6 +345,38 @@ int cgc_exp_lut_len(void);
 int64_t cgc_od_recolor_ws_bytes(void);
 int cgc_od_recolor(const uint8_t* pix, int64_t npix, int order, const int* lut, const int* a, const int* exp_lut, int exp_len, void* ws,
                    uint8_t* out, cgc_stream_t stream);
+
+/* ---- F13 (behind F5/F6, in front of A1): region adjacency of a label image (csrc/adjacency.hip): which regions touch, along how many
+ * pixel pairs, and the smallest value[p] + value[q] over each pair's contacts -- on the cells of expand_labels, the edges of the Voronoi
+ * cell graph (cgc-net_amd/nuclei.py voronoi_graph).  The contract item by item: cgc-net_amd/kernels.py KernelSpec.region_adjacency.
+ * labels, value_or_null int32 [H, W], contiguous, 0 = background, every other value (negative ones too) a region; H * W < 2^29, so that a
+ * pair's count (at most 4 H W) fits int32 -- otherwise CGC_EINVAL and nothing is launched.  connectivity 1 (right and lower neighbour)
+ * or 2 (also the two lower diagonals): every unordered pair of neighbouring pixels is looked at once.  A record is (key, count, sum): key
+ * = ((int64)a << 32) | ((uint32)b ^ 0x80000000) for a < b as signed integers, whose int64 order is the lexicographic order of (a, b).
+ *   cgc_adjacency_tile_side: the side (64) of the tiles one workgroup folds in LDS.
+ *   cgc_adjacency_count: ws = cgc_adjacency_ws_bytes(H, W) bytes.  Counts the records every tile will write -- its distinct pairs, or,
+ *     for a tile with more than 512 of them, its contacts -- and scans the counts; *n_records_out (device) = their total.  H * W = 0:
+ *     only *n_records_out = 0 is written.
+ *   cgc_adjacency_records: after the host has read n_records; the same labels, connectivity and ws.  Out: keys int64 [n_records],
+ *     counts int32 [n_records], sums int32 [n_records] (iff value is given: the smallest value[p] + value[q], summed in 64 bits and
+ *     clamped to int32), grouped by tile, in any order inside a tile.
+ *   cgc_adjacency_heads: sorted_keys = the keys in ascending order; ws = cgc_adjacency_merge_ws_bytes(n_records) bytes;
+ *     *n_pairs_out (device) = the number of distinct keys.
+ *   cgc_adjacency_merge: after the host has read n_pairs; perm int64 [n_records] = the permutation that sorted the keys (sorted_keys[i] =
+ *     keys[perm[i]]), counts / sums as cgc_adjacency_records wrote them, ws untouched since cgc_adjacency_heads.  Out: pairs int32
+ *     [n_pairs, 2] ascending, count int32 [n_pairs] = sum of the records' counts, min_sum int32 [n_pairs] = minimum of their sums (iff
+ *     sums are given).
+ * The library allocates nothing and reads nothing on the host; no workgroup waits for another one; integer sums and minima make the
+ * outputs independent of the order in which tables and records are filled. */
+int cgc_adjacency_tile_side(void);
+int64_t cgc_adjacency_ws_bytes(int H, int W);
+int cgc_adjacency_count(const int* labels, int H, int W, int connectivity, void* ws, int* n_records_out, cgc_stream_t stream);
+int cgc_adjacency_records(const int* labels, const int* value_or_null, int H, int W, int connectivity, void* ws, int64_t n_records,
+                          int64_t* keys, int* counts, int* sums_or_null, cgc_stream_t stream);
+int64_t cgc_adjacency_merge_ws_bytes(int64_t n_records);
+int cgc_adjacency_heads(const int64_t* sorted_keys, int64_t n_records, void* ws, int* n_pairs_out, cgc_stream_t stream);
+int cgc_adjacency_merge(const int64_t* sorted_keys, const int64_t* perm, const int* counts, const int* sums_or_null, int64_t n_records,
+                        const void* ws, int n_pairs, int* pairs, int* count, int* min_sum_or_null, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
