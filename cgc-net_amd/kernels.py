@@ -30,6 +30,7 @@ ANGLE_DIR_MAX = 16384      # angle_histogram's directions: |c_k|, |s_k|
 CONC_BINS = 512            # concentration_histogram: levels of 1/128 of a natural-log unit per stain, the last one open (3.99 and up)
 EXP_LUT_LEN = 6386         # od_recolor's exponential table: floor(255 exp(-k / 1024) + 0.5) is 255 at k = 0 and first 0 at k = 6385
 SMOOTH_MAX_RADIUS = 5      # binomial_smooth: 255 * 4^(2 * 5) < 2^31
+WINDOW_MAX_RADIUS = 127    # window_sums / local_threshold: n <= 255^2, so that Q <= 255^4 < 2^32 and everything of the rule fits int64
 ADJ_MAX_PIXELS = 2 ** 29   # region_adjacency: a pair's count can reach 4 H W and must fit int32
 WS_JUMP_BATCH = 8         # pointer jumps of watershed_flood per host read: resolves parent chains of up to 2^7 pixels in one read
 
@@ -394,6 +395,50 @@ class KernelSpec(object):
             border is replicated, and there is ONE rounding (half up), after both passes.  Everything is exact in int32: 255 * 2^20 <
             2^31.  r = 0 is a copy (no rounding term).
         4.  H < r or W < r are ordinary shapes: the clamp covers them.  H * W = 0 gives an empty output."""
+        raise NotImplementedError
+
+    def window_sums(self, image, radius, within=None):
+        """The number, the sum and the sum of squares of the pixels in a square window around every pixel (F14, behind the stain
+        plane; csrc/window.hip): the primitive under every local statistic.  Returns (n int32, S int32, Q int64), each [H, W] and
+        contiguous; no host read.
+
+        1.  image: uint8 [H, W], any strides, H * W < 2^31.  radius r: an integer in 0..WINDOW_MAX_RADIUS = 127 (ValueError otherwise;
+            the library returns CGC_EINVAL and launches nothing).
+        2.  The window of pixel (y, x) is rows y - r .. y + r and columns x - r .. x + r, CLIPPED to the image: nothing is replicated
+            or reflected, border windows are smaller, and r may exceed either side.
+        3.  within: None or [H, W] of a 1-, 2-, 4- or 8-byte integer type or bool, any strides; only "is zero" is read.  A pixel of the
+            window is *counted* iff within is None or within is non-zero there.  The centre pixel has no special role: outputs are
+            defined at every pixel, selected or not.
+        4.  n = the number of counted pixels, S = the sum of their values, Q = the sum of their squares.  Bounds: n <= 255^2 = 65 025,
+            S <= 255 n = 16 581 375, Q <= 255^2 n = 4 228 250 625, which is above 2^31 and below 2^32: Q is int64.
+        5.  H * W = 0 gives empty outputs; a within that selects nothing gives zeros.
+        6.  One launch, no atomics, integer arithmetic: bit-identical from call to call.
+        Widths inside the kernel ("Window sums and local thresholds"): a workgroup scans the per-column sums of 1024
+        columns in uint32.  The scans of n and S are exact (<= 1024 * 255 and 1024 * 255^2); the scan of Q passes 2^32 and wraps, and a
+        window's Q, a difference of two entries and itself below 2^32, is exact modulo 2^32.  A tile is ``window_tile_rows`` (16) rows
+        by ``window_strip_cols(r)`` (1024 - 2 * (r rounded up to a multiple of 4)) columns."""
+        raise NotImplementedError
+
+    def local_threshold(self, image, radius, k64, offset, floor, within=None):
+        """The local mean / Niblack threshold of one uint8 image, fused with the window sums it needs (F14; csrc/window.hip, the same
+        kernel as window_sums with another epilogue: n, S and Q are never written to memory).  Returns uint8 [H, W] of 0 / 1,
+        contiguous; no host read.
+
+        1.  image, radius, within, n, S, Q: exactly as window_sums, items 1-4.
+        2.  k64: an integer in -128..128, 64 times Niblack's k, so |k| <= 2.  offset c: an integer in -255..255.  floor: an integer in
+            -1..255, -1 meaning no floor.  (ValueError otherwise, before any launch; the library returns CGC_EINVAL.)
+        3.  With v the pixel's own value -- read whatever `within` says there -- m = S / n and s^2 = Q / n - m^2, a pixel is
+            foreground iff n >= 1 and v > floor and v > m + k s + c.  A pixel outside `within` is still decided, from the counted
+            pixels of its window.
+        4.  The decision is made in exact integers, never in floating point.  L = 64 (n v - S - c n), D = n Q - S^2 >= 0 (n^2 times
+            the variance).  k64 >= 0: foreground iff L > 0 and L^2 > k64^2 D.  k64 < 0: foreground iff L > 0, or (L = 0 and D > 0),
+            or (L < 0 and L^2 < k64^2 D).
+        5.  Equality is not foreground: in the 1 x 5 image [0, 0, 0, 0, 200] with r = 4, c = 0 and no floor the last pixel has
+            m + 2 s = v exactly; it is 0 at k64 = 128 and 1 at k64 = 127.  A constant window has D = 0: c = 0 gives nothing, c = -1
+            everything.
+        6.  Everything fits int64: |L| <= 64 * 2 * 255 * 65 025 < 2^31.0, so L^2 < 2^62.0; D <= n^2 * 255^2 / 4 <= 6.874e13, so
+            k64^2 D <= 1.13e18 < 2^63 = 9.22e18.
+        7.  H * W = 0 gives an empty output; where nothing is counted (n = 0) the pixel is background."""
         raise NotImplementedError
 
     def region_adjacency(self, labels, connectivity, value=None):
@@ -766,6 +811,7 @@ class HipKernels(KernelSpec):
         self._ws_cache = {}
         self._graph_local_max = int(self.lib.cgc_graph_local_max_nodes())
         self.histogram_chunk = int(self.lib.cgc_histogram_chunk_pixels())      # pixels one workgroup of histogram_u8 counts (tests)
+        self.window_tile_rows = int(self.lib.cgc_window_tile_rows())          # rows of the tiles of window_sums / local_threshold (tests)
         self.adjacency_tile = int(self.lib.cgc_adjacency_tile_side())          # side of the tiles region_adjacency folds in LDS (tests)
         self.scan_chunk = int(self.lib.cgc_scan_chunk_pixels())                # ... and of od_moments / angle_histogram
         self._dirs_checked = (None, None)                                      # angle_histogram's last direction table and its C array
@@ -1265,6 +1311,45 @@ class HipKernels(KernelSpec):
         H, W = image.shape
         out = torch.empty(H, W, dtype=torch.uint8, device=image.device)
         self._chk(self.lib.cgc_binomial_smooth_u8(_ptr(image), H, W, int(radius), _ptr(out), self._stream()), 'cgc_binomial_smooth_u8')
+        return out
+
+    @staticmethod
+    def _check_window_radius(fn, radius):
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= WINDOW_MAX_RADIUS:
+            raise ValueError('%s: radius must be an integer in 0..%d, got %r' % (fn, WINDOW_MAX_RADIUS, radius))
+
+    @staticmethod
+    def _check_rule(k64, offset, floor):
+        for name, value, lo, hi in (('k64', k64, -128, 128), ('offset', offset, -255, 255), ('floor', floor, -1, 255)):
+            if isinstance(value, bool) or not isinstance(value, int) or not lo <= value <= hi:
+                raise ValueError('local_threshold: %s must be an integer in %d..%d, got %r' % (name, lo, hi, value))
+
+    def _window_images(self, image, within):
+        assert image.dtype == torch.uint8 and (within is None or within.shape == image.shape)
+        return self._image(image), self._image(within)      # after the refusals: may copy
+
+    def window_strip_cols(self, radius):
+        """Columns of the tiles of window_sums / local_threshold at this radius (tests place windows across tile edges)."""
+        return int(self.lib.cgc_window_strip_cols(int(radius)))
+
+    def window_sums(self, image, radius, within=None):
+        HipKernels._check_window_radius('window_sums', radius)
+        image, within = self._window_images(image, within)
+        H, W = image.shape
+        n, s = (torch.empty(H, W, dtype=torch.int32, device=image.device) for _ in range(2))
+        q = torch.empty(H, W, dtype=torch.int64, device=image.device)
+        self._chk(self.lib.cgc_window_sums(_ptr(image), _ptr(within), within.element_size() if within is not None else 0, H, W, radius,
+                                           _ptr(n), _ptr(s), _ptr(q), self._stream()), 'cgc_window_sums')
+        return n, s, q
+
+    def local_threshold(self, image, radius, k64, offset, floor, within=None):
+        HipKernels._check_window_radius('local_threshold', radius)
+        HipKernels._check_rule(k64, offset, floor)
+        image, within = self._window_images(image, within)
+        H, W = image.shape
+        out = torch.empty(H, W, dtype=torch.uint8, device=image.device)
+        self._chk(self.lib.cgc_local_threshold(_ptr(image), _ptr(within), within.element_size() if within is not None else 0, H, W,
+                                               radius, k64, offset, floor, _ptr(out), self._stream()), 'cgc_local_threshold')
         return out
 
     def region_adjacency(self, labels, connectivity, value=None):

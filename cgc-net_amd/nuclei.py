@@ -40,6 +40,12 @@ kernels.KernelSpec.od_recolor).  With normalisation in front, the stage reads
     nucleus_features(L, bgr_to_gray(norm), max_label=n)
 where ``TARGET_STAINS + residual`` stands for the 3 x 3 vectors made of the two target rows plus their cross product.
 
+``local_threshold`` is the local counterpart of ``plane > otsu_threshold(plane)``: every pixel is compared with the mean, and
+optionally the spread (Niblack), of the window around it, so that a tile whose staining or density varies keeps its pale side and
+does not merge its crowded side (csrc/window.hip; kernels.KernelSpec.local_threshold -- exact integers, one byte read and one
+written per pixel).  ``window_sums`` is the primitive under it, for rules of one's own: count, sum and sum of squares of every
+window, over the pixels of ``within`` only if wanted.  ``local_stain_foreground`` is ``stain_foreground`` with the local rule.
+
 ``region_adjacency`` reads off a label image which regions touch and along how many pixels (csrc/adjacency.hip;
 kernels.KernelSpec.region_adjacency), and ``voronoi_graph`` builds on it the other standard cell graph of the literature: the cells of
 ``expand_labels`` are the discrete Voronoi partition of the instance mask, and two nuclei are joined iff their cells share a border.
@@ -871,6 +877,100 @@ def stain_foreground(image, stain=0, radius=2, stains=None, order='bgr', within=
     plane = smooth(separate_stains(image, stains, order, (int(stain),))[0], radius)
     t = otsu_threshold(plane, within)
     return plane > t, t, plane
+
+
+def _check_int_in(name, value, lo, hi):
+    if isinstance(value, bool):
+        raise ValueError('%s must be an integer in %d..%d (got %r)' % (name, lo, hi, value))
+    try:
+        value = operator.index(value)
+    except TypeError:
+        raise ValueError('%s must be an integer in %d..%d (got %r)' % (name, lo, hi, value))
+    if not lo <= value <= hi:
+        raise ValueError('%s must be an integer in %d..%d (got %r)' % (name, lo, hi, value))
+    return value
+
+
+def _check_window(window):
+    return _check_int_in('the window radius', window, 0, kernels.WINDOW_MAX_RADIUS)
+
+
+def window_sums(image, radius, within=None):
+    """Count, sum and sum of squares of the pixels around every pixel of a uint8 [H, W] tensor on the GPU (any strides; other dtypes
+    are a TypeError): the window of (y, x) is rows y - radius .. y + radius and columns x - radius .. x + radius, clipped to the image
+    -- nothing is replicated, border windows are smaller -- and ``radius`` is an integer in 0..127.  With ``within`` (bool / integer,
+    same shape and device) only the pixels where it is non-zero count, which a stock box filter cannot give: statistics over tissue
+    only.  Returns (n int32, S int32, Q int64), each [H, W]: mean = S / n, variance = Q / n - mean^2 wherever n > 0
+    (kernels.KernelSpec.window_sums).  A ``within`` that selects nothing gives zeros, an empty image empty outputs.
+
+    Host syncs: none."""
+    _check_gray('window_sums', image, within)
+    radius = _check_window(radius)
+    with torch.cuda.device(image.device):
+        return kernels.get().window_sums(image, radius, within)
+
+
+def niblack_k64(k):
+    """The integer the local rule uses for a real k: floor(64 k + 1/2), computed exactly (``Fraction``), in -128..128 -- k = 0.2 is
+    13 / 64 = 0.203.  ValueError for a bool, a value that is not a real number, a non-finite one, or a result out of range."""
+    if isinstance(k, bool) or not isinstance(k, numbers.Real):
+        raise ValueError('k must be a real number (got %r)' % (k,))
+    try:
+        exact = k if isinstance(k, numbers.Rational) else float(k)      # numpy scalars and the like: their exact value as a float
+        if isinstance(exact, float) and not math.isfinite(exact):
+            raise ValueError
+        k64 = math.floor(Fraction(exact) * 64 + Fraction(1, 2))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError('k must be a finite real number (got %r)' % (k,))
+    if not -128 <= k64 <= 128:
+        raise ValueError('k must lie in -2..2 (got %r)' % (k,))
+    return k64
+
+
+def local_threshold(image, radius, k=0.0, offset=0, floor=None, within=None):
+    """The local mean / Niblack threshold of a uint8 [H, W] tensor on the GPU (any strides): a pixel of value v is foreground iff
+    v > m + k s + offset, with m and s the mean and the standard deviation of the window of ``radius`` (0..127) around it, clipped to
+    the image and, with ``within``, taken over its non-zero pixels only (a pixel outside ``within`` is still decided, from the counted
+    pixels of its window; where none is counted it is background).  ``k``: a real number in -2..2, used as niblack_k64(k) / 64; k = 0
+    is the local mean rule, Niblack's text binarisation uses k < 0, bright objects on a varying background k >= 0 with an ``offset``
+    (an integer in -255..255) of about half their contrast.  ``floor``: None or an integer in 0..255 -- also require v > floor.
+    Returns bool [H, W].  The decision is made in exact integers (kernels.KernelSpec.local_threshold): the map is a pure function of
+    its inputs, and a pixel that sits exactly on the rule is background.
+
+    Host syncs: none."""
+    _check_gray('local_threshold', image, within)
+    radius = _check_window(radius)
+    k64 = niblack_k64(k)
+    offset = _check_int_in('offset', offset, -255, 255)
+    floor = -1 if floor is None else _check_int_in('floor', floor, 0, 255)
+    with torch.cuda.device(image.device):
+        return kernels.get().local_threshold(image, radius, k64, offset, floor, within).view(torch.bool)
+
+
+def local_stain_foreground(image, window, stain=0, radius=2, stains=None, order='bgr', within=None, k=0.0, offset=0, floor=None):
+    """stain_foreground with a local threshold: plane = smooth(separate_stains(image, stains, order, (stain,))[0], radius) exactly as
+    there, fg = local_threshold(plane, window, k, offset, floor, within).  ``window``: the radius of the statistics' window, 0..127 --
+    a few nucleus diameters; ``k``, ``offset``, ``within``: as local_threshold.  ``floor``: None, an integer in 0..255, or 'otsu':
+    the floor is otsu_threshold(plane, within), so that the local rule only removes pixels from the global foreground.  Returns
+    (fg bool [H, W], the floor used or None, plane uint8 [H, W]); fg goes where stain_foreground's goes:
+        L, n = split_touching(fill_holes(fg), None, markers='h_maxima', growth='flood', h=2.0)
+
+    Host syncs: none; one, that of otsu_threshold, with floor='otsu'."""
+    _check_color('local_stain_foreground', image)
+    _check_planes((stain,))
+    if order not in STAIN_ORDERS:
+        raise ValueError("order must be 'bgr' or 'rgb', got %r" % (order,))
+    radius = _check_radius(radius)
+    window = _check_window(window)
+    _check_within('local_stain_foreground', within, image[:, :, 0])
+    niblack_k64(k)
+    _check_int_in('offset', offset, -255, 255)
+    if floor is not None and not (isinstance(floor, str) and floor == 'otsu'):
+        floor = _check_int_in('floor', floor, 0, 255)
+    plane = smooth(separate_stains(image, stains, order, (int(stain),))[0], radius)
+    if floor == 'otsu':
+        floor = otsu_threshold(plane, within)
+    return local_threshold(plane, window, k, offset, floor, within), floor, plane
 
 
 def _od_min(beta):

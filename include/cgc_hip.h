@@ -70,8 +70,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *  17: stain normalisation: cgc_concentration_bins, cgc_concentration_histogram, cgc_exp_lut_len, cgc_od_recolor_ws_bytes,
  *      cgc_od_recolor
  *  18: region adjacency of a label image: cgc_adjacency_tile_side, cgc_adjacency_ws_bytes, cgc_adjacency_count,
- *      cgc_adjacency_records, cgc_adjacency_merge_ws_bytes, cgc_adjacency_heads, cgc_adjacency_merge */
-#define CGC_ABI_VERSION 18
+ *      cgc_adjacency_records, cgc_adjacency_merge_ws_bytes, cgc_adjacency_heads, cgc_adjacency_merge
+ *  19: window sums and the local (mean / Niblack) threshold: cgc_window_max_radius, cgc_window_tile_rows, cgc_window_strip_cols,
+ *      cgc_window_sums, cgc_local_threshold */
+#define CGC_ABI_VERSION 19
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -377,6 +379,29 @@ int64_t cgc_adjacency_merge_ws_bytes(int64_t n_records);
 int cgc_adjacency_heads(const int64_t* sorted_keys, int64_t n_records, void* ws, int* n_pairs_out, cgc_stream_t stream);
 int cgc_adjacency_merge(const int64_t* sorted_keys, const int64_t* perm, const int* counts, const int* sums_or_null, int64_t n_records,
                         const void* ws, int n_pairs, int* pairs, int* count, int* min_sum_or_null, cgc_stream_t stream);
+
+/* ---- F14 (behind F10's plane, in front of F5): window sums of a uint8 image and the local threshold on them (csrc/window.hip).  The
+ * contract item by item: cgc-net_amd/kernels.py KernelSpec.window_sums / local_threshold.  img uint8 [H, W], contiguous, H * W < 2^31;
+ * radius r in 0..127: the window of (y, x) is rows y - r .. y + r and columns x - r .. x + r, clipped to the image.  within_or_null [H, W]
+ * of within_bytes (1, 2, 4 or 8) bytes per element, of which only "is zero" is read: only pixels with within != 0 count.
+ *   cgc_window_sums: n int32, s int32, q int64, each [H, W]: the number, the sum and the sum of squares of the counted pixels.
+ *   cgc_local_threshold: out uint8 [H, W] of 0 / 1.  With v the pixel's own value (read whatever `within` says), L = 64 (n v - s -
+ *     offset n) and D = n q - s^2: out = 1 iff n >= 1 and v > floor and
+ *       k64 >= 0: L > 0 and L^2 > k64^2 D;      k64 < 0: L > 0, or (L = 0 and D > 0), or (L < 0 and L^2 < k64^2 D)
+ *     -- v > m + (k64 / 64) sd + offset with m = s / n, sd^2 = q / n - m^2, in int64; equality is not foreground.  k64 in -128..128,
+ *     offset in -255..255, floor in -1..255 (-1: no floor).  n, s and q are never written to memory: one byte read, one written.
+ *   cgc_window_max_radius (127), cgc_window_tile_rows (16), cgc_window_strip_cols(radius) (1024 - 2 * (radius rounded up to a multiple
+ *     of 4); 0 for a radius out of range): the tile one workgroup owns, for tests that place windows across tile edges.
+ * One launch per call, no workspace, no atomics: outputs are bit-identical from call to call.  Bad dims, a radius, k64, offset or floor
+ * out of range, within_bytes other than 1, 2, 4, 8 (with a within), or a null pointer with H * W > 0: CGC_EINVAL, nothing launched.
+ * H * W = 0: nothing to do, 0. */
+int cgc_window_max_radius(void);
+int cgc_window_tile_rows(void);
+int cgc_window_strip_cols(int radius);
+int cgc_window_sums(const uint8_t* img, const void* within_or_null, int within_bytes, int H, int W, int radius, int* n, int* s, int64_t* q,
+                    cgc_stream_t stream);
+int cgc_local_threshold(const uint8_t* img, const void* within_or_null, int within_bytes, int H, int W, int radius, int k64, int offset,
+                        int floor, uint8_t* out, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
