@@ -31,6 +31,10 @@ CONC_BINS = 512            # concentration_histogram: levels of 1/128 of a natur
 EXP_LUT_LEN = 6386         # od_recolor's exponential table: floor(255 exp(-k / 1024) + 0.5) is 255 at k = 0 and first 0 at k = 6385
 SMOOTH_MAX_RADIUS = 5      # binomial_smooth: 255 * 4^(2 * 5) < 2^31
 WINDOW_MAX_RADIUS = 127    # window_sums / local_threshold: n <= 255^2, so that Q <= 255^4 < 2^32 and everything of the rule fits int64
+MORPH_MAX_RADIUS = 63      # flat_morphology: a tile plus a halo of r on both sides is one 256-byte LDS row and keeps 128 columns of its own
+MORPH_KINDS = {'square': 0, 'disk': 1, 'diamond': 2}              # include/cgc_hip.h: CGC_MORPH_SQUARE / _DISK / _DIAMOND
+MORPH_OPS = {'erode': 0, 'dilate': 1, 'gradient': 2}              # CGC_MORPH_ERODE / _DILATE / _GRADIENT
+MORPH_EPILOGUES = {None: 0, 'other_minus': 1, 'minus_other': 2}   # CGC_MORPH_PLAIN / _OTHER_MINUS / _MINUS_OTHER
 ADJ_MAX_PIXELS = 2 ** 29   # region_adjacency: a pair's count can reach 4 H W and must fit int32
 WS_JUMP_BATCH = 8         # pointer jumps of watershed_flood per host read: resolves parent chains of up to 2^7 pixels in one read
 
@@ -441,6 +445,36 @@ class KernelSpec(object):
         7.  H * W = 0 gives an empty output; where nothing is counted (n = 0) the pixel is background."""
         raise NotImplementedError
 
+    def flat_morphology(self, image, kind, radius, op, within=None, other=None, epilogue=None):
+        """Erosion, dilation or morphological gradient of one uint8 image over a flat structuring element (F15, on the stain plane,
+        beside window_sums; csrc/morph.hip): the min / max filter under opening, closing, the top-hats and reconstruction's markers.
+        Returns uint8 [H, W], contiguous; no host read.
+
+        1.  image: uint8 [H, W], any strides, H * W < 2^31.  radius r: an integer in 0..MORPH_MAX_RADIUS = 63 (ValueError otherwise;
+            the library returns CGC_EINVAL and launches nothing).  kind: 'square', 'disk' or 'diamond'.
+        2.  The footprint is the set of offsets (dy, dx) with |dy| <= r and |dx| <= w(dy): w = r for the square, w = r - |dy| for the
+            diamond, and for the disk the largest integer with w^2 + dy^2 <= r^2 -- dx^2 + dy^2 <= r^2, skimage's disk(r), decided
+            in integers, never with a floating-point root.  r = 0 is the single pixel for every kind.
+        3.  The footprint is CLIPPED to the image: nothing is replicated or reflected, border footprints are smaller, and r may exceed
+            either side.
+        4.  within: None or [H, W] of a 1-, 2-, 4- or 8-byte integer type or bool, any strides; only "is zero" is read.  A pixel of the
+            footprint is *counted* iff it lies in the image and within is None or non-zero there.  The centre pixel has no special
+            role: outputs are defined at every pixel, selected or not.
+        5.  op 'erode': the minimum over the counted pixels, and 255, the neutral value, where none is counted.  'dilate': the
+            maximum, and 0 where none is counted.  'gradient': maximum minus minimum, both found in ONE pass, and 0 where none is
+            counted.  Bounds: every result lies in 0..255.
+        6.  epilogue None: the result is stored.  'other_minus': max(0, other - result).  'minus_other': max(0, result - other).
+            other: uint8 [H, W], any strides, read at the output pixel only (ValueError if an epilogue comes without it or it
+            without an epilogue).  The white top-hat is erode, then dilate with 'other_minus' against the image; the black
+            top-hat dilate, then erode with 'minus_other': two launches each and no subtraction pass.
+        7.  H * W = 0 gives an empty output.
+        8.  One launch, no workspace, no atomics, integer arithmetic: bit-identical from call to call.
+        Inside the kernel ("Flat morphology"): only maxima are taken -- the minimum is 255 - max(255 - v), so 0 is the one
+        neutral value -- over a table of run maxima M_k(y, x) = max over [x, x + 2^k) that is doubled in place in LDS; a footprint row
+        costs two byte reads per pixel whatever its length.  A tile is ``morph_tile_rows`` (32) rows by ``morph_tile_cols(r)`` (256 -
+        2 * (r rounded up to a multiple of 4)) columns."""
+        raise NotImplementedError
+
     def region_adjacency(self, labels, connectivity, value=None):
         """Region adjacency of one label image (F13, behind label_components / distance_transform; csrc/adjacency.hip): which
         regions touch, along how many pixel pairs, and how near they come.  Returns (pairs int32 [P, 2], count int32 [P], min_sum int32
@@ -812,6 +846,8 @@ class HipKernels(KernelSpec):
         self._graph_local_max = int(self.lib.cgc_graph_local_max_nodes())
         self.histogram_chunk = int(self.lib.cgc_histogram_chunk_pixels())      # pixels one workgroup of histogram_u8 counts (tests)
         self.window_tile_rows = int(self.lib.cgc_window_tile_rows())          # rows of the tiles of window_sums / local_threshold (tests)
+        self.morph_tile_rows = int(self.lib.cgc_morph_tile_rows())            # rows of the tiles of flat_morphology (tests)
+        assert int(self.lib.cgc_morph_max_radius()) == MORPH_MAX_RADIUS
         self.adjacency_tile = int(self.lib.cgc_adjacency_tile_side())          # side of the tiles region_adjacency folds in LDS (tests)
         self.scan_chunk = int(self.lib.cgc_scan_chunk_pixels())                # ... and of od_moments / angle_histogram
         self._dirs_checked = (None, None)                                      # angle_histogram's last direction table and its C array
@@ -1350,6 +1386,36 @@ class HipKernels(KernelSpec):
         out = torch.empty(H, W, dtype=torch.uint8, device=image.device)
         self._chk(self.lib.cgc_local_threshold(_ptr(image), _ptr(within), within.element_size() if within is not None else 0, H, W,
                                                radius, k64, offset, floor, _ptr(out), self._stream()), 'cgc_local_threshold')
+        return out
+
+    @staticmethod
+    def _check_morph(kind, radius, op, other, epilogue):
+        """The refusals of flat_morphology that need no tensor: returns the library's codes (kind, op, epilogue)."""
+        if not isinstance(kind, str) or kind not in MORPH_KINDS:
+            raise ValueError("flat_morphology: kind must be 'square', 'disk' or 'diamond', got %r" % (kind,))
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= MORPH_MAX_RADIUS:
+            raise ValueError('flat_morphology: radius must be an integer in 0..%d, got %r' % (MORPH_MAX_RADIUS, radius))
+        if not isinstance(op, str) or op not in MORPH_OPS:
+            raise ValueError("flat_morphology: op must be 'erode', 'dilate' or 'gradient', got %r" % (op,))
+        if not (epilogue is None or isinstance(epilogue, str)) or epilogue not in MORPH_EPILOGUES:
+            raise ValueError("flat_morphology: epilogue must be None, 'other_minus' or 'minus_other', got %r" % (epilogue,))
+        if (other is None) != (epilogue is None):
+            raise ValueError('flat_morphology: other and epilogue come together or not at all')
+        return MORPH_KINDS[kind], MORPH_OPS[op], MORPH_EPILOGUES[epilogue]
+
+    def morph_tile_cols(self, radius):
+        """Columns of the tiles of flat_morphology at this radius (tests place footprints across tile edges)."""
+        return int(self.lib.cgc_morph_tile_cols(int(radius)))
+
+    def flat_morphology(self, image, kind, radius, op, within=None, other=None, epilogue=None):
+        kind, op, epilogue = HipKernels._check_morph(kind, radius, op, other, epilogue)
+        assert image.dtype == torch.uint8 and (within is None or within.shape == image.shape)
+        assert other is None or (other.dtype == torch.uint8 and other.shape == image.shape)
+        image, within, other = self._image(image), self._image(within), self._image(other)      # after the refusals: may copy
+        H, W = image.shape
+        out = torch.empty(H, W, dtype=torch.uint8, device=image.device)
+        self._chk(self.lib.cgc_morph(_ptr(image), _ptr(within), within.element_size() if within is not None else 0, H, W, kind, radius,
+                                     op, _ptr(other), epilogue, _ptr(out), self._stream()), 'cgc_morph')
         return out
 
     def region_adjacency(self, labels, connectivity, value=None):

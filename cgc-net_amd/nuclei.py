@@ -46,6 +46,20 @@ does not merge its crowded side (csrc/window.hip; kernels.KernelSpec.local_thres
 written per pixel).  ``window_sums`` is the primitive under it, for rules of one's own: count, sum and sum of squares of every
 window, over the pixels of ``within`` only if wanted.  ``local_stain_foreground`` is ``stain_foreground`` with the local rule.
 
+``erode``, ``dilate`` and ``morph_gradient`` are the min / max filters over a flat square, disk or diamond (csrc/morph.hip;
+kernels.KernelSpec.flat_morphology -- one launch each, exact, clipped to the image and optionally to ``within``), and ``opening``,
+``closing``, ``white_tophat``, ``black_tophat``, ``open_by_reconstruction`` and ``close_by_reconstruction`` stand on them.  They sit
+on the stain plane, between ``separate_stains`` / ``smooth`` and the threshold: an opening removes specks smaller than the footprint
+where ``smooth`` would blur them, the white top-hat flattens an unevenly stained background before ``otsu_threshold``, and the
+gradient of the plane is the other standard height for ``watershed`` -- it puts the cut on the stain edge, where the negated distance
+map puts it on the geometric neck.  On a bool mask they are binary erosion and dilation with a square or diamond footprint (the EDT
+gives the Euclidean disk).  End to end:
+    plane = smooth(separate_stains(tile, planes=(0,))[0], 2)
+    flat = white_tophat(plane, 15)                       # nuclei stand out, the background is gone
+    fg = flat > otsu_threshold(flat)
+    markers, n = label_instances(erode(fg, 2))           # cores: what survives a small erosion
+    L = watershed(morph_gradient(plane, 1), markers, within=fg)
+
 ``region_adjacency`` reads off a label image which regions touch and along how many pixels (csrc/adjacency.hip;
 kernels.KernelSpec.region_adjacency), and ``voronoi_graph`` builds on it the other standard cell graph of the literature: the cells of
 ``expand_labels`` are the discrete Voronoi partition of the instance mask, and two nuclei are joined iff their cells share a border.
@@ -971,6 +985,121 @@ def local_stain_foreground(image, window, stain=0, radius=2, stains=None, order=
     if floor == 'otsu':
         floor = otsu_threshold(plane, within)
     return local_threshold(plane, window, k, offset, floor, within), floor, plane
+
+
+MORPH_MAX_RADIUS = kernels.MORPH_MAX_RADIUS
+MORPH_FOOTPRINTS = tuple(kernels.MORPH_KINDS)
+
+
+def _check_morph(fn, image, radius, footprint, within):
+    """The refusals the flat-morphology functions share, before any launch: returns (the image as uint8 -- a bool image as 0 / 1,
+    without a copy --, radius as an int)."""
+    _check_image(fn, 'image', image, (torch.bool, torch.uint8))
+    _check_within(fn, within, image)
+    radius = _check_int_in('radius', radius, 0, MORPH_MAX_RADIUS)
+    if not isinstance(footprint, str) or footprint not in kernels.MORPH_KINDS:
+        raise ValueError("footprint must be 'disk', 'square' or 'diamond', got %r" % (footprint,))
+    return (image.view(torch.uint8) if image.dtype == torch.bool else image), radius
+
+
+def _morph(x, footprint, radius, op, within, other=None, epilogue=None):
+    with torch.cuda.device(x.device):
+        return kernels.get().flat_morphology(x, footprint, radius, op, within, other, epilogue)
+
+
+def erode(image, radius, footprint='disk', within=None):
+    """Grey-scale erosion of a uint8 or bool [H, W] tensor on the GPU (any strides) by a flat structuring element: every pixel becomes
+    the minimum over its footprint.  ``footprint``: 'disk' (dx^2 + dy^2 <= radius^2, skimage's disk), 'square' (side 2 radius + 1) or
+    'diamond' (|dx| + |dy| <= radius); ``radius``: an integer in 0..63, 0 being the single pixel.  The footprint is clipped to the
+    image -- nothing is replicated, so the border never lowers a value -- and with ``within`` (bool / integer, same shape and device)
+    only the pixels where it is non-zero count; where none counts the result is 255, the neutral value (True for a bool image).  A bool
+    image counts as 0 / 1 and gives a bool result: binary erosion.  Other dtypes are a TypeError; int32 images are out of scope.
+    Exact, one launch (kernels.KernelSpec.flat_morphology).
+
+    Host syncs: none."""
+    x, radius = _check_morph('erode', image, radius, footprint, within)
+    out = _morph(x, footprint, radius, 'erode', within)
+    return out != 0 if image.dtype == torch.bool else out
+
+
+def dilate(image, radius, footprint='disk', within=None):
+    """Grey-scale dilation: every pixel becomes the maximum over its footprint; image, radius, footprint, within and the result as
+    erode.  Where no pixel counts the result is 0.  dilate(x) == 255 - erode(255 - x).
+
+    Host syncs: none."""
+    x, radius = _check_morph('dilate', image, radius, footprint, within)
+    out = _morph(x, footprint, radius, 'dilate', within)
+    return out != 0 if image.dtype == torch.bool else out
+
+
+def opening(image, radius, footprint='disk', within=None):
+    """dilate(erode(image)): removes bright structures that the footprint does not fit into and leaves the rest as it was; never above
+    the image, idempotent.  Arguments and result as erode; a bool image is computed as 0 / 1 and converted at the end.  Two launches.
+
+    Host syncs: none."""
+    x, radius = _check_morph('opening', image, radius, footprint, within)
+    out = _morph(_morph(x, footprint, radius, 'erode', within), footprint, radius, 'dilate', within)
+    return out != 0 if image.dtype == torch.bool else out
+
+
+def closing(image, radius, footprint='disk', within=None):
+    """erode(dilate(image)): fills dark gaps that the footprint does not fit into; never below the image, idempotent.  Arguments and
+    result as erode.  Two launches.
+
+    Host syncs: none."""
+    x, radius = _check_morph('closing', image, radius, footprint, within)
+    out = _morph(_morph(x, footprint, radius, 'dilate', within), footprint, radius, 'erode', within)
+    return out != 0 if image.dtype == torch.bool else out
+
+
+def white_tophat(image, radius, footprint='disk', within=None):
+    """image - opening(image): what the opening removed -- bright structures smaller than the footprint on a flattened background.
+    The standard correction for an unevenly stained tile in front of ``otsu_threshold``.  Arguments as erode; returns uint8 [H, W] (a
+    bool image counts as 0 / 1).  Two launches: the subtraction is fused into the dilation, clamped at 0 (without ``within`` the
+    opening is never above the image and the clamp never acts).
+
+    Host syncs: none."""
+    x, radius = _check_morph('white_tophat', image, radius, footprint, within)
+    return _morph(_morph(x, footprint, radius, 'erode', within), footprint, radius, 'dilate', within, x, 'other_minus')
+
+
+def black_tophat(image, radius, footprint='disk', within=None):
+    """closing(image) - image: dark structures smaller than the footprint.  Arguments and result as white_tophat.  Two launches.
+
+    Host syncs: none."""
+    x, radius = _check_morph('black_tophat', image, radius, footprint, within)
+    return _morph(_morph(x, footprint, radius, 'dilate', within), footprint, radius, 'erode', within, x, 'minus_other')
+
+
+def morph_gradient(image, radius, footprint='disk', within=None):
+    """The morphological gradient dilate(image) - erode(image): the local contrast, large on edges -- a height image for
+    ``watershed`` that puts the cut on the stain edge.  Arguments as erode; returns uint8 [H, W]; 0 where no pixel counts.  ONE
+    launch: both extrema are found in the same pass.
+
+    Host syncs: none."""
+    x, radius = _check_morph('morph_gradient', image, radius, footprint, within)
+    return _morph(x, footprint, radius, 'gradient', within)
+
+
+def open_by_reconstruction(image, radius, footprint='disk', connectivity=1, within=None):
+    """reconstruct(erode(image, radius, footprint, within), image, 'dilation', connectivity): like opening it removes what the
+    footprint does not fit into, but what survives the erosion gets its exact shape back.  opening <= open_by_reconstruction <= image.
+    image, radius, footprint, within: as erode; connectivity: as reconstruct.  Returns the image's dtype.
+
+    Host syncs: those of reconstruct."""
+    _check_morph('open_by_reconstruction', image, radius, footprint, within)
+    _check_connectivity(connectivity)
+    return reconstruct(erode(image, radius, footprint, within), image, 'dilation', connectivity)
+
+
+def close_by_reconstruction(image, radius, footprint='disk', connectivity=1, within=None):
+    """The dual: reconstruct(dilate(image, radius, footprint, within), image, 'erosion', connectivity).
+    image <= close_by_reconstruction <= closing.  Arguments and result as open_by_reconstruction.
+
+    Host syncs: those of reconstruct."""
+    _check_morph('close_by_reconstruction', image, radius, footprint, within)
+    _check_connectivity(connectivity)
+    return reconstruct(dilate(image, radius, footprint, within), image, 'erosion', connectivity)
 
 
 def _od_min(beta):

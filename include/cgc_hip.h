@@ -72,8 +72,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *  18: region adjacency of a label image: cgc_adjacency_tile_side, cgc_adjacency_ws_bytes, cgc_adjacency_count,
  *      cgc_adjacency_records, cgc_adjacency_merge_ws_bytes, cgc_adjacency_heads, cgc_adjacency_merge
  *  19: window sums and the local (mean / Niblack) threshold: cgc_window_max_radius, cgc_window_tile_rows, cgc_window_strip_cols,
- *      cgc_window_sums, cgc_local_threshold */
-#define CGC_ABI_VERSION 19
+ *      cgc_window_sums, cgc_local_threshold
+ *  20: flat grey-scale morphology (erode, dilate, gradient over a square, disk or diamond; fused top-hat subtraction):
+ *      cgc_morph_max_radius, cgc_morph_tile_rows, cgc_morph_tile_cols, cgc_morph_footprint_width, cgc_morph, CGC_MORPH_* */
+#define CGC_ABI_VERSION 20
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -402,6 +404,38 @@ int cgc_window_sums(const uint8_t* img, const void* within_or_null, int within_b
                     cgc_stream_t stream);
 int cgc_local_threshold(const uint8_t* img, const void* within_or_null, int within_bytes, int H, int W, int radius, int k64, int offset,
                         int floor, uint8_t* out, cgc_stream_t stream);
+
+/* ---- F15 (on F10's plane, beside F14): flat grey-scale morphology of a uint8 image (csrc/morph.hip).  The contract item by item:
+ * cgc-net_amd/kernels.py KernelSpec.flat_morphology.  img uint8 [H, W], contiguous, H * W < 2^31.  The footprint (kind, radius r in
+ * 0..63) is the set of offsets (dy, dx) with |dy| <= r and |dx| <= w(dy): w = r (square), the largest integer with w^2 + dy^2 <= r^2
+ * (disk, skimage's disk(r)), r - |dy| (diamond); r = 0 is the single pixel.  It is CLIPPED to the image: nothing is replicated.
+ * within_or_null [H, W] of within_bytes (1, 2, 4 or 8) bytes per element, of which only "is zero" is read: a footprint pixel is counted
+ * iff it lies in the image and within is non-zero there (or null).  The centre has no special role.
+ *   op ERODE: the minimum over the counted pixels, 255 where none is counted.  DILATE: the maximum, 0 where none is.  GRADIENT: maximum
+ *     minus minimum in one pass, 0 where none is counted.
+ *   epilogue PLAIN: out = result.  OTHER_MINUS: out = max(0, other - result).  MINUS_OTHER: out = max(0, result - other); other uint8
+ *     [H, W], read at the output pixel only (it may be the image of an earlier call; out must not overlap img).
+ *   cgc_morph_max_radius (63), cgc_morph_tile_rows (32), cgc_morph_tile_cols(radius) (256 - 2 * (radius rounded up to a multiple of 4);
+ *     0 for a radius out of range): the tile one workgroup owns, for tests that place footprints across tile edges.
+ *   cgc_morph_footprint_width(kind, radius, dy): w(dy) as the kernel uses it (host only); CGC_EINVAL for a bad kind, radius or |dy| > r.
+ * One launch per call, no workspace, no atomics: outputs are bit-identical from call to call.  Bad dims, a kind, radius, op or epilogue
+ * out of range, within_bytes other than 1, 2, 4, 8 (with a within), or a null img / out (or other, with an epilogue) with H * W > 0:
+ * CGC_EINVAL, nothing launched.  H * W = 0: nothing to do, 0. */
+#define CGC_MORPH_SQUARE 0
+#define CGC_MORPH_DISK 1
+#define CGC_MORPH_DIAMOND 2
+#define CGC_MORPH_ERODE 0
+#define CGC_MORPH_DILATE 1
+#define CGC_MORPH_GRADIENT 2
+#define CGC_MORPH_PLAIN 0
+#define CGC_MORPH_OTHER_MINUS 1
+#define CGC_MORPH_MINUS_OTHER 2
+int cgc_morph_max_radius(void);
+int cgc_morph_tile_rows(void);
+int cgc_morph_tile_cols(int radius);
+int cgc_morph_footprint_width(int kind, int radius, int dy);
+int cgc_morph(const uint8_t* img, const void* within_or_null, int within_bytes, int H, int W, int kind, int radius, int op,
+              const uint8_t* other_or_null, int epilogue, uint8_t* out, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
