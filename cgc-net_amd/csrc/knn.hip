@@ -3,9 +3,17 @@
 // r + 1e-8) per graph on the host (dataflow/data.py:246,255,297,348; dataflow/prepare_cv_dataset.py:102).
 //
 // Uniform-grid bucket search, a whole batch of graphs per call (block-diagonal: a node only sees its own graph):
-//   k_knn_bbox   one workgroup per graph: bounding box, cell size = max(r, sqrt(w h / n_g), max(w,h) / n_g)  (>= r so that
-//                the 3x3 neighbourhood is exhaustive; the other two terms bound the cell count by 3 n_g + 1 whatever the
-//                coordinates are), grid extent, and -- last graph done -- the per-graph cell offsets
+//   k_knn_bbox   one workgroup per graph: bounding box, cell size c = max(r + 1e-8, sqrt(w h / n_g), max(w,h) / n_g) (1 + 2^-18)
+//                rounded to float32 (the last two terms bound the cell count by 3 n_g + 1 whatever the coordinates are), grid
+//                extent, and -- last graph done -- the per-graph cell offsets
+//                Cell of a node: trunc(fl((x - minx) / c)), the difference and the quotient in fp64 (knn_cell_of).  Why the 3x3
+//                neighbourhood misses nobody: the distance test of k_knn_query accepts an axis separation a - b of at most
+//                (r + 1e-8)(1 + 2^-50), and c >= (r + 1e-8)(1 + 2^-18)(1 - 2^-24) > (r + 1e-8)(1 + 2^-19), so (a - b) / c
+//                < 1 - 2^-19 + 2^-37.  Each computed quotient is off by at most 2^-52 relative (two roundings) and is at most
+//                n_g < 2^31 (c >= max(w,h) / n_g), so q_a - q_b <= (a - b) / c + 2 * 2^-52 * 2^31 < 1 - 2^-21: the truncations differ by
+//                at most one.  (c = r with float32 arithmetic was not enough: 194 / 97 came out below 2 and 291 / 97 as 3, and a
+//                pair r + 1e-8 apart can straddle a whole cell of size r in exact arithmetic.)  The same margin keeps
+//                gx gy <= (w/c + 1)(h/c + 1) < n_g + 2 n_g + 1 through the roundings.
 //   k_knn_hist / k_knn_scan / k_knn_fill   counting sort of the nodes by cell
 //   k_knn_query  one thread per node: scans its 3x3 cells, squared distances in fp64 (the host tree works in double too),
 //                keeps the k+1 best (distance, index) pairs in registers (static insertion network) -> ELL rows sorted by
@@ -18,7 +26,7 @@
 #include "common.hpp"
 
 struct KnnGrid {          // per graph
-  float minx, miny, inv_cell;
+  float minx, miny, cell;
   int gx, gy, cell0;      // grid extent, first cell id
 };
 
@@ -48,15 +56,14 @@ __global__ __launch_bounds__(256) void k_knn_bbox(const float* __restrict__ pos,
     KnnGrid k;
     const int ng = hi - lo;
     if (ng <= 0) {
-      k.minx = k.miny = 0.f; k.inv_cell = 0.f; k.gx = k.gy = 0;
+      k.minx = k.miny = 0.f; k.cell = 1.f; k.gx = k.gy = 0;
     } else {
-      const float w = mxx - mnx, h = mxy - mny;
-      float cell = fmaxf(r, sqrtf(w * h / (float)ng));
-      cell = fmaxf(cell, fmaxf(w, h) / (float)ng);
-      if (!(cell > 0.f)) cell = 1.f;                           // r = 0 and all points coincident
-      k.minx = mnx; k.miny = mny; k.inv_cell = 1.f / cell;
-      k.gx = (int)(w * k.inv_cell) + 1;
-      k.gy = (int)(h * k.inv_cell) + 1;
+      const double w = (double)mxx - (double)mnx, h = (double)mxy - (double)mny;
+      double cell = fmax((double)r + 1e-8, sqrt(w * h / (double)ng));          // > 0 also for r = 0 and all points coincident
+      cell = fmax(cell, fmax(w, h) / (double)ng);
+      k.minx = mnx; k.miny = mny; k.cell = (float)(cell * (1.0 + 0x1p-18));   // +inf (huge r) puts every node in cell 0
+      k.gx = (int)(w / (double)k.cell) + 1;                                    // = cell of the rightmost node + 1, see knn_cell_of
+      k.gy = (int)(h / (double)k.cell) + 1;
     }
     k.cell0 = 0;
     grid[g] = k;
@@ -84,8 +91,9 @@ __device__ __forceinline__ int knn_graph_of(const int* __restrict__ gptr, int B,
 }
 
 __device__ __forceinline__ void knn_cell_of(const KnnGrid& k, float x, float y, int& cx, int& cy) {
-  cx = min(max((int)((x - k.minx) * k.inv_cell), 0), k.gx - 1);
-  cy = min(max((int)((y - k.miny) * k.inv_cell), 0), k.gy - 1);
+  const double c = (double)k.cell;                             // fp64 difference and quotient: the argument at the top of the file
+  cx = min(max((int)(((double)x - (double)k.minx) / c), 0), k.gx - 1);
+  cy = min(max((int)(((double)y - (double)k.miny) / c), 0), k.gy - 1);
 }
 
 __global__ void k_knn_hist(const float* __restrict__ pos, const int* __restrict__ gptr, int B, int n, const KnnGrid* __restrict__ grid,
