@@ -286,6 +286,12 @@ __global__ __launch_bounds__(JK_THREADS) void k_jk_bwd(const float* __restrict__
     }
 }
 
+// npad is the row stride of HS / CS / DHC and a third of DGT's / INT's: at least n and a multiple of 64.  k_jk_bwd_mfma walks the
+// npad / 32 node tiles in pairs (an odd count would put the second tile of the last pair past the end of every DGT / INT row),
+// and rows of DGT / INT that start 16-byte aligned keep the parameter-gradient GEMM on its 16-byte operand loads.  Checked by all
+// four entry points before anything is launched, so that a pair of buffers is valid for every one of them or for none.
+static bool jk_npad_ok(int n, int npad) { return npad >= n && npad % 64 == 0; }
+
 static void fill_weights(JkWeights& w, const float* const* lstm, const float* w_att, const float* b_att) {
   for (int d = 0; d < 2; ++d) {
     w.w_ih[d] = lstm[4 * d + 0];
@@ -332,7 +338,7 @@ static int launch_jk_bwd(const float* xs, const float* dout, int n, int npad, co
 extern "C" int cgc_jk_lstm_fwd(const float* xs, int n, int npad, int C, const float* const* lstm, const float* w_att,
                                const float* b_att, float* out, float* HS, float* CS, cgc_stream_t stream) {
   if (n <= 0) return 0;
-  if (npad < n) return CGC_EINVAL;
+  if (!jk_npad_ok(n, npad)) return CGC_EINVAL;
   JkWeights w;
   fill_weights(w, lstm, w_att, b_att);
   const int rc = jk_mfma_fwd(xs, n, npad, C, w, out, HS, CS, as_stream(stream));
@@ -349,7 +355,7 @@ extern "C" int cgc_jk_lstm_bwd(const float* xs, const float* dout, int n, int np
                                const float* w_att, const float* b_att, const float* HS, const float* CS, float* dxs, float* DGT,
                                float* INT, float* DHC, cgc_stream_t stream) {
   if (n <= 0) return 0;
-  if (npad < n) return CGC_EINVAL;
+  if (!jk_npad_ok(n, npad)) return CGC_EINVAL;
   JkWeights w;
   fill_weights(w, lstm, w_att, b_att);
   const int rc = jk_mfma_bwd(xs, dout, n, npad, C, w, HS, CS, dxs, DGT, INT, as_stream(stream));
@@ -370,7 +376,7 @@ extern "C" int cgc_jk_lstm_bwd_params(const float* xs, const float* dout, int n,
                                       const float* w_att, const float* b_att, const float* HS, const float* CS, float* dxs,
                                       float* G, float* ws, cgc_stream_t stream) {
   if (n <= 0) return 0;
-  if (npad < n) return CGC_EINVAL;
+  if (!jk_npad_ok(n, npad)) return CGC_EINVAL;
   JkWeights w;
   fill_weights(w, lstm, w_att, b_att);
   return jk_mfma_bwd_params(xs, dout, n, npad, C, w, HS, CS, dxs, G, ws, as_stream(stream));
@@ -381,7 +387,7 @@ extern "C" int cgc_jk_lstm_bwd_flat(const float* xs, const float* dout, int n, i
                                     const float* w_att, const float* b_att, const float* HS, const float* CS, float* dxs,
                                     float* flat, float* ws, cgc_stream_t stream) {
   if (n <= 0) return 0;
-  if (npad < n) return CGC_EINVAL;
+  if (!jk_npad_ok(n, npad)) return CGC_EINVAL;
   JkWeights w;
   fill_weights(w, lstm, w_att, b_att);
   return jk_mfma_bwd_flat(xs, dout, n, npad, C, w, HS, CS, dxs, flat, ws, as_stream(stream));

@@ -46,7 +46,21 @@ __device__ __forceinline__ float jk_rcp(float d) {
   const float r = __builtin_amdgcn_rcpf(d);
   return fmaf(fmaf(-d, r, 1.f), r, r);
 }
-__device__ __forceinline__ float fast_sigmoid(float x) { return jk_rcp(1.f + __expf(fminf(-x, 87.f))); }
+// exp(a), a <= 87, with a few ulp of relative error for every a.  __expf is v_exp_f32(t), t = a * log2(e): the rounding of that
+// product, and of the constant, is an ABSOLUTE error of the exponent, i.e. a relative error of the result that grows with |a|
+// (measured through the sigmoid's readout, in units of 2^-23: 4.4 up to a = 10, 14.5 at a = 27.6).  From t = 16 on (a >= 11.09),
+// where an ulp of t reaches 2^-19 and its rounding alone 5.5 units, the product's error r = a * log2(e) - t (two FMAs, log2(e) in
+// two pieces) is put back as exp2(t) * (1 + r ln 2): 2.3 units modelled with v_exp_f32 at 1 ulp.  Below, r is dropped and the value
+// is __expf(a) bit for bit: gates that are not deeply saturated keep the arithmetic every recorded output and margin was measured
+// with -- one ulp of a gate is amplified a thousandfold by the reference-generated fixtures (see fast_tanh), and without bound by
+// training steps (a benchmark run of 25 steps has gates at 8 < a < 11: with the cut at 8 all of its outputs moved).
+__device__ __forceinline__ float jk_exp(float a) {
+  const float t = a * 0x1.715476p+0f;
+  const float r = fmaf(a, 0x1.4ae0cp-26f, fmaf(a, 0x1.715476p+0f, -t));
+  const float e = __builtin_amdgcn_exp2f(t);
+  return fmaf(e, t >= 16.f ? r * 0x1.62e43p-1f : 0.f, e);
+}
+__device__ __forceinline__ float fast_sigmoid(float x) { return jk_rcp(1.f + jk_exp(fminf(-x, 87.f))); }
 // tanh with a few ulp of RELATIVE error everywhere.  The one-line form 2 / (1 + exp(-2x)) - 1 has ~2e-7 of ABSOLUTE error, i.e.
 // 2e-6 relative at |x| = 0.1 and 2e-4 at 1e-3 -- cell states and gate inputs of a freshly initialised LSTM are that small, and on
 // the reference-generated medium_shipped fixture the network amplifies it a thousandfold (a one-ulp perturbation of the parameters

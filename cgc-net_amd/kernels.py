@@ -628,7 +628,10 @@ class KernelSpec(object):
     def jk_fwd(self, xs, n, npad, C, lstm, w_att, b_att, out, HS, CS):
         """DenseJK forward (model/network.py:36-52): xs [n,3C] -> out [n,C].  ``lstm`` = 8 tensors
         (w_ih, w_hh, b_ih, b_hh) x (forward, reverse) in torch.nn.LSTM layout, hidden H = 3C/2.
-        HS, CS [6H, npad]: hidden / cell state of (direction d, step t, unit j) at row (d*3+t)*H + j."""
+        HS, CS [6H, npad]: hidden / cell state of (direction d, step t, unit j) at row (d*3+t)*H + j.
+        npad, here and in the three backward calls: npad >= n and npad % 64 == 0 (include/cgc_hip.h), else the call is refused
+        before anything is launched; ``jk_bwd_params`` may need npad % 256 == 0 (see there).  Columns >= n of HS / CS are never
+        read: the buffers need not be cleared."""
         raise NotImplementedError
 
     def jk_bwd(self, xs, dout, n, npad, C, lstm, w_att, b_att, HS, CS, dxs, DGT, INT, DHC):
@@ -640,7 +643,9 @@ class KernelSpec(object):
     def jk_bwd_params(self, xs, dout, n, npad, C, lstm, w_att, b_att, HS, CS, dxs, G_out):
         """DenseJK backward with the parameter gradients delivered directly: dxs [n,3C] and G_out [2, 4H+1, C+2H+1] with
         the meaning of ``DGT[d] @ INT[d]^T`` in ``jk_bwd`` (entries of the last row that are not parameter gradients are
-        unspecified)."""
+        unspecified).  Where the gradients are staged through DGT / INT (channel counts off the matrix cores, buffers that are
+        not 16-byte aligned) the product runs over K slices of 768 columns: npad % 256 == 0 there, else ValueError before
+        anything is launched.  ops._DenseJK pads to multiples of 1024."""
         raise NotImplementedError
 
     def jk_unpack_param_grads(self, G, C):
@@ -1660,16 +1665,21 @@ class HipKernels(KernelSpec):
                                              _ptr(HS), _ptr(CS), _ptr(dxs), _ptr(G_out), _ptr(ws), self._stream())
         if rc == 0:
             return
-        if rc != -1:
+        if rc != _EINVAL:
             self._chk(rc, 'cgc_jk_lstm_bwd_params')
         # unaligned buffers / other channel counts: staged path -- gate gradients and cell inputs transposed, one batched NT
         # GEMM per direction over K slices of 768 columns, combined deterministically
+        kp = 768
+        if npad < n or npad % 64 != 0:
+            raise ValueError('jk_bwd_params: npad = %d must be a multiple of 64 and at least n = %d' % (npad, n))
+        if ktot % kp != 0:          # (columns past the last whole slice would silently drop out of the gradients)
+            raise ValueError('jk_bwd_params: the staged parameter gradients (C = %d, or unaligned buffers) take npad %% 256 == 0, '
+                             'got %d' % (C, npad))
         dev = xs.device
         DGT = torch.empty(2, ng, ktot, dtype=torch.float32, device=dev)
         INT = torch.empty(2, ni, ktot, dtype=torch.float32, device=dev)
         DHC = torch.empty(2, 2, H, npad, dtype=torch.float32, device=dev)
         self.jk_bwd(xs, dout, n, npad, C, lstm, w_att, b_att, HS, CS, dxs, DGT, INT, DHC)
-        kp = 768
         parts = ktot // kp
         ws2 = torch.empty(parts, ng * ni, dtype=torch.float32, device=dev)
         for d in range(2):

@@ -74,8 +74,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *  19: window sums and the local (mean / Niblack) threshold: cgc_window_max_radius, cgc_window_tile_rows, cgc_window_strip_cols,
  *      cgc_window_sums, cgc_local_threshold
  *  20: flat grey-scale morphology (erode, dilate, gradient over a square, disk or diamond; fused top-hat subtraction):
- *      cgc_morph_max_radius, cgc_morph_tile_rows, cgc_morph_tile_cols, cgc_morph_footprint_width, cgc_morph, CGC_MORPH_* */
-#define CGC_ABI_VERSION 20
+ *      cgc_morph_max_radius, cgc_morph_tile_rows, cgc_morph_tile_cols, cgc_morph_footprint_width, cgc_morph, CGC_MORPH_*
+ *  21: DenseJK: cgc_jk_lstm_fwd, cgc_jk_lstm_bwd, cgc_jk_lstm_bwd_params and cgc_jk_lstm_bwd_flat refuse an npad that is not a
+ *      multiple of 64 (CGC_EINVAL, nothing launched); they took any npad >= n before */
+#define CGC_ABI_VERSION 21
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -611,11 +613,17 @@ int cgc_segment_max_bwd_full(const float* dout, const int* arg, const int* gptr,
 /* ---- A7: DenseJK (model/network.py:11-55): bi-LSTM(C -> H = 3C/2) over a node's 3 layer embeddings + Linear(2H -> 1)
  * attention + softmax-weighted sum, one thread per node.  xs [n, 3C], out [n, C].  lstm = HOST array of 8 device pointers
  * {w_ih[4H,C], w_hh[4H,H], b_ih[4H], b_hh[4H]} for the forward direction, then the same four for the reverse direction
- * (torch.nn.LSTM layout, gate order i,f,g,o).  HS, CS: [6H, npad] saved hidden / cell states (npad >= n).
+ * (torch.nn.LSTM layout, gate order i,f,g,o).  HS, CS: [6H, npad] saved hidden / cell states.
+ * npad (the same value in the forward and the backward of a call pair): npad >= n and npad % 64 == 0, else every entry point
+ * below returns CGC_EINVAL before it launches anything.  64 = the pair of 32-node tiles the staged matrix-core backward walks
+ * npad in, and rows of DGT / INT (3 * npad floats) then start 16-byte aligned (cgc_gemm_f32's 16-byte loads).  The forward
+ * writes columns < n of HS / CS (the matrix-core forward also the rest of the last 32-node tile: finite values nobody reads);
+ * no backward reads a column >= n, so the buffers need not be cleared.  n <= 0 returns 0 at once.
  * cgc_jk_supported(C): 1 if this C is compiled in (every even C <= 32); cgc_jk_matrix_core(C): 1 if it runs on the matrix-core
  * kernels (C in 4, 8, 12, 16, 20: those also have cgc_jk_lstm_bwd_params), else on the thread-per-direction kernels.
  * Backward writes dxs [n, 3C] and, for the parameter gradients, the transposed buffers DGT [2][4H+1][3*npad] and
- * INT [2][C+2H+1][3*npad] (zero in padded columns) whose per-direction product DGT_d * INT_d^T (cgc_gemm_f32, NT) holds
+ * INT [2][C+2H+1][3*npad] (every column written; in the padded ones DGT is zero and INT finite) whose per-direction product
+ * DGT_d * INT_d^T (cgc_gemm_f32, NT) holds
  * [dW_ih | dW_hh | db | .] in rows 0..4H-1 and [. | . | d b_att | d w_att[dH:(d+1)H]] in row 4H.  DHC: [2][2][H][npad] scratch. */
 int cgc_jk_supported(int C);
 int cgc_jk_matrix_core(int C);
