@@ -1,0 +1,304 @@
+// Rank filters of a uint8 image on gfx950: a quantile (QUANTILE), the difference of two quantiles (RANGE) or the Shannon entropy in
+// fixed point (ENTROPY) of the counted pixels under a flat footprint -- square, disk or diamond of radius r <= 63 (ENTROPY: r <= 15) --
+// clipped to the image and, if wanted, to the non-zero pixels of `within`.  Footprints, clipping and `within` are morph.hip's.
+// Contract item by item: cgc-net_amd/kernels.py KernelSpec.rank_filter; design and measurements: DESIGN.md, "Rank filters".
+//
+// ONE kernel, k_rank<WITHIN, DWORDS, ENTROPY>, one launch per call, no workspace, no global atomics.  Every result is a function of
+// the 256-bin histogram of the window, and the histogram of a window one pixel to the right differs by one pixel leaving and one
+// entering per footprint row (Huang 1979).  A workgroup owns a tile of RANK_ROWS rows x cols(r) columns, cols(r) = RANK_SPAN -
+// 2 halo(r), halo(r) = r rounded up to a multiple of 4, and looks at the RANK_SPAN = 256 columns [x0 - halo, x0 - halo + 256) of the
+// rows y0 - r .. y0 + RANK_ROWS - 1 + r.
+//   load       as morph.hip: an LDS row is 256 bytes = one dword per lane of a wave (rows 260 bytes apart: the slide reads down a
+//              column, and 65 dwords put its lanes into different banks); wave u loads rows u, u + 4, ...  Whether a pixel is
+//              counted (inside the image, non-zero in `within`) becomes one bit per pixel beside the bytes: four ballots per row, plane
+//              j holding the pixels 4 lane + j.  After the load the border and `within` are gone from every later step.
+//   runs       wave u owns the output rows u, u + 4, ... of the tile, one after the other, and its own histogram, 256 uint32 counters
+//              in LDS (a bin can reach 16129).  At the first pixel of a row it counts the whole footprint, 64 columns of one footprint
+//              row per instruction; then it slides: lane i (and i + 64 in a second pass) owns footprint row i, takes out the pixel at
+//              x - w(i) and puts in the one at x + w(i) + 1, both predicated by "counted", as LDS atomics.
+//   rank       every lane reads its four bins (one 16-byte read), the wave scans the 64 sums in registers (DPP), and the bin of rank
+//              k is the first lane whose inclusive sum exceeds k (a ballot) and the first of its four bins that does.  The total of
+//              the scan is n.
+//   entropy    every lane adds T[count] of its four bins from a copy of the term table in LDS; the same scan gives the wave's sum.
+//   store      a lane keeps the result of pixel x in a register, lane x mod 64; every 64 pixels the wave stores them together.
+// DWORDS is the launcher's choice as in morph.hip: with W % 4 == 0, dword-aligned bases and a 1-byte `within` a lane's four pixels are
+// one dword load per plane; otherwise pixel by pixel -- same values, slower.  The widths w(dy) are computed on the host in integers
+// and travel as a kernel argument.
+#include <stdint.h>
+
+#include "common.hpp"
+#include "image_common.hpp"
+#include "rank_entropy_table.hpp"
+
+namespace {
+
+constexpr int RANK_MAX_RADIUS = 63;
+constexpr int RANK_ENTROPY_MAX_RADIUS = 15;
+constexpr int RANK_ROWS = 8;                                   // output rows of a tile: two per wave
+constexpr int RANK_SPAN = 256;                                 // columns a workgroup looks at = bytes of an LDS row
+constexpr int RANK_DWORDS = RANK_SPAN / 4;                     // one per lane
+constexpr int RANK_STRIDE = RANK_SPAN + 4;                     // bytes from an LDS row to the next: 65 dwords, so that the lanes of the
+                                                               // slide, one row each at nearly the same column, fall into different banks
+constexpr int RANK_WAVES = CGC_BLOCK / CGC_WAVE;
+constexpr int RANK_BINS = 256;
+constexpr int RANK_MASK_DWORDS = RANK_SPAN / 32 + 1;           // per row: 4 planes of 64 bits, and one dword of padding for the same reason
+static_assert(RANK_ROWS % 2 == 0 && (2 * (RANK_STRIDE + 4 * RANK_MASK_DWORDS)) % 16 == 0, "the histograms behind the rows stay 16-byte aligned");
+static_assert(RANK_DWORDS == CGC_WAVE, "a wave loads whole LDS rows, one dword per lane");
+static_assert(RANK_BINS == 4 * CGC_WAVE, "a lane owns four bins");
+static_assert(2 * RANK_MAX_RADIUS + 1 <= 2 * CGC_WAVE, "two passes of one lane per footprint row");
+static_assert((2 * RANK_ENTROPY_MAX_RADIUS + 1) * (2 * RANK_ENTROPY_MAX_RADIUS + 1) == RANK_ENTROPY_TERMS - 1, "T[n] exists for every n");
+
+const int32_t rank_terms_host[RANK_ENTROPY_TERMS] = {RANK_ENTROPY_TERM_LIST};
+__device__ const int32_t rank_terms_dev[RANK_ENTROPY_TERMS] = {RANK_ENTROPY_TERM_LIST};
+
+__host__ __device__ __forceinline__ int rank_halo(int r) { return (r + 3) & ~3; }
+__host__ __device__ __forceinline__ int rank_cols(int r) { return RANK_SPAN - 2 * rank_halo(r); }
+static inline int rank_lds_bytes(int r, bool entropy) {
+  return (RANK_ROWS + 2 * r) * (RANK_STRIDE + 4 * RANK_MASK_DWORDS) + RANK_WAVES * RANK_BINS * 4 + (entropy ? RANK_ENTROPY_TERMS * 4 : 0);
+}
+
+struct RankFootprint {
+  uint8_t w[2 * CGC_WAVE];                                      // w[i] = the half width of footprint row dy = i - r, i <= 2 r
+};
+
+// the half width of footprint row dy, in integers, as morph.hip's morph_width; kind and |dy| <= r have been checked
+static inline int rank_width(int kind, int r, int dy) {
+  const int a = dy < 0 ? -dy : dy;
+  if (kind == CGC_MORPH_SQUARE) return r;
+  if (kind == CGC_MORPH_DIAMOND) return r - a;
+  int w = 0;
+  while ((w + 1) * (w + 1) + a * a <= r * r) ++w;
+  return w;
+}
+
+// Four adjacent pixels of row y from column x (a multiple of 4 relative to the tile; negative or >= W outside the image): v their
+// values, m 0xFF in every byte whose pixel is counted.  Addresses are clamped into the image, as in morph.hip.
+template <bool WITHIN, bool DWORDS>
+__device__ __forceinline__ void rank_fetch(const uint8_t* __restrict__ img, const void* __restrict__ within, int wbytes, int H, int W,
+                                           int64_t x, int64_t y, uint32_t& v, uint32_t& m) {
+  const bool row = y >= 0 && y < H;
+  const int base = row ? (int)y * W : 0;                                // pixel indices fit int32: H W < 2^31
+  if (DWORDS) {
+    const bool ok = row && x >= 0 && x < W;
+    const int i = ok ? base + (int)x : 0;
+    v = *reinterpret_cast<const uint32_t*>(img + i);
+    m = ok ? 0xFFFFFFFFu : 0u;
+    if (WITHIN) {
+      const uint32_t q = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(within) + i);
+      uint32_t nz = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) nz |= ((q >> (8 * j)) & 255u) != 0 ? 255u << (8 * j) : 0u;
+      m &= nz;
+    }
+  } else {
+    v = m = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool in = row && x + j >= 0 && x + j < W;
+      const int i = in ? base + (int)(x + j) : 0;
+      const bool counted = in && (!WITHIN || image_nonzero(within, wbytes, i));
+      v |= (uint32_t)img[i] << (8 * j);
+      m |= counted ? 255u << (8 * j) : 0u;
+    }
+  }
+}
+
+// The lanes of a wave talk through its histogram: what they wrote before this point is what they read after it.  LDS operations of
+// one wave complete in order; the fence and the barrier keep the compiler from moving them across.
+__device__ __forceinline__ void rank_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// The inclusive prefix sum of x over the 64 lanes, in registers (DPP): the lane's three left neighbours inside its row of 16, then
+// shifts by 4 and 8 inside the row, then the last lane of rows 0 and 2 into rows 1 and 3, then lane 31 into rows 2 and 3.  A lane
+// that a step does not write, or whose source lies outside its row, adds 0.
+template <int CTRL, int ROW_MASK, int BANK_MASK>
+__device__ __forceinline__ uint32_t rank_dpp(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, BANK_MASK, false);
+}
+__device__ __forceinline__ uint32_t rank_wave_scan(uint32_t x) {
+  uint32_t v = x + rank_dpp<0x111, 0xf, 0xf>(x);                        // row_shr:1
+  v += rank_dpp<0x112, 0xf, 0xf>(x);                                    // row_shr:2
+  v += rank_dpp<0x113, 0xf, 0xf>(x);                                    // row_shr:3
+  v += rank_dpp<0x114, 0xf, 0xe>(v);                                    // row_shr:4, lanes 4 .. 15 of a row
+  v += rank_dpp<0x118, 0xf, 0xc>(v);                                    // row_shr:8, lanes 8 .. 15
+  v += rank_dpp<0x142, 0xa, 0xf>(v);                                    // row_bcast:15, rows 1 and 3
+  v += rank_dpp<0x143, 0xc, 0xf>(v);                                    // row_bcast:31, rows 2 and 3
+  return v;
+}
+
+// is pixel (row, col) of the tile counted: plane col & 3, bit col >> 2
+__device__ __forceinline__ bool rank_counted(const uint32_t* mask, int row, int col) {
+  return (mask[row * RANK_MASK_DWORDS + (col & 3) * 2 + (col >> 7)] >> ((col >> 2) & 31)) & 1u;
+}
+
+// the value of rank k < n: c the lane's four bins, incl the inclusive scan of their sums
+__device__ __forceinline__ int rank_value(const uint4& c, uint32_t incl, uint32_t k) {
+  const unsigned long long above = __ballot(incl > k);                  // not 0: the last lane's incl is n > k
+  const int lane = __builtin_ctzll(above);
+  const uint32_t c0 = __builtin_amdgcn_readlane(c.x, lane), c1 = __builtin_amdgcn_readlane(c.y, lane);
+  const uint32_t c2 = __builtin_amdgcn_readlane(c.z, lane), c3 = __builtin_amdgcn_readlane(c.w, lane);
+  uint32_t below = __builtin_amdgcn_readlane(incl, lane) - (c0 + c1 + c2 + c3);      // <= k
+  int bin = 4 * lane;
+  below += c0;
+  if (below > k) return bin;
+  below += c1;
+  if (below > k) return bin + 1;
+  below += c2;
+  return below > k ? bin + 2 : bin + 3;
+}
+
+template <bool WITHIN, bool DWORDS, bool ENTROPY>
+__global__ void __launch_bounds__(CGC_BLOCK) k_rank(const uint8_t* __restrict__ img, const void* __restrict__ within, int wbytes, int H, int W,
+                                                    int r, int tiles_x, int op, int q_lo, int q_hi, RankFootprint fp,
+                                                    void* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t rank_lds[];    // [rows][65 dwords] | [rows][9 dwords] | [4][256] | T
+  const int rows = RANK_ROWS + 2 * r;
+  const int halo = rank_halo(r), cols = RANK_SPAN - 2 * halo;
+  const int tile_x = blockIdx.x % tiles_x, tile_y = blockIdx.x / tiles_x;
+  const int x0 = tile_x * cols, y0 = tile_y * RANK_ROWS;                // x0 < W, y0 < H
+  const int t = threadIdx.x, lane = t & (CGC_WAVE - 1), wave = t / CGC_WAVE;
+  const uint8_t* tile = reinterpret_cast<const uint8_t*>(rank_lds);
+  uint32_t* mask = rank_lds + rows * (RANK_STRIDE / 4);
+  uint32_t* hist = mask + rows * RANK_MASK_DWORDS + wave * RANK_BINS;
+  int32_t* terms = reinterpret_cast<int32_t*>(mask + rows * RANK_MASK_DWORDS + RANK_WAVES * RANK_BINS);
+
+  // ---- load: wave u takes rows u, u + 4, ...
+  {
+    const int64_t xg = (int64_t)x0 - halo + 4 * lane;
+    for (int row = wave; row < rows; row += RANK_WAVES) {
+      uint32_t v, m;
+      rank_fetch<WITHIN, DWORDS>(img, within, wbytes, H, W, xg, (int64_t)y0 - r + row, v, m);
+      rank_lds[row * (RANK_STRIDE / 4) + lane] = v;
+      const unsigned long long b0 = __ballot(m & 1u), b1 = __ballot(m & 0x100u), b2 = __ballot(m & 0x10000u), b3 = __ballot(m & 0x1000000u);
+      if (lane < 4) {
+        const unsigned long long b = lane == 0 ? b0 : lane == 1 ? b1 : lane == 2 ? b2 : b3;
+        mask[row * RANK_MASK_DWORDS + 2 * lane] = (uint32_t)b;
+        mask[row * RANK_MASK_DWORDS + 2 * lane + 1] = (uint32_t)(b >> 32);
+      }
+    }
+    if (ENTROPY)
+      for (int i = t; i < RANK_ENTROPY_TERMS; i += CGC_BLOCK) terms[i] = rank_terms_dev[i];
+  }
+  __syncthreads();
+
+  const int nrows = min(RANK_ROWS, H - y0), ncols = min(cols, W - x0);  // both >= 1
+  const int nf = 2 * r + 1;                                             // footprint rows
+  const bool has0 = lane < nf, has1 = lane + CGC_WAVE < nf;
+  const int w0 = has0 ? fp.w[lane] : 0, w1 = has1 ? fp.w[lane + CGC_WAVE] : 0;
+
+  for (int orow = wave; orow < nrows; orow += RANK_WAVES) {
+    // ---- the histogram of the first window of the row: centre at tile column halo, footprint row i in tile row orow + i
+    reinterpret_cast<uint4*>(hist)[lane] = make_uint4(0u, 0u, 0u, 0u);
+    rank_wave_sync();
+    for (int i = 0; i < nf; ++i) {
+      const int w = fp.w[i], row = orow + i;                            // uniform
+      for (int c = lane; c <= 2 * w; c += CGC_WAVE) {
+        const int col = halo - w + c;                                   // 0 <= col <= halo + r <= 255
+        if (rank_counted(mask, row, col)) atomicAdd(&hist[tile[row * RANK_STRIDE + col]], 1u);
+      }
+    }
+
+    const int64_t out_row = (int64_t)(y0 + orow) * W + x0;
+    int res = 0;                                                        // the result of pixel col, in lane col & 63
+    for (int col = 0;; ++col) {
+      rank_wave_sync();
+      // ---- evaluate the window of column col
+      const uint4 c = reinterpret_cast<const uint4*>(hist)[lane];
+      const uint32_t s = c.x + c.y + c.z + c.w;
+      const uint32_t incl = rank_wave_scan(s);
+      const int n = (int)__builtin_amdgcn_readlane(incl, CGC_WAVE - 1);
+      int value = 0;
+      if (ENTROPY) {
+        const uint32_t mine = (uint32_t)(terms[c.x] + terms[c.y] + terms[c.z] + terms[c.w]);      // counts <= n <= 961
+        const int e = (int)__builtin_amdgcn_readlane(rank_wave_scan(mine), CGC_WAVE - 1);         // <= T[n] + 128 < 2^31
+        if (n > 0) value = (terms[n] - e) / n;                          // E >= 0
+      } else if (n > 0) {
+        const int k_hi = min(n - 1, n * q_hi / 10000);                  // n q < 2^31
+        value = rank_value(c, incl, (uint32_t)k_hi);
+        if (op == CGC_RANK_RANGE) value -= rank_value(c, incl, (uint32_t)min(n - 1, n * q_lo / 10000));
+      }
+      if (lane == (col & (CGC_WAVE - 1))) res = value;
+      const bool last = col == ncols - 1;
+      if ((col & (CGC_WAVE - 1)) == CGC_WAVE - 1 || last) {
+        const int first = col & ~(CGC_WAVE - 1);
+        if (first + lane <= col) {
+          if (ENTROPY) static_cast<int32_t*>(out)[out_row + first + lane] = res;
+          else static_cast<uint8_t*>(out)[out_row + first + lane] = (uint8_t)res;
+        }
+      }
+      if (last) break;
+      rank_wave_sync();                                                 // every lane has read its bins
+      // ---- slide to column col + 1: the centre was at tile column halo + col
+      const int cx = halo + col;
+      if (has0) {
+        const int row = orow + lane, ca = cx - w0, cb = cx + w0 + 1;    // ca >= 0; cb <= halo + cols - 1 + r <= 255
+        if (rank_counted(mask, row, ca)) atomicSub(&hist[tile[row * RANK_STRIDE + ca]], 1u);
+        if (rank_counted(mask, row, cb)) atomicAdd(&hist[tile[row * RANK_STRIDE + cb]], 1u);
+      }
+      if (has1) {
+        const int row = orow + lane + CGC_WAVE, ca = cx - w1, cb = cx + w1 + 1;
+        if (rank_counted(mask, row, ca)) atomicSub(&hist[tile[row * RANK_STRIDE + ca]], 1u);
+        if (rank_counted(mask, row, cb)) atomicAdd(&hist[tile[row * RANK_STRIDE + cb]], 1u);
+      }
+    }
+  }
+}
+
+static inline bool dword_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+struct RankArgs {
+  const uint8_t* img;
+  const void* within;
+  int within_bytes, H, W, radius, op, q_lo, q_hi;
+  RankFootprint fp;
+  void* out;
+};
+
+template <bool WITHIN, bool DWORDS, bool ENTROPY>
+void launch_rank_as(const RankArgs& a, hipStream_t st) {
+  const int tiles_x = (int)ceil_div64(a.W, rank_cols(a.radius));
+  const int64_t blocks = tiles_x * ceil_div64(a.H, RANK_ROWS);          // < H W / (128 * 8) + H / 8 + W / 128 + 1 < 2^31
+  hipLaunchKernelGGL((k_rank<WITHIN, DWORDS, ENTROPY>), dim3((unsigned)blocks), dim3(CGC_BLOCK), (size_t)rank_lds_bytes(a.radius, ENTROPY), st,
+                     a.img, a.within, a.within_bytes, a.H, a.W, a.radius, tiles_x, a.op, a.q_lo, a.q_hi, a.fp, a.out);
+}
+
+template <bool WITHIN, bool DWORDS>
+void launch_rank_op(const RankArgs& a, hipStream_t st) {
+  if (a.op == CGC_RANK_ENTROPY) launch_rank_as<WITHIN, DWORDS, true>(a, st);
+  else launch_rank_as<WITHIN, DWORDS, false>(a, st);
+}
+
+}  // namespace
+
+extern "C" int cgc_rank_max_radius(void) { return RANK_MAX_RADIUS; }
+extern "C" int cgc_rank_entropy_max_radius(void) { return RANK_ENTROPY_MAX_RADIUS; }
+extern "C" int cgc_rank_tile_rows(void) { return RANK_ROWS; }
+extern "C" int cgc_rank_tile_cols(int radius) { return radius < 0 || radius > RANK_MAX_RADIUS ? 0 : rank_cols(radius); }
+extern "C" int cgc_rank_entropy_term(int c) { return c < 0 || c >= RANK_ENTROPY_TERMS ? CGC_EINVAL : rank_terms_host[c]; }
+
+extern "C" int cgc_rank_filter(const uint8_t* img, const void* within_or_null, int within_bytes, int H, int W, int kind, int radius, int op,
+                               int q_lo, int q_hi, void* out, cgc_stream_t stream) {
+  if (bad_image_dims(H, W) || op < CGC_RANK_QUANTILE || op > CGC_RANK_ENTROPY) return CGC_EINVAL;
+  if (radius < 0 || radius > (op == CGC_RANK_ENTROPY ? RANK_ENTROPY_MAX_RADIUS : RANK_MAX_RADIUS)) return CGC_EINVAL;
+  if (kind < CGC_MORPH_SQUARE || kind > CGC_MORPH_DIAMOND) return CGC_EINVAL;
+  if (q_lo < 0 || q_hi > 10000 || q_lo > q_hi) return CGC_EINVAL;
+  if (within_or_null != nullptr && bad_elem_bytes(within_bytes)) return CGC_EINVAL;
+  if ((int64_t)H * W == 0) return 0;
+  if (img == nullptr || out == nullptr) return CGC_EINVAL;
+  RankArgs a{img, within_or_null, within_or_null != nullptr ? within_bytes : 0, H, W, radius, op, q_lo, q_hi, {}, out};
+  for (int dy = -radius; dy <= radius; ++dy) a.fp.w[dy + radius] = (uint8_t)rank_width(kind, radius, dy);
+  // rows as dwords: every row starts on a dword boundary, and the flags of `within` are bytes
+  const bool dwords = (W & 3) == 0 && dword_aligned(img) && (within_or_null == nullptr || (within_bytes == 1 && dword_aligned(within_or_null)));
+  const hipStream_t st = as_stream(stream);
+  if (within_or_null != nullptr) {
+    if (dwords) launch_rank_op<true, true>(a, st);
+    else launch_rank_op<true, false>(a, st);
+  } else {
+    if (dwords) launch_rank_op<false, true>(a, st);
+    else launch_rank_op<false, false>(a, st);
+  }
+  CGC_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}

@@ -35,6 +35,10 @@ MORPH_MAX_RADIUS = 63      # flat_morphology: a tile plus a halo of r on both si
 MORPH_KINDS = {'square': 0, 'disk': 1, 'diamond': 2}              # include/cgc_hip.h: CGC_MORPH_SQUARE / _DISK / _DIAMOND
 MORPH_OPS = {'erode': 0, 'dilate': 1, 'gradient': 2}              # CGC_MORPH_ERODE / _DILATE / _GRADIENT
 MORPH_EPILOGUES = {None: 0, 'other_minus': 1, 'minus_other': 2}   # CGC_MORPH_PLAIN / _OTHER_MINUS / _MINUS_OTHER
+RANK_MAX_RADIUS = 63       # rank_filter: morph's tile geometry; n <= 127^2 = 16129, so n * q10k < 2^31
+ENTROPY_MAX_RADIUS = 15    # rank_filter 'entropy': n <= 31^2 = 961, the length of the table of c log2 c terms
+RANK_ENTROPY_TERMS = 962   # T[0..961]
+RANK_OPS = {'quantile': 0, 'range': 1, 'entropy': 2}              # CGC_RANK_QUANTILE / _RANGE / _ENTROPY
 ADJ_MAX_PIXELS = 2 ** 29   # region_adjacency: a pair's count can reach 4 H W and must fit int32
 WS_JUMP_BATCH = 8         # pointer jumps of watershed_flood per host read: resolves parent chains of up to 2^7 pixels in one read
 
@@ -475,6 +479,43 @@ class KernelSpec(object):
         2 * (r rounded up to a multiple of 4)) columns."""
         raise NotImplementedError
 
+    def rank_filter(self, image, kind, radius, op, q_lo=0, q_hi=0, within=None):
+        """A quantile, a quantile range or the local entropy of one uint8 image over a flat footprint (F16, on the stain plane, beside
+        flat_morphology; csrc/rank.hip): the order statistics of the window -- median, robust erode / dilate / gradient, the majority
+        filter of a mask -- and the texture measure skimage.filters.rank.entropy.  Returns [H, W], contiguous: uint8 for 'quantile'
+        and 'range', int32 for 'entropy'; no host read.
+
+        1.  image: uint8 [H, W], any strides, H * W < 2^31.  kind: 'square', 'disk' or 'diamond'.  radius r: an integer in
+            0..RANK_MAX_RADIUS = 63, for 'entropy' in 0..ENTROPY_MAX_RADIUS = 15 (ValueError otherwise; the library returns
+            CGC_EINVAL and launches nothing).
+        2.  The footprint is flat_morphology's, item 2: offsets (dy, dx) with |dy| <= r and |dx| <= w(dy), the widths decided in
+            integers on the host; r = 0 is the single pixel.
+        3.  The footprint is CLIPPED to the image: nothing is replicated, border windows are smaller.
+        4.  within: None or [H, W] of a 1-, 2-, 4- or 8-byte integer type or bool, any strides; only "is zero" is read.  A footprint
+            pixel is *counted* iff it lies in the image and within is None or non-zero there.  The centre has no special role.
+            Below, n is the number of counted pixels of a window and v[0] <= ... <= v[n-1] their values sorted.
+        5.  op 'quantile', q_hi = q10k, an integer in 0..10000 (q_lo is not used; pass 0): the result is v[k], k = min(n - 1,
+            floor(n * q10k / 10000)) in exact integers (n <= 16129: n * q10k < 2^31) -- the smallest value t whose cumulative count
+            #{v <= t} exceeds k.  q10k = 0 is the minimum, 10000 the maximum, 5000 the median (the upper one when n is even).  n = 0
+            gives 0.  The 1 x 2 image [10, 20] at r = 1 gives [20, 20] at 5000 and [10, 10] at 4999; in the interior of a square
+            of r = 2 (n = 25) 2000 takes k = 5 and 1999 takes k = 4.
+        6.  op 'range', q_lo <= q_hi (both as q10k; ValueError otherwise): v[k(q_hi)] - v[k(q_lo)] from one histogram in one pass, in
+            0..255, and 0 where n = 0.  (0, 10000) is the morphological gradient.
+        7.  op 'entropy': the Shannon entropy H = -sum p log2 p of the counted values in bits, in fixed point and integers only.  With
+            T[c] = round(c * log2(c) * 2^16) for c = 0..961 (T[0] = T[1] = 0; every entry fits int32; the library's table,
+            ``rank_entropy_term``, is the one the kernel reads), E = T[n] - sum over the non-empty bins of T[count], and the result
+            is H16 = floor(E / n) as int32, 0 where n = 0.  Derived: E >= 0, and E == 0 iff one bin holds everything (T is the
+            rounding of a superadditive function with integer gaps of at least 2 * 2^16 between T[a + b] and T[a] + T[b]); with m
+            occupied bins |E - 2^16 n H| <= (m + 1) / 2 (m + 1 roundings of at most 1/2); hence, m <= n and the floor,
+            |H16 / 2^16 - H| <= (n + 1) / (2 n 2^16) + 2^-16 <= 2^-15.
+        8.  H * W = 0 gives an empty output.
+        9.  One launch, NO workspace, no global atomics (the histograms are counters in LDS, and integer sums do not depend on the
+            order of their terms), integer arithmetic: bit-identical from call to call.
+        Inside the kernel ("Rank filters"): a wave slides one 256-bin histogram along a row of a tile of
+        ``rank_tile_rows`` (8) rows by ``rank_tile_cols(r)`` (256 - 2 * (r rounded up to a multiple of 4)) columns, one pixel out
+        and one in per footprint row and step, and reads the rank off a scan of the bins."""
+        raise NotImplementedError
+
     def region_adjacency(self, labels, connectivity, value=None):
         """Region adjacency of one label image (F13, behind label_components / distance_transform; csrc/adjacency.hip): which
         regions touch, along how many pixel pairs, and how near they come.  Returns (pairs int32 [P, 2], count int32 [P], min_sum int32
@@ -853,6 +894,8 @@ class HipKernels(KernelSpec):
         self.window_tile_rows = int(self.lib.cgc_window_tile_rows())          # rows of the tiles of window_sums / local_threshold (tests)
         self.morph_tile_rows = int(self.lib.cgc_morph_tile_rows())            # rows of the tiles of flat_morphology (tests)
         assert int(self.lib.cgc_morph_max_radius()) == MORPH_MAX_RADIUS
+        self.rank_tile_rows = int(self.lib.cgc_rank_tile_rows())              # rows of the tiles of rank_filter (tests)
+        assert int(self.lib.cgc_rank_max_radius()) == RANK_MAX_RADIUS and int(self.lib.cgc_rank_entropy_max_radius()) == ENTROPY_MAX_RADIUS
         self.adjacency_tile = int(self.lib.cgc_adjacency_tile_side())          # side of the tiles region_adjacency folds in LDS (tests)
         self.scan_chunk = int(self.lib.cgc_scan_chunk_pixels())                # ... and of od_moments / angle_histogram
         self._dirs_checked = (None, None)                                      # angle_histogram's last direction table and its C array
@@ -1421,6 +1464,43 @@ class HipKernels(KernelSpec):
         out = torch.empty(H, W, dtype=torch.uint8, device=image.device)
         self._chk(self.lib.cgc_morph(_ptr(image), _ptr(within), within.element_size() if within is not None else 0, H, W, kind, radius,
                                      op, _ptr(other), epilogue, _ptr(out), self._stream()), 'cgc_morph')
+        return out
+
+    @staticmethod
+    def _check_rank(kind, radius, op, q_lo, q_hi):
+        """The refusals of rank_filter that need no tensor: returns the library's codes (kind, op)."""
+        if not isinstance(kind, str) or kind not in MORPH_KINDS:
+            raise ValueError("rank_filter: kind must be 'square', 'disk' or 'diamond', got %r" % (kind,))
+        if not isinstance(op, str) or op not in RANK_OPS:
+            raise ValueError("rank_filter: op must be 'quantile', 'range' or 'entropy', got %r" % (op,))
+        top = ENTROPY_MAX_RADIUS if op == 'entropy' else RANK_MAX_RADIUS
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= top:
+            raise ValueError('rank_filter: radius must be an integer in 0..%d for %r, got %r' % (top, op, radius))
+        for name, q in (('q_lo', q_lo), ('q_hi', q_hi)):
+            if isinstance(q, bool) or not isinstance(q, int) or not 0 <= q <= 10000:
+                raise ValueError('rank_filter: %s must be an integer in 0..10000, got %r' % (name, q))
+        if q_lo > q_hi:
+            raise ValueError('rank_filter: q_lo <= q_hi (got %d > %d)' % (q_lo, q_hi))
+        return MORPH_KINDS[kind], RANK_OPS[op]
+
+    def rank_tile_cols(self, radius):
+        """Columns of the tiles of rank_filter at this radius (tests place footprints across tile edges)."""
+        return int(self.lib.cgc_rank_tile_cols(int(radius)))
+
+    def rank_entropy_term(self, c):
+        """T[c] = round(c log2(c) 2^16) of rank_filter's entropy, c in 0..961, from the library's table (host only)."""
+        if isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < RANK_ENTROPY_TERMS:
+            raise ValueError('rank_entropy_term: c must be an integer in 0..%d, got %r' % (RANK_ENTROPY_TERMS - 1, c))
+        return int(self.lib.cgc_rank_entropy_term(c))
+
+    def rank_filter(self, image, kind, radius, op, q_lo=0, q_hi=0, within=None):
+        kind, op = HipKernels._check_rank(kind, radius, op, q_lo, q_hi)
+        assert image.dtype == torch.uint8 and (within is None or within.shape == image.shape)
+        image, within = self._image(image), self._image(within)               # after the refusals: may copy
+        H, W = image.shape
+        out = torch.empty(H, W, dtype=torch.int32 if op == RANK_OPS['entropy'] else torch.uint8, device=image.device)
+        self._chk(self.lib.cgc_rank_filter(_ptr(image), _ptr(within), within.element_size() if within is not None else 0, H, W, kind,
+                                           radius, op, q_lo, q_hi, _ptr(out), self._stream()), 'cgc_rank_filter')
         return out
 
     def region_adjacency(self, labels, connectivity, value=None):

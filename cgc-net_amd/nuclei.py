@@ -60,6 +60,17 @@ gives the Euclidean disk).  End to end:
     markers, n = label_instances(erode(fg, 2))           # cores: what survives a small erosion
     L = watershed(morph_gradient(plane, 1), markers, within=fg)
 
+``rank_filter``, ``median``, ``quantile_range`` and ``local_entropy`` are the order statistics of the same windows (csrc/rank.hip;
+kernels.KernelSpec.rank_filter -- one launch each, exact integers, footprints, clipping and ``within`` as erode).  ``median`` sits
+between ``separate_stains`` and the threshold as the alternative to ``smooth``: it removes specks and keeps the stain edge that
+``watershed(morph_gradient(plane, 1), ...)`` cuts on.  A low or high quantile is the robust erode or dilate -- one hot pixel does not
+move it --, and ``quantile_range`` the robust gradient.  On a bool mask ``median`` is the majority filter, which smooths a ragged
+foreground map in front of ``fill_holes`` / ``split_touching``; ``local_entropy`` (skimage.filters.rank.entropy) is a texture map to
+threshold or to hand to ``watershed`` as a height:
+    plane = median(separate_stains(tile, planes=(0,))[0], 2)
+    fg = fill_holes(median(plane > otsu_threshold(plane), 1, 'square'))
+    texture = local_entropy(bgr_to_gray(tile), 3)
+
 ``region_adjacency`` reads off a label image which regions touch and along how many pixels (csrc/adjacency.hip;
 kernels.KernelSpec.region_adjacency), and ``voronoi_graph`` builds on it the other standard cell graph of the literature: the cells of
 ``expand_labels`` are the discrete Voronoi partition of the instance mask, and two nuclei are joined iff their cells share a border.
@@ -1100,6 +1111,98 @@ def close_by_reconstruction(image, radius, footprint='disk', connectivity=1, wit
     _check_morph('close_by_reconstruction', image, radius, footprint, within)
     _check_connectivity(connectivity)
     return reconstruct(dilate(image, radius, footprint, within), image, 'erosion', connectivity)
+
+
+RANK_MAX_RADIUS = kernels.RANK_MAX_RADIUS
+ENTROPY_MAX_RADIUS = kernels.ENTROPY_MAX_RADIUS
+
+
+def rank_q10k(q):
+    """The integer the rank filters use for a quantile q in [0, 1]: the nearest integer to 10000 q, decided exactly (``Fraction``),
+    halves rounding up -- 0.5 is 5000, 0.05 is 500, Fraction(1, 3) is 3333.  ``q``: an int, float or Fraction.  ValueError for a bool,
+    a value that is not a real number, NaN, or anything outside [0, 1]."""
+    if isinstance(q, bool) or not isinstance(q, numbers.Real):
+        raise ValueError('q must be a real number in [0, 1] (got %r)' % (q,))
+    try:
+        exact = q if isinstance(q, numbers.Rational) else float(q)      # numpy scalars and the like: their exact value as a float
+        if isinstance(exact, float) and not math.isfinite(exact):
+            raise ValueError
+        q10k = math.floor(Fraction(exact) * 10000 + Fraction(1, 2))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError('q must be a finite real number in [0, 1] (got %r)' % (q,))
+    if not 0 <= Fraction(exact) <= 1:
+        raise ValueError('q must lie in [0, 1] (got %r)' % (q,))
+    return q10k
+
+
+def _check_rank(fn, image, radius, footprint, within, top=RANK_MAX_RADIUS):
+    """The refusals the rank filters share, before any launch: returns (the image as uint8 -- a bool image as 0 / 1, without a copy
+    --, radius as an int)."""
+    _check_image(fn, 'image', image, (torch.bool, torch.uint8))
+    _check_within(fn, within, image)
+    radius = _check_int_in('radius', radius, 0, top)
+    if not isinstance(footprint, str) or footprint not in kernels.MORPH_KINDS:
+        raise ValueError("footprint must be 'disk', 'square' or 'diamond', got %r" % (footprint,))
+    return (image.view(torch.uint8) if image.dtype == torch.bool else image), radius
+
+
+def _rank(x, footprint, radius, op, q_lo, q_hi, within):
+    with torch.cuda.device(x.device):
+        return kernels.get().rank_filter(x, footprint, radius, op, q_lo, q_hi, within)
+
+
+def rank_filter(image, radius, q, footprint='disk', within=None):
+    """The q-quantile of every window of a uint8 or bool [H, W] tensor on the GPU (any strides): with n the number of counted pixels of
+    the window and v[0] <= ... <= v[n-1] their values sorted, the result is v[min(n - 1, floor(n * q10k / 10000))], q10k =
+    rank_q10k(q) -- q = 0 is erode, 1 is dilate, 1/2 the median (the upper one when n is even); 0.05 and 0.95 are the erode and dilate
+    that one hot pixel does not decide.  ``radius`` (0..63), ``footprint`` and ``within`` as erode: the footprint is clipped to the
+    image, and with ``within`` only its non-zero pixels count; where none counts the result is 0 (False).  A bool image counts as
+    0 / 1 and gives a bool result.  Exact integers, one launch (kernels.KernelSpec.rank_filter).
+
+    Host syncs: none."""
+    x, radius = _check_rank('rank_filter', image, radius, footprint, within)
+    out = _rank(x, footprint, radius, 'quantile', 0, rank_q10k(q), within)
+    return out != 0 if image.dtype == torch.bool else out
+
+
+def median(image, radius, footprint='disk', within=None):
+    """rank_filter(image, radius, 1/2): the median filter, the edge-preserving denoiser in front of a threshold -- it removes bright
+    and dark specks smaller than half the footprint and leaves a step edge where it is.  With an even count the upper median is
+    taken.  On a bool mask it is the majority filter: True iff at least half of the counted pixels are True -- a tie gives True,
+    and a window in which nothing is counted gives False.  Arguments and result as rank_filter.
+
+    Host syncs: none."""
+    x, radius = _check_rank('median', image, radius, footprint, within)
+    out = _rank(x, footprint, radius, 'quantile', 0, 5000, within)
+    return out != 0 if image.dtype == torch.bool else out
+
+
+def quantile_range(image, radius, q_lo, q_hi, footprint='disk', within=None):
+    """The q_hi-quantile minus the q_lo-quantile of every window (q_lo <= q_hi, both as rank_filter's q; ValueError otherwise), both
+    read off one histogram in ONE launch: the robust local contrast -- quantile_range(x, r, 0, 1) is morph_gradient(x, r), and
+    (0.05, 0.95) is the gradient that a single hot or dead pixel does not decide.  Arguments as rank_filter; returns uint8 [H, W] (a
+    bool image counts as 0 / 1), 0 where no pixel counts.
+
+    Host syncs: none."""
+    x, radius = _check_rank('quantile_range', image, radius, footprint, within)
+    lo, hi = rank_q10k(q_lo), rank_q10k(q_hi)
+    if lo > hi:
+        raise ValueError('q_lo <= q_hi (got %r > %r)' % (q_lo, q_hi))
+    return _rank(x, footprint, radius, 'range', lo, hi, within)
+
+
+def local_entropy(image, radius=3, footprint='disk', within=None, raw=False):
+    """The Shannon entropy, in bits, of the values under every window: skimage.filters.rank.entropy(image, disk(radius)), with the
+    footprint clipped to the image -- 0 on a flat region, log2(n) where all n pixels differ; a texture map to threshold or to flood.
+    ``radius``: an integer in 0..15; ``footprint`` and ``within`` as rank_filter (where no pixel counts the result is 0).  Computed
+    in integers from a table of c log2 c terms (kernels.KernelSpec.rank_filter, item 7): the result is H16 / 65536 as float32 -- exact,
+    H16 < 2^24 -- with |H16 / 65536 - H| <= 2^-15, or, with ``raw=True``, the int32 H16 itself.  One launch; a pure function of its
+    inputs.
+
+    Host syncs: none."""
+    x, radius = _check_rank('local_entropy', image, radius, footprint, within, ENTROPY_MAX_RADIUS)
+    h16 = _rank(x, footprint, radius, 'entropy', 0, 0, within)
+    return h16 if raw else h16.to(torch.float32) / 65536.0
 
 
 def _od_min(beta):

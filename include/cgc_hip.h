@@ -76,8 +76,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *  20: flat grey-scale morphology (erode, dilate, gradient over a square, disk or diamond; fused top-hat subtraction):
  *      cgc_morph_max_radius, cgc_morph_tile_rows, cgc_morph_tile_cols, cgc_morph_footprint_width, cgc_morph, CGC_MORPH_*
  *  21: DenseJK: cgc_jk_lstm_fwd, cgc_jk_lstm_bwd, cgc_jk_lstm_bwd_params and cgc_jk_lstm_bwd_flat refuse an npad that is not a
- *      multiple of 64 (CGC_EINVAL, nothing launched); they took any npad >= n before */
-#define CGC_ABI_VERSION 21
+ *      multiple of 64 (CGC_EINVAL, nothing launched); they took any npad >= n before
+ *  22: rank filters (quantile, quantile range, local entropy over a square, disk or diamond): cgc_rank_max_radius,
+ *      cgc_rank_entropy_max_radius, cgc_rank_tile_rows, cgc_rank_tile_cols, cgc_rank_entropy_term, cgc_rank_filter, CGC_RANK_* */
+#define CGC_ABI_VERSION 22
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -438,6 +440,33 @@ int cgc_morph_tile_cols(int radius);
 int cgc_morph_footprint_width(int kind, int radius, int dy);
 int cgc_morph(const uint8_t* img, const void* within_or_null, int within_bytes, int H, int W, int kind, int radius, int op,
               const uint8_t* other_or_null, int epilogue, uint8_t* out, cgc_stream_t stream);
+
+/* ---- F16 (on F10's plane, beside F15): rank filters of a uint8 image (csrc/rank.hip) -- order statistics and the entropy of the
+ * histogram of the counted pixels under a flat footprint.  The contract item by item: cgc-net_amd/kernels.py KernelSpec.rank_filter.
+ * img, kind, radius, the widths w(dy), the clipping to the image, within_or_null / within_bytes and "counted" are exactly F15's (kinds
+ * are CGC_MORPH_SQUARE / _DISK / _DIAMOND; radius 0..63).  With n the number of counted pixels of a window and v[0] <= ... <= v[n-1]
+ * their values sorted, and k(q) = min(n - 1, floor(n * q / 10000)) for an integer q in 0..10000:
+ *   op QUANTILE: out uint8 = v[k(q_hi)] (q_lo is not used, but must still be a valid q <= q_hi); 0 where n = 0.
+ *   op RANGE:    out uint8 = v[k(q_hi)] - v[k(q_lo)], q_lo <= q_hi, both from one histogram; 0 where n = 0.
+ *   op ENTROPY:  radius 0..15 only (n <= 961).  out int32 = floor(E / n), E = T[n] - sum over the non-empty bins of T[count], with
+ *                T[c] = round(c * log2(c) * 2^16): the Shannon entropy of the counted values in bits, times 2^16, within 2 of the
+ *                real value; 0 where n = 0.  q_lo, q_hi are checked as for the other ops and not used.
+ *   cgc_rank_max_radius (63), cgc_rank_entropy_max_radius (15), cgc_rank_tile_rows (8), cgc_rank_tile_cols(radius) (256 - 2 * (radius
+ *     rounded up to a multiple of 4); 0 for a radius out of range): the tile one workgroup owns, for tests.
+ *   cgc_rank_entropy_term(c): T[c] for c in 0..961 (host only; the one table the kernel reads); CGC_EINVAL outside.
+ * One launch per call, no workspace, no global atomics, integers only: outputs are bit-identical from call to call.  Bad dims, a kind,
+ * radius or op out of range (radius > 15 with ENTROPY), q_lo or q_hi outside 0..10000, q_lo > q_hi, within_bytes other than 1, 2, 4,
+ * 8 (with a within), or a null img / out with H * W > 0: CGC_EINVAL, nothing launched.  H * W = 0: nothing to do, 0. */
+#define CGC_RANK_QUANTILE 0
+#define CGC_RANK_RANGE 1
+#define CGC_RANK_ENTROPY 2
+int cgc_rank_max_radius(void);
+int cgc_rank_entropy_max_radius(void);
+int cgc_rank_tile_rows(void);
+int cgc_rank_tile_cols(int radius);
+int cgc_rank_entropy_term(int c);
+int cgc_rank_filter(const uint8_t* img, const void* within_or_null, int within_bytes, int H, int W, int kind, int radius, int op,
+                    int q_lo, int q_hi, void* out, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
