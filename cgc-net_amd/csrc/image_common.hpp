@@ -1,4 +1,5 @@
-// Helpers of the image stage (nuclei.hip, label.hip, edt.hip, geodesic.hip, reconstruct.hip, watershed.hip): the argument rules these
+// Helpers of the image stage (nuclei.hip, label.hip, edt.hip, geodesic.hip, reconstruct.hip, watershed.hip, and through
+// image_window.hpp window.hip, morph.hip, rank.hip): the argument rules these
 // files share, the one reader of "is this pixel zero", and the carver that lays out their workspaces.  Each stage has ONE layout function that uses up a Carver and fills the stage's pointer struct;
 // its *_ws_bytes entry point runs that function on a counting carver (layout_bytes) and its launchers run it on the caller's buffer,
 // so a size and the offsets behind it cannot drift apart.

@@ -20,14 +20,14 @@
 //              pixel, consecutive lanes on consecutive bytes.  Entries whose run passes the right end of the 256 columns take 0 there;
 //              no output reads them: x + w <= cols - 1 + halo + r <= 255.
 //   epilogue   complement (ERODE) or the sum (GRADIENT), the optional subtraction against other[y, x], one byte stored.
-// DWORDS is the launcher's choice as in window.hip: with W % 4 == 0, dword-aligned bases and a 1-byte `within` a lane's four pixels are
-// all inside or all outside the image and are one dword load per plane; otherwise pixel by pixel -- same values, slower.
-// The widths w(dy) are computed on the host in integers (the disk: the largest w with w^2 + dy^2 <= r^2) and travel, sorted by level,
-// as a kernel argument.
+// The halo, the loader of four pixels (flat_fetch, looked at straight away with flat_counted) and the launcher's choice DWORDS are
+// image_window.hpp's, shared with window.hip and rank.hip: with W % 4 == 0, dword-aligned bases and a 1-byte `within` a lane's four
+// pixels are all inside or all outside the image and are one dword load per plane; otherwise pixel by pixel -- same values, slower.
+// The widths w(dy) are computed on the host in integers (flat_width there) and travel, sorted by level, as a kernel argument.
 #include <stdint.h>
 
 #include "common.hpp"
-#include "image_common.hpp"
+#include "image_window.hpp"
 
 namespace {
 
@@ -38,10 +38,9 @@ constexpr int MORPH_DWORDS = MORPH_SPAN / 4;                    // one per lane
 constexpr int MORPH_WAVES = CGC_BLOCK / CGC_WAVE;
 constexpr int MORPH_PPT = MORPH_ROWS * MORPH_SPAN / CGC_BLOCK;  // output pixels of a thread, at most (at cols = 256)
 static_assert(MORPH_DWORDS == CGC_WAVE, "a wave owns whole LDS rows, one dword per lane");
-static_assert(MORPH_SPAN - 2 * ((MORPH_MAX_RADIUS + 3) & ~3) >= MORPH_SPAN / 2, "the pixel walk below assumes cols >= 128");
+static_assert(MORPH_SPAN - 2 * flat_halo(MORPH_MAX_RADIUS) >= MORPH_SPAN / 2, "the pixel walk below assumes cols >= 128");
 
-__host__ __device__ __forceinline__ int morph_halo(int r) { return (r + 3) & ~3; }
-__host__ __device__ __forceinline__ int morph_cols(int r) { return MORPH_SPAN - 2 * morph_halo(r); }
+__host__ __device__ __forceinline__ int morph_cols(int r) { return MORPH_SPAN - 2 * flat_halo(r); }
 static inline int morph_lds_bytes(int r, bool gradient) { return (MORPH_ROWS + 2 * r) * MORPH_SPAN * (gradient ? 2 : 1); }
 
 // The footprint as the kernel walks it: its rows sorted by the level of the table they are read from.  Dwords, so that the (uniform)
@@ -53,16 +52,6 @@ struct MorphFootprint {
 };
 static_assert(2 * MORPH_MAX_RADIUS + 1 < (1 << MORPH_LEVELS), "a row's run length has a level");
 
-// the half width of footprint row dy, in integers; kind and |dy| <= r have been checked
-static inline int morph_width(int kind, int r, int dy) {
-  const int a = dy < 0 ? -dy : dy;
-  if (kind == CGC_MORPH_SQUARE) return r;
-  if (kind == CGC_MORPH_DIAMOND) return r - a;
-  int w = 0;
-  while ((w + 1) * (w + 1) + a * a <= r * r) ++w;
-  return w;
-}
-
 typedef unsigned short morph_u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t morph_pk_max(uint32_t a, uint32_t b) {
   return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(morph_u16x2, a), __builtin_bit_cast(morph_u16x2, b)));
@@ -71,38 +60,6 @@ __device__ __forceinline__ uint32_t morph_pk_max(uint32_t a, uint32_t b) {
 __device__ __forceinline__ uint32_t morph_byte_max(uint32_t a, uint32_t b) {
   const uint32_t m = 0x00FF00FFu;
   return morph_pk_max(a & m, b & m) | (morph_pk_max((a >> 8) & m, (b >> 8) & m) << 8);
-}
-
-// Four adjacent pixels of row y from column x (a multiple of 4 relative to the tile; negative or >= W outside the image): v their
-// values, m 0xFF in every byte whose pixel is counted.  Addresses are clamped into the image, as in window.hip.
-template <bool WITHIN, bool DWORDS>
-__device__ __forceinline__ void morph_fetch(const uint8_t* __restrict__ img, const void* __restrict__ within, int wbytes, int H, int W,
-                                            int64_t x, int64_t y, uint32_t& v, uint32_t& m) {
-  const bool row = y >= 0 && y < H;
-  const int base = row ? (int)y * W : 0;                                // pixel indices fit int32: H W < 2^31
-  if (DWORDS) {
-    const bool ok = row && x >= 0 && x < W;
-    const int i = ok ? base + (int)x : 0;
-    v = *reinterpret_cast<const uint32_t*>(img + i);
-    m = ok ? 0xFFFFFFFFu : 0u;
-    if (WITHIN) {
-      const uint32_t q = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(within) + i);
-      uint32_t nz = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) nz |= ((q >> (8 * j)) & 255u) != 0 ? 255u << (8 * j) : 0u;
-      m &= nz;
-    }
-  } else {
-    v = m = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const bool in = row && x + j >= 0 && x + j < W;
-      const int i = in ? base + (int)(x + j) : 0;
-      const bool counted = in && (!WITHIN || image_nonzero(within, wbytes, i));
-      v |= (uint32_t)img[i] << (8 * j);
-      m |= counted ? 255u << (8 * j) : 0u;
-    }
-  }
 }
 
 // The walk over a thread's output pixels: pixel number t + 256 j of the tile in raster order, j = 0 .. cols / 8 - 1 (32 cols pixels in
@@ -148,7 +105,7 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_morph(const uint8_t* __restrict__
   extern __shared__ __attribute__((aligned(16))) uint32_t morph_lds[];   // [tables][rows][64 dwords]
   constexpr int TABLES = GRADIENT ? 2 : 1;
   const int rows = MORPH_ROWS + 2 * r;
-  const int halo = morph_halo(r), cols = MORPH_SPAN - 2 * halo;
+  const int halo = flat_halo(r), cols = MORPH_SPAN - 2 * halo;
   const int tile_x = blockIdx.x % tiles_x, tile_y = blockIdx.x / tiles_x;
   const int x0 = tile_x * cols, y0 = tile_y * MORPH_ROWS;               // x0 < W, y0 < H
   const int t = threadIdx.x, lane = t & (CGC_WAVE - 1), wave = t / CGC_WAVE;
@@ -158,8 +115,8 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_morph(const uint8_t* __restrict__
     const int64_t xg = (int64_t)x0 - halo + 4 * lane;
 #pragma unroll 4
     for (int row = wave; row < rows; row += MORPH_WAVES) {
-      uint32_t v, m;
-      morph_fetch<WITHIN, DWORDS>(img, within, wbytes, H, W, xg, (int64_t)y0 - r + row, v, m);
+      const FlatRow o = flat_fetch<WITHIN, DWORDS>(img, within, wbytes, H, W, xg, (int64_t)y0 - r + row);
+      const uint32_t v = o.p, m = flat_counted<DWORDS>(o);             // 0xFF in every byte whose pixel is counted
       if (GRADIENT) {
         morph_lds[row * MORPH_DWORDS + lane] = v & m;
         morph_lds[(rows + row) * MORPH_DWORDS + lane] = ~v & m;
@@ -254,8 +211,6 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_morph(const uint8_t* __restrict__
   }
 }
 
-static inline bool dword_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 struct MorphArgs {
   const uint8_t* img;
   const void* within;
@@ -290,20 +245,17 @@ void launch_morph_op(const MorphArgs& a, hipStream_t st) {
 
 extern "C" int cgc_morph_max_radius(void) { return MORPH_MAX_RADIUS; }
 extern "C" int cgc_morph_tile_rows(void) { return MORPH_ROWS; }
-extern "C" int cgc_morph_tile_cols(int radius) { return radius < 0 || radius > MORPH_MAX_RADIUS ? 0 : morph_cols(radius); }
+extern "C" int cgc_morph_tile_cols(int radius) { return bad_flat_radius(radius, MORPH_MAX_RADIUS) ? 0 : morph_cols(radius); }
 
 extern "C" int cgc_morph_footprint_width(int kind, int radius, int dy) {
-  if (kind < CGC_MORPH_SQUARE || kind > CGC_MORPH_DIAMOND || radius < 0 || radius > MORPH_MAX_RADIUS) return CGC_EINVAL;
-  if (dy < -radius || dy > radius) return CGC_EINVAL;
-  return morph_width(kind, radius, dy);
+  if (bad_footprint(kind, radius, MORPH_MAX_RADIUS) || dy < -radius || dy > radius) return CGC_EINVAL;
+  return flat_width(kind, radius, dy);
 }
 
 extern "C" int cgc_morph(const uint8_t* img, const void* within_or_null, int within_bytes, int H, int W, int kind, int radius, int op,
                          const uint8_t* other_or_null, int epilogue, uint8_t* out, cgc_stream_t stream) {
-  if (bad_image_dims(H, W) || radius < 0 || radius > MORPH_MAX_RADIUS) return CGC_EINVAL;
-  if (kind < CGC_MORPH_SQUARE || kind > CGC_MORPH_DIAMOND || op < CGC_MORPH_ERODE || op > CGC_MORPH_GRADIENT) return CGC_EINVAL;
-  if (epilogue < CGC_MORPH_PLAIN || epilogue > CGC_MORPH_MINUS_OTHER) return CGC_EINVAL;
-  if (within_or_null != nullptr && bad_elem_bytes(within_bytes)) return CGC_EINVAL;
+  if (bad_flat_image(H, W, within_or_null, within_bytes) || bad_footprint(kind, radius, MORPH_MAX_RADIUS)) return CGC_EINVAL;
+  if (op < CGC_MORPH_ERODE || op > CGC_MORPH_GRADIENT || epilogue < CGC_MORPH_PLAIN || epilogue > CGC_MORPH_MINUS_OTHER) return CGC_EINVAL;
   if ((int64_t)H * W == 0) return 0;
   if (img == nullptr || out == nullptr || (epilogue != CGC_MORPH_PLAIN && other_or_null == nullptr)) return CGC_EINVAL;
   MorphArgs a{img, within_or_null, within_or_null != nullptr ? within_bytes : 0, H, W, radius, op, {}, other_or_null, epilogue, out};
@@ -311,21 +263,14 @@ extern "C" int cgc_morph(const uint8_t* img, const void* within_or_null, int wit
   for (int k = 0; k < MORPH_LEVELS; ++k) {
     a.fp.start[k] = n;
     for (int dy = -radius; dy <= radius; ++dy) {
-      const int w = morph_width(kind, radius, dy);
+      const int w = flat_width(kind, radius, dy);
       if (31 - __builtin_clz((unsigned)(2 * w + 1)) == k) a.fp.entry[n++] = (uint32_t)(dy + radius) << 8 | (uint32_t)w;
     }
   }
   a.fp.start[MORPH_LEVELS] = n;                                         // = 2 radius + 1
-  // rows as dwords: every row starts on a dword boundary, and the flags of `within` are bytes
-  const bool dwords = (W & 3) == 0 && dword_aligned(img) && (within_or_null == nullptr || (within_bytes == 1 && dword_aligned(within_or_null)));
-  const hipStream_t st = as_stream(stream);
-  if (within_or_null != nullptr) {
-    if (dwords) launch_morph_op<true, true>(a, st);
-    else launch_morph_op<true, false>(a, st);
-  } else {
-    if (dwords) launch_morph_op<false, true>(a, st);
-    else launch_morph_op<false, false>(a, st);
-  }
+  flat_dispatch(within_or_null != nullptr, flat_dword_rows(img, within_or_null, within_bytes, W), [&](auto with, auto dwords) {
+    launch_morph_op<with.value, dwords.value>(a, as_stream(stream));
+  });
   CGC_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }

@@ -1,6 +1,7 @@
 // Rank filters of a uint8 image on gfx950: a quantile (QUANTILE), the difference of two quantiles (RANGE) or the Shannon entropy in
 // fixed point (ENTROPY) of the counted pixels under a flat footprint -- square, disk or diamond of radius r <= 63 (ENTROPY: r <= 15) --
-// clipped to the image and, if wanted, to the non-zero pixels of `within`.  Footprints, clipping and `within` are morph.hip's.
+// clipped to the image and, if wanted, to the non-zero pixels of `within`.  Footprints, clipping and `within` are flat_morphology's:
+// both stages take them from image_window.hpp.
 // Contract item by item: cgc-net_amd/kernels.py KernelSpec.rank_filter; design and measurements: DESIGN.md, "Rank filters".
 //
 // ONE kernel, k_rank<WITHIN, DWORDS, ENTROPY>, one launch per call, no workspace, no global atomics.  Every result is a function of
@@ -21,13 +22,14 @@
 //              the scan is n.
 //   entropy    every lane adds T[count] of its four bins from a copy of the term table in LDS; the same scan gives the wave's sum.
 //   store      a lane keeps the result of pixel x in a register, lane x mod 64; every 64 pixels the wave stores them together.
-// DWORDS is the launcher's choice as in morph.hip: with W % 4 == 0, dword-aligned bases and a 1-byte `within` a lane's four pixels are
-// one dword load per plane; otherwise pixel by pixel -- same values, slower.  The widths w(dy) are computed on the host in integers
-// and travel as a kernel argument.
+// The halo, the loader of four pixels (flat_fetch, looked at straight away with flat_counted) and the launcher's choice DWORDS are
+// image_window.hpp's: with W % 4 == 0, dword-aligned bases and a 1-byte `within` a lane's four pixels are one dword load per plane;
+// otherwise pixel by pixel -- same values, slower.  The widths w(dy) are computed on the host in integers (flat_width there) and
+// travel as a kernel argument.
 #include <stdint.h>
 
 #include "common.hpp"
-#include "image_common.hpp"
+#include "image_window.hpp"
 #include "rank_entropy_table.hpp"
 
 namespace {
@@ -51,8 +53,7 @@ static_assert((2 * RANK_ENTROPY_MAX_RADIUS + 1) * (2 * RANK_ENTROPY_MAX_RADIUS +
 const int32_t rank_terms_host[RANK_ENTROPY_TERMS] = {RANK_ENTROPY_TERM_LIST};
 __device__ const int32_t rank_terms_dev[RANK_ENTROPY_TERMS] = {RANK_ENTROPY_TERM_LIST};
 
-__host__ __device__ __forceinline__ int rank_halo(int r) { return (r + 3) & ~3; }
-__host__ __device__ __forceinline__ int rank_cols(int r) { return RANK_SPAN - 2 * rank_halo(r); }
+__host__ __device__ __forceinline__ int rank_cols(int r) { return RANK_SPAN - 2 * flat_halo(r); }
 static inline int rank_lds_bytes(int r, bool entropy) {
   return (RANK_ROWS + 2 * r) * (RANK_STRIDE + 4 * RANK_MASK_DWORDS) + RANK_WAVES * RANK_BINS * 4 + (entropy ? RANK_ENTROPY_TERMS * 4 : 0);
 }
@@ -60,48 +61,6 @@ static inline int rank_lds_bytes(int r, bool entropy) {
 struct RankFootprint {
   uint8_t w[2 * CGC_WAVE];                                      // w[i] = the half width of footprint row dy = i - r, i <= 2 r
 };
-
-// the half width of footprint row dy, in integers, as morph.hip's morph_width; kind and |dy| <= r have been checked
-static inline int rank_width(int kind, int r, int dy) {
-  const int a = dy < 0 ? -dy : dy;
-  if (kind == CGC_MORPH_SQUARE) return r;
-  if (kind == CGC_MORPH_DIAMOND) return r - a;
-  int w = 0;
-  while ((w + 1) * (w + 1) + a * a <= r * r) ++w;
-  return w;
-}
-
-// Four adjacent pixels of row y from column x (a multiple of 4 relative to the tile; negative or >= W outside the image): v their
-// values, m 0xFF in every byte whose pixel is counted.  Addresses are clamped into the image, as in morph.hip.
-template <bool WITHIN, bool DWORDS>
-__device__ __forceinline__ void rank_fetch(const uint8_t* __restrict__ img, const void* __restrict__ within, int wbytes, int H, int W,
-                                           int64_t x, int64_t y, uint32_t& v, uint32_t& m) {
-  const bool row = y >= 0 && y < H;
-  const int base = row ? (int)y * W : 0;                                // pixel indices fit int32: H W < 2^31
-  if (DWORDS) {
-    const bool ok = row && x >= 0 && x < W;
-    const int i = ok ? base + (int)x : 0;
-    v = *reinterpret_cast<const uint32_t*>(img + i);
-    m = ok ? 0xFFFFFFFFu : 0u;
-    if (WITHIN) {
-      const uint32_t q = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(within) + i);
-      uint32_t nz = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) nz |= ((q >> (8 * j)) & 255u) != 0 ? 255u << (8 * j) : 0u;
-      m &= nz;
-    }
-  } else {
-    v = m = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const bool in = row && x + j >= 0 && x + j < W;
-      const int i = in ? base + (int)(x + j) : 0;
-      const bool counted = in && (!WITHIN || image_nonzero(within, wbytes, i));
-      v |= (uint32_t)img[i] << (8 * j);
-      m |= counted ? 255u << (8 * j) : 0u;
-    }
-  }
-}
 
 // The lanes of a wave talk through its histogram: what they wrote before this point is what they read after it.  LDS operations of
 // one wave complete in order; the fence and the barrier keep the compiler from moving them across.
@@ -155,7 +114,7 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_rank(const uint8_t* __restrict__ 
                                                     void* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) uint32_t rank_lds[];    // [rows][65 dwords] | [rows][9 dwords] | [4][256] | T
   const int rows = RANK_ROWS + 2 * r;
-  const int halo = rank_halo(r), cols = RANK_SPAN - 2 * halo;
+  const int halo = flat_halo(r), cols = RANK_SPAN - 2 * halo;
   const int tile_x = blockIdx.x % tiles_x, tile_y = blockIdx.x / tiles_x;
   const int x0 = tile_x * cols, y0 = tile_y * RANK_ROWS;                // x0 < W, y0 < H
   const int t = threadIdx.x, lane = t & (CGC_WAVE - 1), wave = t / CGC_WAVE;
@@ -168,9 +127,9 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_rank(const uint8_t* __restrict__ 
   {
     const int64_t xg = (int64_t)x0 - halo + 4 * lane;
     for (int row = wave; row < rows; row += RANK_WAVES) {
-      uint32_t v, m;
-      rank_fetch<WITHIN, DWORDS>(img, within, wbytes, H, W, xg, (int64_t)y0 - r + row, v, m);
-      rank_lds[row * (RANK_STRIDE / 4) + lane] = v;
+      const FlatRow o = flat_fetch<WITHIN, DWORDS>(img, within, wbytes, H, W, xg, (int64_t)y0 - r + row);
+      const uint32_t m = flat_counted<DWORDS>(o);                       // 0xFF in every byte whose pixel is counted
+      rank_lds[row * (RANK_STRIDE / 4) + lane] = o.p;
       const unsigned long long b0 = __ballot(m & 1u), b1 = __ballot(m & 0x100u), b2 = __ballot(m & 0x10000u), b3 = __ballot(m & 0x1000000u);
       if (lane < 4) {
         const unsigned long long b = lane == 0 ? b0 : lane == 1 ? b1 : lane == 2 ? b2 : b3;
@@ -246,8 +205,6 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_rank(const uint8_t* __restrict__ 
   }
 }
 
-static inline bool dword_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 struct RankArgs {
   const uint8_t* img;
   const void* within;
@@ -275,30 +232,21 @@ void launch_rank_op(const RankArgs& a, hipStream_t st) {
 extern "C" int cgc_rank_max_radius(void) { return RANK_MAX_RADIUS; }
 extern "C" int cgc_rank_entropy_max_radius(void) { return RANK_ENTROPY_MAX_RADIUS; }
 extern "C" int cgc_rank_tile_rows(void) { return RANK_ROWS; }
-extern "C" int cgc_rank_tile_cols(int radius) { return radius < 0 || radius > RANK_MAX_RADIUS ? 0 : rank_cols(radius); }
+extern "C" int cgc_rank_tile_cols(int radius) { return bad_flat_radius(radius, RANK_MAX_RADIUS) ? 0 : rank_cols(radius); }
 extern "C" int cgc_rank_entropy_term(int c) { return c < 0 || c >= RANK_ENTROPY_TERMS ? CGC_EINVAL : rank_terms_host[c]; }
 
 extern "C" int cgc_rank_filter(const uint8_t* img, const void* within_or_null, int within_bytes, int H, int W, int kind, int radius, int op,
                                int q_lo, int q_hi, void* out, cgc_stream_t stream) {
-  if (bad_image_dims(H, W) || op < CGC_RANK_QUANTILE || op > CGC_RANK_ENTROPY) return CGC_EINVAL;
-  if (radius < 0 || radius > (op == CGC_RANK_ENTROPY ? RANK_ENTROPY_MAX_RADIUS : RANK_MAX_RADIUS)) return CGC_EINVAL;
-  if (kind < CGC_MORPH_SQUARE || kind > CGC_MORPH_DIAMOND) return CGC_EINVAL;
+  if (bad_flat_image(H, W, within_or_null, within_bytes) || op < CGC_RANK_QUANTILE || op > CGC_RANK_ENTROPY) return CGC_EINVAL;
+  if (bad_footprint(kind, radius, op == CGC_RANK_ENTROPY ? RANK_ENTROPY_MAX_RADIUS : RANK_MAX_RADIUS)) return CGC_EINVAL;
   if (q_lo < 0 || q_hi > 10000 || q_lo > q_hi) return CGC_EINVAL;
-  if (within_or_null != nullptr && bad_elem_bytes(within_bytes)) return CGC_EINVAL;
   if ((int64_t)H * W == 0) return 0;
   if (img == nullptr || out == nullptr) return CGC_EINVAL;
   RankArgs a{img, within_or_null, within_or_null != nullptr ? within_bytes : 0, H, W, radius, op, q_lo, q_hi, {}, out};
-  for (int dy = -radius; dy <= radius; ++dy) a.fp.w[dy + radius] = (uint8_t)rank_width(kind, radius, dy);
-  // rows as dwords: every row starts on a dword boundary, and the flags of `within` are bytes
-  const bool dwords = (W & 3) == 0 && dword_aligned(img) && (within_or_null == nullptr || (within_bytes == 1 && dword_aligned(within_or_null)));
-  const hipStream_t st = as_stream(stream);
-  if (within_or_null != nullptr) {
-    if (dwords) launch_rank_op<true, true>(a, st);
-    else launch_rank_op<true, false>(a, st);
-  } else {
-    if (dwords) launch_rank_op<false, true>(a, st);
-    else launch_rank_op<false, false>(a, st);
-  }
+  for (int dy = -radius; dy <= radius; ++dy) a.fp.w[dy + radius] = (uint8_t)flat_width(kind, radius, dy);
+  flat_dispatch(within_or_null != nullptr, flat_dword_rows(img, within_or_null, within_bytes, W), [&](auto with, auto dwords) {
+    launch_rank_op<with.value, dwords.value>(a, as_stream(stream));
+  });
   CGC_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }

@@ -14,8 +14,9 @@
 //              reads per sum (consecutive lanes take consecutive columns)
 //   epilogue   DECIDE = false: store n, S, Q.  DECIDE = true: the pixel's own value (loaded before the scan), the rule in integers,
 //              one byte stored.
-// DWORDS is the launcher's choice: with W % 4 == 0, dword-aligned bases and a 1-byte `within` a row of a thread is one dword load per
-// plane; otherwise (odd widths, an unaligned view, a `within` of wider elements) pixels are loaded one by one -- same sums, slower.
+// The halo, the loader of a row (flat_fetch) and the launcher's choice DWORDS are image_window.hpp's, shared with morph.hip and
+// rank.hip: with W % 4 == 0, dword-aligned bases and a 1-byte `within` a row of a thread is one dword load per plane; otherwise (odd
+// widths, an unaligned view, a `within` of wider elements) pixels are loaded one by one -- same sums, slower.
 // WIDTHS.  A column sum holds at most 255 pixels: n <= 255, S <= 65 025, Q <= 255^3 < 2^24.  The scan over 1024 columns keeps n
 // (<= 261 120) and S (<= 66 585 600) exactly in uint32.  The scan of Q reaches 1024 * 255^3 > 2^32 and WRAPS; a window's Q is a
 // difference of two scan entries and is at most 255^2 * 255^2 = 4 228 250 625 < 2^32, so the difference modulo 2^32 is the sum
@@ -24,7 +25,7 @@
 #include <stdint.h>
 
 #include "common.hpp"
-#include "image_common.hpp"
+#include "image_window.hpp"
 
 namespace {
 
@@ -33,53 +34,15 @@ constexpr int WIN_CPT = 4;                            // adjacent columns per th
 constexpr int WIN_COLS = CGC_BLOCK * WIN_CPT;         // 1024 columns a workgroup looks at
 constexpr int WIN_ROWS = 16;                          // rows of a tile
 constexpr int WIN_WAVES = CGC_BLOCK / CGC_WAVE;
-static_assert(WIN_COLS > 2 * ((WIN_MAX_RADIUS + 3) & ~3), "a strip must keep columns of its own at the largest radius");
-
-__host__ __device__ __forceinline__ int win_halo(int r) { return (r + 3) & ~3; }
+static_assert(WIN_COLS > 2 * flat_halo(WIN_MAX_RADIUS), "a strip must keep columns of its own at the largest radius");
 
 struct WinRule {
   int k64, offset, floor;
 };
 
-// One row of a thread's four adjacent columns, as loaded: four values and four flags (a non-zero byte = counted), not yet looked at
-// -- the loads of the next row are in flight while this row is scanned, and nothing may wait for them before then.
-struct WinRow {
-  uint32_t p, q;
-  bool ok;       // the row and the thread's columns lie inside the image
-};
-
-// x: the thread's first column, a multiple of 4 (negative in the left halo of the first strip, >= W past the image).  With DWORDS
-// (the launcher's choice: W % 4 == 0, aligned bases, a 1-byte `within`) a thread's columns are all inside or all outside the image, and
-// a row is one dword load per plane at an address clamped into the image: no branch.  Otherwise pixel by pixel, also at clamped
-// addresses.
-template <bool WITHIN, bool DWORDS>
-__device__ __forceinline__ WinRow win_fetch(const uint8_t* __restrict__ img, const void* __restrict__ within, int wbytes, int H, int W,
-                                            int64_t x, int64_t y) {
-  const bool row = y >= 0 && y < H;
-  const int base = row ? (int)y * W : 0;                                // pixel indices fit int32: H W < 2^31
-  WinRow o;
-  if (DWORDS) {
-    o.ok = row && x >= 0 && x < W;
-    const int i = o.ok ? base + (int)x : 0;
-    o.p = *reinterpret_cast<const uint32_t*>(img + i);
-    o.q = WITHIN ? *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(within) + i) : 0x01010101u;
-  } else {
-    o.ok = row;
-    o.p = o.q = 0;
-#pragma unroll
-    for (int j = 0; j < WIN_CPT; ++j) {
-      const bool in = row && x + j >= 0 && x + j < W;
-      const int i = in ? base + (int)(x + j) : 0;
-      const bool counted = in && (!WITHIN || image_nonzero(within, wbytes, i));
-      o.p |= (uint32_t)img[i] << (8 * j);
-      o.q |= (uint32_t)counted << (8 * j);
-    }
-  }
-  return o;
-}
-
-// w = 1 iff the pixel is inside the image and counted, v = its value or 0
-__device__ __forceinline__ void win_unpack(const WinRow& o, uint32_t (&v)[WIN_CPT], uint32_t (&w)[WIN_CPT]) {
+// The look at a row that flat_fetch loaded, and the first: the loads of the next row are in flight while this row is scanned, and
+// nothing may wait for them before then.  w = 1 iff the pixel is inside the image and counted, v = its value or 0
+__device__ __forceinline__ void win_unpack(const FlatRow& o, uint32_t (&v)[WIN_CPT], uint32_t (&w)[WIN_CPT]) {
 #pragma unroll
   for (int j = 0; j < WIN_CPT; ++j) {
     w[j] = o.ok && ((o.q >> (8 * j)) & 255u) != 0;
@@ -122,7 +85,7 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_window(const uint8_t* __restrict_
   __shared__ uint32_t wave_tot[2][WIN_WAVES][K];
   __shared__ __attribute__((aligned(16))) uint32_t P[2][K][WIN_COLS];   // the scans of two consecutive rows: two barriers per row
   const int strip = blockIdx.x % strips, chunk = blockIdx.x / strips;
-  const int halo = win_halo(r), tw = WIN_COLS - 2 * halo;
+  const int halo = flat_halo(r), tw = WIN_COLS - 2 * halo;
   const int64_t x0 = (int64_t)strip * tw;                               // < W
   const int y0 = chunk * WIN_ROWS, y1 = H - y0 < WIN_ROWS ? H : y0 + WIN_ROWS;      // y0 < H
   const int t = threadIdx.x, lane = t & (CGC_WAVE - 1), wave = t / CGC_WAVE;
@@ -138,7 +101,7 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_window(const uint8_t* __restrict_
     const int64_t ya = (int64_t)y0 - r - 1 > 0 ? (int64_t)y0 - r - 1 : 0, yb = (int64_t)y0 + r - 1 < H - 1 ? (int64_t)y0 + r - 1 : H - 1;
 #pragma unroll 4
     for (int64_t y = ya; y <= yb; ++y) {
-      win_unpack(win_fetch<WITHIN, DWORDS>(img, within, wbytes, H, W, xc, y), v, w);
+      win_unpack(flat_fetch<WITHIN, DWORDS>(img, within, wbytes, H, W, xc, y), v, w);
 #pragma unroll
       for (int j = 0; j < WIN_CPT; ++j) {
         c[0][j] += v[j];
@@ -158,16 +121,16 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_window(const uint8_t* __restrict_
     cols_in[j] = (int)((x + r < W - 1 ? x + r : W - 1) - (x - r > 0 ? x - r : 0)) + 1;
   }
   // the row that enters and the row that leaves are loaded one output row ahead: their latency hides behind the scan
-  WinRow enter = win_fetch<WITHIN, DWORDS>(img, within, wbytes, H, W, xc, (int64_t)y0 + r);
-  WinRow leave = win_fetch<WITHIN, DWORDS>(img, within, wbytes, H, W, xc, (int64_t)y0 - r - 1);
+  FlatRow enter = flat_fetch<WITHIN, DWORDS>(img, within, wbytes, H, W, xc, (int64_t)y0 + r);
+  FlatRow leave = flat_fetch<WITHIN, DWORDS>(img, within, wbytes, H, W, xc, (int64_t)y0 - r - 1);
 
   for (int y = y0; y < y1; ++y) {
     const int b = (y - y0) & 1;
     const int row0 = y * W + (int)x0;                                   // index of the tile's first pixel in this row: < H W
     win_unpack(enter, v, w);
     win_unpack(leave, lv, lw);
-    enter = win_fetch<WITHIN, DWORDS>(img, within, wbytes, H, W, xc, (int64_t)y + 1 + r);
-    leave = win_fetch<WITHIN, DWORDS>(img, within, wbytes, H, W, xc, (int64_t)y - r);
+    enter = flat_fetch<WITHIN, DWORDS>(img, within, wbytes, H, W, xc, (int64_t)y + 1 + r);
+    leave = flat_fetch<WITHIN, DWORDS>(img, within, wbytes, H, W, xc, (int64_t)y - r);
     uint32_t own[WIN_CPT];                                              // the pixels this thread decides: needed after the scan
     if (DECIDE) {
 #pragma unroll
@@ -224,16 +187,10 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_window(const uint8_t* __restrict_
   }
 }
 
-static inline bool bad_window_args(int H, int W, int radius, const void* within, int within_bytes) {
-  return bad_image_dims(H, W) || radius < 0 || radius > WIN_MAX_RADIUS || (within != nullptr && bad_elem_bytes(within_bytes));
-}
-
-static inline bool dword_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 template <bool WITHIN, bool DECIDE, bool DWORDS>
 void launch_window_as(const uint8_t* img, const void* within, int within_bytes, int H, int W, int radius, WinRule rule, int* n, int* s,
                       int64_t* q, uint8_t* fg, hipStream_t st) {
-  const int strips = (int)ceil_div64(W, WIN_COLS - 2 * win_halo(radius));
+  const int strips = (int)ceil_div64(W, WIN_COLS - 2 * flat_halo(radius));
   const int64_t blocks = strips * ceil_div64(H, WIN_ROWS);              // < H W / (768 WIN_ROWS) + H / WIN_ROWS + W / 768 + 1 < 2^31
   hipLaunchKernelGGL((k_window<WITHIN, DECIDE, DWORDS>), dim3((unsigned)blocks), dim3(CGC_BLOCK), 0, st, img, within, within_bytes, H, W,
                      radius, strips, rule, n, s, q, fg);
@@ -242,15 +199,9 @@ void launch_window_as(const uint8_t* img, const void* within, int within_bytes, 
 template <bool DECIDE>
 int launch_window(const uint8_t* img, const void* within, int within_bytes, int H, int W, int radius, WinRule rule, int* n, int* s,
                   int64_t* q, uint8_t* fg, hipStream_t st) {
-  // rows as dwords: every row starts on a dword boundary, and the flags of `within` are bytes
-  const bool dwords = (W & 3) == 0 && dword_aligned(img) && (within == nullptr || (within_bytes == 1 && dword_aligned(within)));
-  if (within != nullptr) {
-    if (dwords) launch_window_as<true, DECIDE, true>(img, within, within_bytes, H, W, radius, rule, n, s, q, fg, st);
-    else launch_window_as<true, DECIDE, false>(img, within, within_bytes, H, W, radius, rule, n, s, q, fg, st);
-  } else {
-    if (dwords) launch_window_as<false, DECIDE, true>(img, within, 0, H, W, radius, rule, n, s, q, fg, st);
-    else launch_window_as<false, DECIDE, false>(img, within, 0, H, W, radius, rule, n, s, q, fg, st);
-  }
+  flat_dispatch(within != nullptr, flat_dword_rows(img, within, within_bytes, W), [&](auto with, auto dwords) {
+    launch_window_as<with.value, DECIDE, dwords.value>(img, within, with.value ? within_bytes : 0, H, W, radius, rule, n, s, q, fg, st);
+  });
   CGC_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
@@ -260,12 +211,12 @@ int launch_window(const uint8_t* img, const void* within, int within_bytes, int 
 extern "C" int cgc_window_max_radius(void) { return WIN_MAX_RADIUS; }
 extern "C" int cgc_window_tile_rows(void) { return WIN_ROWS; }
 extern "C" int cgc_window_strip_cols(int radius) {
-  return radius < 0 || radius > WIN_MAX_RADIUS ? 0 : WIN_COLS - 2 * win_halo(radius);
+  return bad_flat_radius(radius, WIN_MAX_RADIUS) ? 0 : WIN_COLS - 2 * flat_halo(radius);
 }
 
 extern "C" int cgc_window_sums(const uint8_t* img, const void* within_or_null, int within_bytes, int H, int W, int radius, int* n, int* s,
                                int64_t* q, cgc_stream_t stream) {
-  if (bad_window_args(H, W, radius, within_or_null, within_bytes)) return CGC_EINVAL;
+  if (bad_flat_image(H, W, within_or_null, within_bytes) || bad_flat_radius(radius, WIN_MAX_RADIUS)) return CGC_EINVAL;
   if ((int64_t)H * W == 0) return 0;
   if (img == nullptr || n == nullptr || s == nullptr || q == nullptr) return CGC_EINVAL;
   return launch_window<false>(img, within_or_null, within_bytes, H, W, radius, WinRule{0, 0, -1}, n, s, q, nullptr, as_stream(stream));
@@ -273,7 +224,7 @@ extern "C" int cgc_window_sums(const uint8_t* img, const void* within_or_null, i
 
 extern "C" int cgc_local_threshold(const uint8_t* img, const void* within_or_null, int within_bytes, int H, int W, int radius, int k64,
                                    int offset, int floor, uint8_t* out, cgc_stream_t stream) {
-  if (bad_window_args(H, W, radius, within_or_null, within_bytes)) return CGC_EINVAL;
+  if (bad_flat_image(H, W, within_or_null, within_bytes) || bad_flat_radius(radius, WIN_MAX_RADIUS)) return CGC_EINVAL;
   if (k64 < -128 || k64 > 128 || offset < -255 || offset > 255 || floor < -1 || floor > 255) return CGC_EINVAL;
   if ((int64_t)H * W == 0) return 0;
   if (img == nullptr || out == nullptr) return CGC_EINVAL;

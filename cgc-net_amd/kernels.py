@@ -795,6 +795,11 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+def _within_args(within):
+    """The (pointer, element size) pair a flat-window entry point takes for ``within``: (NULL, 0) without one."""
+    return _ptr(within), within.element_size() if within is not None else 0
+
+
 class LaunchTimer(object):
     """HIP-event timing of every launch of the dominant 128 x 128 GEMM and of the wide SpMM between ``start()`` and ``stop()``
     (the library's measurement hook, csrc/timing.hip: events on the stream of the launch, whoever issues it -- the per-operator
@@ -1398,9 +1403,15 @@ class HipKernels(KernelSpec):
         return out
 
     @staticmethod
-    def _check_window_radius(fn, radius):
-        if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= WINDOW_MAX_RADIUS:
-            raise ValueError('%s: radius must be an integer in 0..%d, got %r' % (fn, WINDOW_MAX_RADIUS, radius))
+    def _check_flat_radius(fn, radius, top, what=''):
+        """The radius of a flat-window stage: an int (no bool) in 0..top; ``what`` names the case a smaller ``top`` belongs to."""
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= top:
+            raise ValueError('%s: radius must be an integer in 0..%d%s, got %r' % (fn, top, what, radius))
+
+    @staticmethod
+    def _check_footprint_kind(fn, kind):
+        if not isinstance(kind, str) or kind not in MORPH_KINDS:
+            raise ValueError("%s: kind must be 'square', 'disk' or 'diamond', got %r" % (fn, kind))
 
     @staticmethod
     def _check_rule(k64, offset, floor):
@@ -1417,32 +1428,30 @@ class HipKernels(KernelSpec):
         return int(self.lib.cgc_window_strip_cols(int(radius)))
 
     def window_sums(self, image, radius, within=None):
-        HipKernels._check_window_radius('window_sums', radius)
+        HipKernels._check_flat_radius('window_sums', radius, WINDOW_MAX_RADIUS)
         image, within = self._window_images(image, within)
         H, W = image.shape
         n, s = (torch.empty(H, W, dtype=torch.int32, device=image.device) for _ in range(2))
         q = torch.empty(H, W, dtype=torch.int64, device=image.device)
-        self._chk(self.lib.cgc_window_sums(_ptr(image), _ptr(within), within.element_size() if within is not None else 0, H, W, radius,
+        self._chk(self.lib.cgc_window_sums(_ptr(image), *_within_args(within), H, W, radius,
                                            _ptr(n), _ptr(s), _ptr(q), self._stream()), 'cgc_window_sums')
         return n, s, q
 
     def local_threshold(self, image, radius, k64, offset, floor, within=None):
-        HipKernels._check_window_radius('local_threshold', radius)
+        HipKernels._check_flat_radius('local_threshold', radius, WINDOW_MAX_RADIUS)
         HipKernels._check_rule(k64, offset, floor)
         image, within = self._window_images(image, within)
         H, W = image.shape
         out = torch.empty(H, W, dtype=torch.uint8, device=image.device)
-        self._chk(self.lib.cgc_local_threshold(_ptr(image), _ptr(within), within.element_size() if within is not None else 0, H, W,
+        self._chk(self.lib.cgc_local_threshold(_ptr(image), *_within_args(within), H, W,
                                                radius, k64, offset, floor, _ptr(out), self._stream()), 'cgc_local_threshold')
         return out
 
     @staticmethod
     def _check_morph(kind, radius, op, other, epilogue):
         """The refusals of flat_morphology that need no tensor: returns the library's codes (kind, op, epilogue)."""
-        if not isinstance(kind, str) or kind not in MORPH_KINDS:
-            raise ValueError("flat_morphology: kind must be 'square', 'disk' or 'diamond', got %r" % (kind,))
-        if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= MORPH_MAX_RADIUS:
-            raise ValueError('flat_morphology: radius must be an integer in 0..%d, got %r' % (MORPH_MAX_RADIUS, radius))
+        HipKernels._check_footprint_kind('flat_morphology', kind)
+        HipKernels._check_flat_radius('flat_morphology', radius, MORPH_MAX_RADIUS)
         if not isinstance(op, str) or op not in MORPH_OPS:
             raise ValueError("flat_morphology: op must be 'erode', 'dilate' or 'gradient', got %r" % (op,))
         if not (epilogue is None or isinstance(epilogue, str)) or epilogue not in MORPH_EPILOGUES:
@@ -1462,20 +1471,17 @@ class HipKernels(KernelSpec):
         image, within, other = self._image(image), self._image(within), self._image(other)      # after the refusals: may copy
         H, W = image.shape
         out = torch.empty(H, W, dtype=torch.uint8, device=image.device)
-        self._chk(self.lib.cgc_morph(_ptr(image), _ptr(within), within.element_size() if within is not None else 0, H, W, kind, radius,
+        self._chk(self.lib.cgc_morph(_ptr(image), *_within_args(within), H, W, kind, radius,
                                      op, _ptr(other), epilogue, _ptr(out), self._stream()), 'cgc_morph')
         return out
 
     @staticmethod
     def _check_rank(kind, radius, op, q_lo, q_hi):
         """The refusals of rank_filter that need no tensor: returns the library's codes (kind, op)."""
-        if not isinstance(kind, str) or kind not in MORPH_KINDS:
-            raise ValueError("rank_filter: kind must be 'square', 'disk' or 'diamond', got %r" % (kind,))
+        HipKernels._check_footprint_kind('rank_filter', kind)
         if not isinstance(op, str) or op not in RANK_OPS:
             raise ValueError("rank_filter: op must be 'quantile', 'range' or 'entropy', got %r" % (op,))
-        top = ENTROPY_MAX_RADIUS if op == 'entropy' else RANK_MAX_RADIUS
-        if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= top:
-            raise ValueError('rank_filter: radius must be an integer in 0..%d for %r, got %r' % (top, op, radius))
+        HipKernels._check_flat_radius('rank_filter', radius, ENTROPY_MAX_RADIUS if op == 'entropy' else RANK_MAX_RADIUS, ' for %r' % (op,))
         for name, q in (('q_lo', q_lo), ('q_hi', q_hi)):
             if isinstance(q, bool) or not isinstance(q, int) or not 0 <= q <= 10000:
                 raise ValueError('rank_filter: %s must be an integer in 0..10000, got %r' % (name, q))
@@ -1499,7 +1505,7 @@ class HipKernels(KernelSpec):
         image, within = self._image(image), self._image(within)               # after the refusals: may copy
         H, W = image.shape
         out = torch.empty(H, W, dtype=torch.int32 if op == RANK_OPS['entropy'] else torch.uint8, device=image.device)
-        self._chk(self.lib.cgc_rank_filter(_ptr(image), _ptr(within), within.element_size() if within is not None else 0, H, W, kind,
+        self._chk(self.lib.cgc_rank_filter(_ptr(image), *_within_args(within), H, W, kind,
                                            radius, op, q_lo, q_hi, _ptr(out), self._stream()), 'cgc_rank_filter')
         return out
 

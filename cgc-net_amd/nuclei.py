@@ -1002,12 +1002,12 @@ MORPH_MAX_RADIUS = kernels.MORPH_MAX_RADIUS
 MORPH_FOOTPRINTS = tuple(kernels.MORPH_KINDS)
 
 
-def _check_morph(fn, image, radius, footprint, within):
-    """The refusals the flat-morphology functions share, before any launch: returns (the image as uint8 -- a bool image as 0 / 1,
-    without a copy --, radius as an int)."""
+def _check_flat(fn, image, radius, footprint, within, top=MORPH_MAX_RADIUS):
+    """The refusals the flat-morphology functions and the rank filters share, before any launch (``top``: the largest radius):
+    returns (the image as uint8 -- a bool image as 0 / 1, without a copy --, radius as an int)."""
     _check_image(fn, 'image', image, (torch.bool, torch.uint8))
     _check_within(fn, within, image)
-    radius = _check_int_in('radius', radius, 0, MORPH_MAX_RADIUS)
+    radius = _check_int_in('radius', radius, 0, top)
     if not isinstance(footprint, str) or footprint not in kernels.MORPH_KINDS:
         raise ValueError("footprint must be 'disk', 'square' or 'diamond', got %r" % (footprint,))
     return (image.view(torch.uint8) if image.dtype == torch.bool else image), radius
@@ -1028,7 +1028,7 @@ def erode(image, radius, footprint='disk', within=None):
     Exact, one launch (kernels.KernelSpec.flat_morphology).
 
     Host syncs: none."""
-    x, radius = _check_morph('erode', image, radius, footprint, within)
+    x, radius = _check_flat('erode', image, radius, footprint, within)
     out = _morph(x, footprint, radius, 'erode', within)
     return out != 0 if image.dtype == torch.bool else out
 
@@ -1038,7 +1038,7 @@ def dilate(image, radius, footprint='disk', within=None):
     erode.  Where no pixel counts the result is 0.  dilate(x) == 255 - erode(255 - x).
 
     Host syncs: none."""
-    x, radius = _check_morph('dilate', image, radius, footprint, within)
+    x, radius = _check_flat('dilate', image, radius, footprint, within)
     out = _morph(x, footprint, radius, 'dilate', within)
     return out != 0 if image.dtype == torch.bool else out
 
@@ -1048,7 +1048,7 @@ def opening(image, radius, footprint='disk', within=None):
     the image, idempotent.  Arguments and result as erode; a bool image is computed as 0 / 1 and converted at the end.  Two launches.
 
     Host syncs: none."""
-    x, radius = _check_morph('opening', image, radius, footprint, within)
+    x, radius = _check_flat('opening', image, radius, footprint, within)
     out = _morph(_morph(x, footprint, radius, 'erode', within), footprint, radius, 'dilate', within)
     return out != 0 if image.dtype == torch.bool else out
 
@@ -1058,7 +1058,7 @@ def closing(image, radius, footprint='disk', within=None):
     result as erode.  Two launches.
 
     Host syncs: none."""
-    x, radius = _check_morph('closing', image, radius, footprint, within)
+    x, radius = _check_flat('closing', image, radius, footprint, within)
     out = _morph(_morph(x, footprint, radius, 'dilate', within), footprint, radius, 'erode', within)
     return out != 0 if image.dtype == torch.bool else out
 
@@ -1070,7 +1070,7 @@ def white_tophat(image, radius, footprint='disk', within=None):
     opening is never above the image and the clamp never acts).
 
     Host syncs: none."""
-    x, radius = _check_morph('white_tophat', image, radius, footprint, within)
+    x, radius = _check_flat('white_tophat', image, radius, footprint, within)
     return _morph(_morph(x, footprint, radius, 'erode', within), footprint, radius, 'dilate', within, x, 'other_minus')
 
 
@@ -1078,7 +1078,7 @@ def black_tophat(image, radius, footprint='disk', within=None):
     """closing(image) - image: dark structures smaller than the footprint.  Arguments and result as white_tophat.  Two launches.
 
     Host syncs: none."""
-    x, radius = _check_morph('black_tophat', image, radius, footprint, within)
+    x, radius = _check_flat('black_tophat', image, radius, footprint, within)
     return _morph(_morph(x, footprint, radius, 'dilate', within), footprint, radius, 'erode', within, x, 'minus_other')
 
 
@@ -1088,7 +1088,7 @@ def morph_gradient(image, radius, footprint='disk', within=None):
     launch: both extrema are found in the same pass.
 
     Host syncs: none."""
-    x, radius = _check_morph('morph_gradient', image, radius, footprint, within)
+    x, radius = _check_flat('morph_gradient', image, radius, footprint, within)
     return _morph(x, footprint, radius, 'gradient', within)
 
 
@@ -1098,7 +1098,7 @@ def open_by_reconstruction(image, radius, footprint='disk', connectivity=1, with
     image, radius, footprint, within: as erode; connectivity: as reconstruct.  Returns the image's dtype.
 
     Host syncs: those of reconstruct."""
-    _check_morph('open_by_reconstruction', image, radius, footprint, within)
+    _check_flat('open_by_reconstruction', image, radius, footprint, within)
     _check_connectivity(connectivity)
     return reconstruct(erode(image, radius, footprint, within), image, 'dilation', connectivity)
 
@@ -1108,7 +1108,7 @@ def close_by_reconstruction(image, radius, footprint='disk', connectivity=1, wit
     image <= close_by_reconstruction <= closing.  Arguments and result as open_by_reconstruction.
 
     Host syncs: those of reconstruct."""
-    _check_morph('close_by_reconstruction', image, radius, footprint, within)
+    _check_flat('close_by_reconstruction', image, radius, footprint, within)
     _check_connectivity(connectivity)
     return reconstruct(dilate(image, radius, footprint, within), image, 'erosion', connectivity)
 
@@ -1135,17 +1135,6 @@ def rank_q10k(q):
     return q10k
 
 
-def _check_rank(fn, image, radius, footprint, within, top=RANK_MAX_RADIUS):
-    """The refusals the rank filters share, before any launch: returns (the image as uint8 -- a bool image as 0 / 1, without a copy
-    --, radius as an int)."""
-    _check_image(fn, 'image', image, (torch.bool, torch.uint8))
-    _check_within(fn, within, image)
-    radius = _check_int_in('radius', radius, 0, top)
-    if not isinstance(footprint, str) or footprint not in kernels.MORPH_KINDS:
-        raise ValueError("footprint must be 'disk', 'square' or 'diamond', got %r" % (footprint,))
-    return (image.view(torch.uint8) if image.dtype == torch.bool else image), radius
-
-
 def _rank(x, footprint, radius, op, q_lo, q_hi, within):
     with torch.cuda.device(x.device):
         return kernels.get().rank_filter(x, footprint, radius, op, q_lo, q_hi, within)
@@ -1160,7 +1149,7 @@ def rank_filter(image, radius, q, footprint='disk', within=None):
     0 / 1 and gives a bool result.  Exact integers, one launch (kernels.KernelSpec.rank_filter).
 
     Host syncs: none."""
-    x, radius = _check_rank('rank_filter', image, radius, footprint, within)
+    x, radius = _check_flat('rank_filter', image, radius, footprint, within, RANK_MAX_RADIUS)
     out = _rank(x, footprint, radius, 'quantile', 0, rank_q10k(q), within)
     return out != 0 if image.dtype == torch.bool else out
 
@@ -1172,7 +1161,7 @@ def median(image, radius, footprint='disk', within=None):
     and a window in which nothing is counted gives False.  Arguments and result as rank_filter.
 
     Host syncs: none."""
-    x, radius = _check_rank('median', image, radius, footprint, within)
+    x, radius = _check_flat('median', image, radius, footprint, within, RANK_MAX_RADIUS)
     out = _rank(x, footprint, radius, 'quantile', 0, 5000, within)
     return out != 0 if image.dtype == torch.bool else out
 
@@ -1184,7 +1173,7 @@ def quantile_range(image, radius, q_lo, q_hi, footprint='disk', within=None):
     bool image counts as 0 / 1), 0 where no pixel counts.
 
     Host syncs: none."""
-    x, radius = _check_rank('quantile_range', image, radius, footprint, within)
+    x, radius = _check_flat('quantile_range', image, radius, footprint, within, RANK_MAX_RADIUS)
     lo, hi = rank_q10k(q_lo), rank_q10k(q_hi)
     if lo > hi:
         raise ValueError('q_lo <= q_hi (got %r > %r)' % (q_lo, q_hi))
@@ -1200,7 +1189,7 @@ def local_entropy(image, radius=3, footprint='disk', within=None, raw=False):
     inputs.
 
     Host syncs: none."""
-    x, radius = _check_rank('local_entropy', image, radius, footprint, within, ENTROPY_MAX_RADIUS)
+    x, radius = _check_flat('local_entropy', image, radius, footprint, within, ENTROPY_MAX_RADIUS)
     h16 = _rank(x, footprint, radius, 'entropy', 0, 0, within)
     return h16 if raw else h16.to(torch.float32) / 65536.0
 
