@@ -1,0 +1,379 @@
+// Region statistics of a label image on gfx950: per label value the count, sum, sum of squares, extrema with their positions
+// (MOMENTS) or the 256-bin histogram (HISTOGRAM) of a second plane over the label's pixels, and quantiles read off such histograms
+// (QUANTILES).  Contract item by item: cgc-net_amd/kernels.py KernelSpec.region_statistics / region_histogram / region_quantiles;
+// design and measurements: DESIGN.md, "Region statistics".
+//
+// A pixel p is *counted* in row L iff labels[p] == L, 0 <= L <= max_label, and within is null or non-zero at p.  A pixel whose label
+// lies outside [0, max_label] is counted nowhere and adds one to *meta, whatever `within` says there.
+// Launches of one MOMENTS call:
+//   k_region_init      count = sum = sumsq = 0, the two key tables of the workspace to "nothing yet", *meta = 0
+//   k_region_moments   one 64 x 64 tile per workgroup.  A thread owns 16 consecutive rows of one column: all its loads are issued
+//                      before the first is looked at, and a run of equal labels down the column is summed in registers.  A finished run
+//                      is folded into an LDS table keyed by label (REGION_SLOTS slots, LDS atomics); after a barrier every claimed slot
+//                      goes to the global tables with one integer atomic per quantity.
+//   k_region_finish    keys -> min, max, argmin, argmax; the values of an empty row
+// HISTOGRAM: hipMemsetAsync, then k_region_hist -- the same tile, table and walk, with 256 16-bit bins per slot (two per dword; a bin
+// holds at most the 4096 pixels of a tile) and one LDS atomic per counted pixel; a claimed slot is flushed as 256 consecutive counters.
+// OVERFLOW.  region_slot() probes at most REGION_PROBES <= REGION_SLOTS slots and never waits: a label that finds neither itself nor
+// an empty slot there is sent to the global tables directly (a run at a time in MOMENTS, a pixel at a time in HISTOGRAM).  Both routes
+// end in the same integer atomics on the same global words, so which pixels take which route -- it depends on the order in which lanes
+// arrive -- changes no result: integer sums, and minima / maxima of 64-bit keys, are independent of order.  A tile in which every pixel
+// has its own label is an ordinary input: 64 labels fold, the rest go direct.
+// EXTREMA.  The value and its position travel as one key: min key = (v ^ 0x80000000) << 32 | i, combined by unsigned min; max key =
+// (v ^ 0x80000000) << 32 | ~i, combined by unsigned max -- of equal values the smallest raster index i wins in both, in a thread's
+// run (i grows down the column, strict comparisons), in LDS and in global memory.  No key equals the initial ~0 / 0: i < 2^31.
+#include <stdint.h>
+
+#include "common.hpp"
+#include "image_common.hpp"
+#include "rank_scan.hpp"
+
+namespace {
+
+constexpr int REGION_TILE = 64;                                  // tile side (exported: the tests place seams from it)
+constexpr int REGION_BAND = REGION_TILE * REGION_TILE / CGC_BLOCK;      // 16 consecutive rows of one column per thread
+constexpr int REGION_SLOT_BITS = 6;
+constexpr int REGION_SLOTS = 1 << REGION_SLOT_BITS;              // labels a tile folds in LDS (exported)
+constexpr int REGION_PROBES = 8;                                 // slots a label looks at before it goes to global memory
+constexpr int REGION_EMPTY = -1;                                 // no label: only labels in [0, max_label] reach the table
+constexpr int REGION_MAX_Q = 8;
+constexpr int REGION_INIT_BLOCKS = 4096;
+constexpr unsigned long long REGION_NO_MIN = ~0ull, REGION_NO_MAX = 0ull;
+static_assert(REGION_PROBES <= REGION_SLOTS, "a probe sequence is bounded by the slot count");
+static_assert(REGION_TILE * REGION_TILE < (1 << 16), "a 16-bit bin holds a whole tile of one label and one value");
+static_assert(REGION_TILE == CGC_WAVE && REGION_BAND * (CGC_BLOCK / CGC_WAVE) == REGION_TILE, "a wave is one row of a tile, four bands");
+
+typedef unsigned long long u64;
+
+struct RegionWs {
+  u64* kmin;      // [max_label + 1] the smallest (value, index) key of a row
+  u64* kmax;      // [max_label + 1] the largest (value, ~index) key
+};
+static inline RegionWs region_layout(Carver&& c, int64_t rows) {
+  RegionWs w;
+  w.kmin = c.take<u64>(rows);
+  w.kmax = c.take<u64>(rows);
+  return w;
+}
+
+__device__ __forceinline__ u64 region_min_key(int v, int i) { return ((u64)((uint32_t)v ^ 0x80000000u) << 32) | (uint32_t)i; }
+__device__ __forceinline__ u64 region_max_key(int v, int i) { return ((u64)((uint32_t)v ^ 0x80000000u) << 32) | (uint32_t)~i; }
+
+// The slot of label L in an LDS table of REGION_SLOTS keys, claimed if need be; -1 if REGION_PROBES slots hold other labels.  A key
+// only ever changes from REGION_EMPTY to a label, so a slot that once answered L answers L for the rest of the tile.
+__device__ __forceinline__ int region_slot(int* key, int L) {
+  const unsigned h = ((unsigned)L * 0x9E3779B1u) >> (32 - REGION_SLOT_BITS);
+  for (int p = 0; p < REGION_PROBES; ++p) {
+    const int s = (int)((h + p) & (REGION_SLOTS - 1));
+    int k = __hip_atomic_load(&key[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (k == REGION_EMPTY) {
+      k = atomicCAS(&key[s], REGION_EMPTY, L);
+      if (k == REGION_EMPTY) return s;
+    }
+    if (k == L) return s;
+  }
+  return -1;
+}
+
+// The 16 pixels of a thread: labels, values and the bits "counted" and "refused" (label outside [0, max_label]).  Addresses are clamped
+// into the image, so that no load needs a branch; what lies outside is neither counted nor refused.
+template <typename T, bool WITHIN>
+struct RegionColumn {
+  int lab[REGION_BAND], val[REGION_BAND];
+  unsigned counted, refused;
+  int first;                                                     // raster index of the thread's first pixel (meaningful if inside)
+  __device__ __forceinline__ void load(const int* __restrict__ labels, const T* __restrict__ values, const void* __restrict__ within,
+                                       int wbytes, int H, int W, int tiles_x, int max_label) {
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int x = tx * REGION_TILE + (threadIdx.x & (REGION_TILE - 1));
+    const int y0 = ty * REGION_TILE + (threadIdx.x / REGION_TILE) * REGION_BAND;
+    const int xc = x < W ? x : W - 1;
+    unsigned on = 0;
+#pragma unroll
+    for (int k = 0; k < REGION_BAND; ++k) {
+      const int yc = y0 + k < H ? y0 + k : H - 1;
+      const int64_t i = (int64_t)yc * W + xc;
+      lab[k] = labels[i];
+      val[k] = (int)values[i];
+      if (WITHIN) on |= (unsigned)image_nonzero(within, wbytes, i) << k;
+    }
+    counted = refused = 0;
+#pragma unroll
+    for (int k = 0; k < REGION_BAND; ++k) {
+      const bool inside = x < W && y0 + k < H;
+      const bool bad = lab[k] < 0 || lab[k] > max_label;
+      refused |= (unsigned)(inside && bad) << k;
+      counted |= (unsigned)(inside && !bad && (!WITHIN || (on >> k & 1u))) << k;
+    }
+    first = (int)((int64_t)y0 * W + x);                          // < H W < 2^31 whenever a bit of `counted` is set
+  }
+};
+
+struct RegionMoments {
+  int key[REGION_SLOTS];
+  int cnt[REGION_SLOTS];
+  u64 sum[REGION_SLOTS], sq[REGION_SLOTS], kmin[REGION_SLOTS], kmax[REGION_SLOTS];
+};
+
+struct RegionTables {
+  int* count;
+  u64 *sum, *sumsq, *kmin, *kmax;      // sumsq may be null
+};
+
+template <typename T, bool WITHIN>
+__global__ void __launch_bounds__(CGC_BLOCK) k_region_moments(const int* __restrict__ labels, const T* __restrict__ values,
+                                                              const void* __restrict__ within, int wbytes, int H, int W, int tiles_x,
+                                                              int max_label, RegionTables g, int* meta) {
+  __shared__ RegionMoments t;
+  for (int i = threadIdx.x; i < REGION_SLOTS; i += CGC_BLOCK) {
+    t.key[i] = REGION_EMPTY;
+    t.cnt[i] = 0;
+    t.sum[i] = t.sq[i] = 0;
+    t.kmin[i] = REGION_NO_MIN;
+    t.kmax[i] = REGION_NO_MAX;
+  }
+  RegionColumn<T, WITHIN> c;
+  c.load(labels, values, within, wbytes, H, W, tiles_x, max_label);
+  __syncthreads();
+  const bool with_sq = g.sumsq != nullptr;
+
+  // the run in flight: label rl (REGION_EMPTY: none), rc pixels, their sum and sum of squares, the first smallest and first largest
+  int rl = REGION_EMPTY, rc = 0, vmin = 0, imin = 0, vmax = 0, imax = 0;
+  int64_t rs = 0, rq = 0;
+  auto fold = [&]() {
+    const u64 kmn = region_min_key(vmin, imin), kmx = region_max_key(vmax, imax);
+    const int s = region_slot(t.key, rl);
+    if (s >= 0) {
+      atomicAdd(&t.cnt[s], rc);
+      atomicAdd(&t.sum[s], (u64)rs);
+      if (with_sq) atomicAdd(&t.sq[s], (u64)rq);
+      atomicMin(&t.kmin[s], kmn);
+      atomicMax(&t.kmax[s], kmx);
+    } else {
+      atomicAdd(&g.count[rl], rc);
+      atomicAdd(&g.sum[rl], (u64)rs);
+      if (with_sq) atomicAdd(&g.sumsq[rl], (u64)rq);
+      atomicMin(&g.kmin[rl], kmn);
+      atomicMax(&g.kmax[rl], kmx);
+    }
+  };
+#pragma unroll
+  for (int k = 0; k <= REGION_BAND; ++k) {
+    const bool on = k < REGION_BAND && (c.counted >> k & 1u);
+    const int L = on ? c.lab[k < REGION_BAND ? k : 0] : REGION_EMPTY;
+    if (rl != REGION_EMPTY && (L != rl || k == REGION_BAND)) {      // the run ends: at another label, at a pixel not counted, at the end
+      fold();
+      rl = REGION_EMPTY;
+    }
+    if (on) {
+      const int v = c.val[k < REGION_BAND ? k : 0], i = c.first + k * W;
+      if (rl == REGION_EMPTY) {
+        rl = L;
+        rc = 0;
+        rs = rq = 0;
+        vmin = vmax = v;
+        imin = imax = i;
+      }
+      ++rc;
+      rs += v;
+      rq += (int64_t)v * v;                                       // used for values of at most 16 bits only: 16 * 2^30
+      if (v < vmin) vmin = v, imin = i;
+      if (v > vmax) vmax = v, imax = i;
+    }
+  }
+  if (c.refused != 0) atomicAdd(meta, (int)__builtin_popcount(c.refused));
+  __syncthreads();
+  for (int s = threadIdx.x; s < REGION_SLOTS; s += CGC_BLOCK) {
+    const int L = t.key[s];
+    if (L == REGION_EMPTY) continue;
+    atomicAdd(&g.count[L], t.cnt[s]);
+    atomicAdd(&g.sum[L], t.sum[s]);
+    if (with_sq) atomicAdd(&g.sumsq[L], t.sq[s]);
+    atomicMin(&g.kmin[L], t.kmin[s]);
+    atomicMax(&g.kmax[L], t.kmax[s]);
+  }
+}
+
+__global__ void __launch_bounds__(CGC_BLOCK) k_region_init(int rows, RegionTables g, int* meta) {
+  for (int64_t r = (int64_t)blockIdx.x * CGC_BLOCK + threadIdx.x; r < rows; r += (int64_t)gridDim.x * CGC_BLOCK) {
+    g.count[r] = 0;
+    g.sum[r] = 0;
+    if (g.sumsq != nullptr) g.sumsq[r] = 0;
+    g.kmin[r] = REGION_NO_MIN;
+    g.kmax[r] = REGION_NO_MAX;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) *meta = 0;
+}
+
+__global__ void __launch_bounds__(CGC_BLOCK) k_region_finish(int rows, const int* __restrict__ count, const u64* __restrict__ kmin,
+                                                             const u64* __restrict__ kmax, int* __restrict__ mn, int* __restrict__ mx,
+                                                             int* __restrict__ amin, int* __restrict__ amax) {
+  for (int64_t r = (int64_t)blockIdx.x * CGC_BLOCK + threadIdx.x; r < rows; r += (int64_t)gridDim.x * CGC_BLOCK) {
+    const bool any = count[r] != 0;
+    const u64 a = kmin[r], b = kmax[r];
+    mn[r] = any ? (int)((uint32_t)(a >> 32) ^ 0x80000000u) : 0;
+    mx[r] = any ? (int)((uint32_t)(b >> 32) ^ 0x80000000u) : 0;
+    amin[r] = any ? (int)(uint32_t)a : -1;
+    amax[r] = any ? (int)~(uint32_t)b : -1;
+  }
+}
+
+struct RegionHist {
+  int key[REGION_SLOTS];
+  uint32_t bins[REGION_SLOTS * 128];      // slot s, value v: the half v & 1 of dword 128 s + (v >> 1)
+};
+
+template <bool WITHIN>
+__global__ void __launch_bounds__(CGC_BLOCK) k_region_hist(const int* __restrict__ labels, const uint8_t* __restrict__ values,
+                                                           const void* __restrict__ within, int wbytes, int H, int W, int tiles_x,
+                                                           int max_label, int* hist, int* meta) {
+  __shared__ RegionHist t;
+  for (int i = threadIdx.x; i < REGION_SLOTS; i += CGC_BLOCK) t.key[i] = REGION_EMPTY;
+  for (int i = threadIdx.x; i < REGION_SLOTS * 128; i += CGC_BLOCK) t.bins[i] = 0;
+  RegionColumn<uint8_t, WITHIN> c;
+  c.load(labels, values, within, wbytes, H, W, tiles_x, max_label);
+  __syncthreads();
+  int cl = REGION_EMPTY, cs = -1;                                 // the label of the pixel above and its slot
+#pragma unroll
+  for (int k = 0; k < REGION_BAND; ++k) {
+    if (!(c.counted >> k & 1u)) continue;
+    const int L = c.lab[k], v = c.val[k];
+    if (L != cl) {
+      cl = L;
+      cs = region_slot(t.key, L);
+    }
+    if (cs >= 0) atomicAdd(&t.bins[cs * 128 + (v >> 1)], 1u << ((v & 1) * 16));
+    else atomicAdd(&hist[(int64_t)L * 256 + v], 1);
+  }
+  if (c.refused != 0) atomicAdd(meta, (int)__builtin_popcount(c.refused));
+  __syncthreads();
+  const int v = threadIdx.x;                                      // CGC_BLOCK == 256: a thread flushes one value of every claimed slot
+  for (int s = 0; s < REGION_SLOTS; ++s) {
+    const int L = t.key[s];                                       // uniform
+    if (L == REGION_EMPTY) continue;
+    const int n = (int)(t.bins[s * 128 + (v >> 1)] >> ((v & 1) * 16) & 0xffffu);
+    if (n != 0) atomicAdd(&hist[(int64_t)L * 256 + v], n);
+  }
+}
+
+struct RegionQuantiles {
+  int n;
+  int q[REGION_MAX_Q];
+};
+
+// one wave per row: four bins per lane, rank.hip's scan and search
+__global__ void __launch_bounds__(CGC_BLOCK) k_region_quantiles(const uint32_t* __restrict__ hist, int64_t rows, RegionQuantiles q,
+                                                                uint8_t* __restrict__ out) {
+  const int lane = threadIdx.x & (CGC_WAVE - 1);
+  const int64_t row = (int64_t)blockIdx.x * (CGC_BLOCK / CGC_WAVE) + threadIdx.x / CGC_WAVE;
+  if (row >= rows) return;                                        // the whole wave
+  const uint4 c = reinterpret_cast<const uint4*>(hist + row * 256)[lane];
+  const uint32_t incl = rank_wave_scan(c.x + c.y + c.z + c.w);
+  const uint32_t n = __builtin_amdgcn_readlane(incl, CGC_WAVE - 1);
+  for (int j = 0; j < q.n; ++j) {
+    int value = 0;
+    if (n > 0) {
+      const uint64_t k = (uint64_t)n * (uint32_t)q.q[j] / 10000u;   // n q10k < 2^46
+      value = rank_value(c, incl, k < n - 1 ? (uint32_t)k : n - 1);
+    }
+    if (lane == 0) out[row * q.n + j] = (uint8_t)value;
+  }
+}
+
+static inline bool bad_region(int H, int W, int max_label, const void* within, int wbytes) {
+  return bad_image_dims(H, W) || max_label < 0 || max_label == 0x7fffffff || (within != nullptr && bad_elem_bytes(wbytes));
+}
+static inline int region_blocks(int64_t rows) {
+  const int64_t b = ceil_div64(rows, CGC_BLOCK);
+  return (int)(b < REGION_INIT_BLOCKS ? b : REGION_INIT_BLOCKS);
+}
+
+template <typename T>
+void launch_moments(const int* labels, const void* values, const void* within, int wbytes, int H, int W, int max_label,
+                    const RegionTables& g, int* meta, hipStream_t st) {
+  const int tiles_x = ceil_div(W, REGION_TILE);
+  const dim3 grid((unsigned)((int64_t)tiles_x * ceil_div(H, REGION_TILE)));      // < 2^31 / 4096 + H / 64 + W / 64 + 1
+  if (within != nullptr)
+    hipLaunchKernelGGL((k_region_moments<T, true>), grid, dim3(CGC_BLOCK), 0, st, labels, static_cast<const T*>(values), within, wbytes, H, W,
+                       tiles_x, max_label, g, meta);
+  else
+    hipLaunchKernelGGL((k_region_moments<T, false>), grid, dim3(CGC_BLOCK), 0, st, labels, static_cast<const T*>(values), within, 0, H, W,
+                       tiles_x, max_label, g, meta);
+}
+
+}  // namespace
+
+extern "C" int cgc_region_tile_side(void) { return REGION_TILE; }
+extern "C" int cgc_region_table_slots(void) { return REGION_SLOTS; }
+
+extern "C" int64_t cgc_region_ws_bytes(int max_label) {
+  if (max_label < 0 || max_label == 0x7fffffff) return 0;
+  return layout_bytes(region_layout, (int64_t)max_label + 1);
+}
+
+extern "C" int cgc_region_moments(const int* labels, const void* values, int value_bytes, int value_signed, const void* within_or_null,
+                                  int within_bytes, int H, int W, int max_label, void* ws, int* count, int64_t* sum,
+                                  int64_t* sumsq_or_null, int* min, int* max, int* argmin, int* argmax, int* meta, cgc_stream_t stream) {
+  if (bad_region(H, W, max_label, within_or_null, within_bytes)) return CGC_EINVAL;
+  const bool u8 = value_bytes == 1 && value_signed == 0, i8 = value_bytes == 1 && value_signed == 1;
+  const bool i16 = value_bytes == 2 && value_signed == 1, i32 = value_bytes == 4 && value_signed == 1;
+  if (!(u8 || i8 || i16 || i32) || (i32 && sumsq_or_null != nullptr)) return CGC_EINVAL;
+  if (ws == nullptr || count == nullptr || sum == nullptr || min == nullptr || max == nullptr || argmin == nullptr || argmax == nullptr ||
+      meta == nullptr)
+    return CGC_EINVAL;
+  const bool empty = (int64_t)H * W == 0;
+  if (!empty && (labels == nullptr || values == nullptr)) return CGC_EINVAL;
+  hipStream_t st = as_stream(stream);
+  const int rows = max_label + 1;
+  const RegionWs w = region_layout(Carver(ws), rows);
+  const RegionTables g{count, reinterpret_cast<u64*>(sum), reinterpret_cast<u64*>(sumsq_or_null), w.kmin, w.kmax};
+  hipLaunchKernelGGL(k_region_init, dim3(region_blocks(rows)), dim3(CGC_BLOCK), 0, st, rows, g, meta);
+  CGC_RETURN_IF_LAUNCH_FAILED();
+  if (!empty) {
+    if (u8) launch_moments<uint8_t>(labels, values, within_or_null, within_bytes, H, W, max_label, g, meta, st);
+    else if (i8) launch_moments<int8_t>(labels, values, within_or_null, within_bytes, H, W, max_label, g, meta, st);
+    else if (i16) launch_moments<int16_t>(labels, values, within_or_null, within_bytes, H, W, max_label, g, meta, st);
+    else launch_moments<int32_t>(labels, values, within_or_null, within_bytes, H, W, max_label, g, meta, st);
+    CGC_RETURN_IF_LAUNCH_FAILED();
+  }
+  hipLaunchKernelGGL(k_region_finish, dim3(region_blocks(rows)), dim3(CGC_BLOCK), 0, st, rows, count, w.kmin, w.kmax, min, max, argmin, argmax);
+  CGC_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}
+
+extern "C" int cgc_region_histogram(const int* labels, const uint8_t* values, const void* within_or_null, int within_bytes, int H, int W,
+                                    int max_label, int* hist, int* meta, cgc_stream_t stream) {
+  if (bad_region(H, W, max_label, within_or_null, within_bytes) || hist == nullptr || meta == nullptr) return CGC_EINVAL;
+  const bool empty = (int64_t)H * W == 0;
+  if (!empty && (labels == nullptr || values == nullptr)) return CGC_EINVAL;
+  hipStream_t st = as_stream(stream);
+  hipError_t e = hipMemsetAsync(hist, 0, ((size_t)max_label + 1) * 256 * sizeof(int), st);
+  if (e == hipSuccess) e = hipMemsetAsync(meta, 0, sizeof(int), st);
+  if (e != hipSuccess) return (int)e;
+  if (empty) return 0;
+  const int tiles_x = ceil_div(W, REGION_TILE);
+  const dim3 grid((unsigned)((int64_t)tiles_x * ceil_div(H, REGION_TILE)));
+  if (within_or_null != nullptr)
+    hipLaunchKernelGGL(k_region_hist<true>, grid, dim3(CGC_BLOCK), 0, st, labels, values, within_or_null, within_bytes, H, W, tiles_x, max_label,
+                       hist, meta);
+  else
+    hipLaunchKernelGGL(k_region_hist<false>, grid, dim3(CGC_BLOCK), 0, st, labels, values, within_or_null, 0, H, W, tiles_x, max_label, hist,
+                       meta);
+  CGC_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}
+
+extern "C" int cgc_region_quantiles(const int* hist, int64_t rows, const int* q10k, int nq, uint8_t* out, cgc_stream_t stream) {
+  if (rows < 0 || rows >= ((int64_t)1 << 31) || nq < 1 || nq > REGION_MAX_Q || q10k == nullptr) return CGC_EINVAL;
+  RegionQuantiles q{nq, {}};
+  for (int j = 0; j < nq; ++j) {
+    if (q10k[j] < 0 || q10k[j] > 10000) return CGC_EINVAL;
+    q.q[j] = q10k[j];
+  }
+  if (rows == 0) return 0;
+  if (hist == nullptr || out == nullptr || !aligned16(hist)) return CGC_EINVAL;
+  hipLaunchKernelGGL(k_region_quantiles, dim3((unsigned)ceil_div64(rows, CGC_BLOCK / CGC_WAVE)), dim3(CGC_BLOCK), 0, as_stream(stream),
+                     reinterpret_cast<const uint32_t*>(hist), rows, q, out);
+  CGC_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}

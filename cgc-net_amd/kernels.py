@@ -40,7 +40,9 @@ ENTROPY_MAX_RADIUS = 15    # rank_filter 'entropy': n <= 31^2 = 961, the length 
 RANK_ENTROPY_TERMS = 962   # T[0..961]
 RANK_OPS = {'quantile': 0, 'range': 1, 'entropy': 2}              # CGC_RANK_QUANTILE / _RANGE / _ENTROPY
 ADJ_MAX_PIXELS = 2 ** 29   # region_adjacency: a pair's count can reach 4 H W and must fit int32
-WS_JUMP_BATCH = 8         # pointer jumps of watershed_flood per host read: resolves parent chains of up to 2^7 pixels in one read
+REGION_MAX_QUANTILES = 8   # region_quantiles: quantiles read off one histogram per launch
+REGION_VALUE_DTYPES = {torch.uint8: (1, 0), torch.int8: (1, 1), torch.int16: (2, 1), torch.int32: (4, 1)}      # (bytes, signed)
+WS_JUMP_BATCH = 8        # pointer jumps of watershed_flood per host read: resolves parent chains of up to 2^7 pixels in one read
 
 
 @functools.lru_cache(maxsize=4)
@@ -541,6 +543,64 @@ class KernelSpec(object):
         merge of equal keys are library kernels."""
         raise NotImplementedError
 
+    def region_statistics(self, labels, values, max_label, within=None):
+        """Moments and extrema of one plane over the regions of a label image (F17, beside region_adjacency; csrc/region.hip): a
+        segmented reduction that joins the planes of the image stage to the instance mask.  Returns ((count int32, sum int64, sumsq
+        int64 or None, min int32, max int32, argmin int32, argmax int32), meta int32 [1]), every table [max_label + 1], all on the device;
+        no host read.
+
+        1.  labels: [H, W] of any integer dtype, H * W < 2^31; the kernel reads contiguous int32, so other dtypes and strides are
+            copied, and an int64 value that does not fit int32 stays outside [0, max_label] (item 4).  max_label: an integer in 0 .. 2^31 - 2 (ValueError otherwise;
+            the library returns CGC_EINVAL and launches nothing).  Tables are indexed by label value; row 0, the background, is a
+            region like any other.
+        2.  values: uint8, int8, int16 or int32 [H, W], any strides (TypeError for another dtype; bool is the caller's to pass as uint8).
+        3.  within: None or [H, W] of a 1-, 2-, 4- or 8-byte integer type or bool, any strides; only "is zero" is read.  A pixel p is
+            *counted* in row L iff labels[p] == L and within is None or non-zero at p.
+        4.  A pixel whose label lies outside [0, max_label] is counted nowhere.  meta[0] = the number of such pixels, whatever within
+            says there; the caller reads it and refuses.
+        5.  count = the number of counted pixels; sum = their sum (|sum| <= 2^31 * 2^31: it fits int64); sumsq = the sum of their
+            squares for values of at most 16 bits (at most 2^31 * 2^30), None for int32 values.
+        6.  min, max: the extrema of the counted values; argmin, argmax: the raster index y * W + x at which they are attained, of
+            equal values the SMALLEST index -- inside a tile, across tiles and however lanes arrive: value and position travel as one
+            64-bit key, (v ^ 2^31) << 32 | i under an unsigned minimum and (v ^ 2^31) << 32 | ~i under an unsigned maximum.
+        7.  An empty row has count = sum = sumsq = min = max = 0 and argmin = argmax = -1.  H * W = 0 gives such rows only.
+        8.  Exact for every input: a tile with more distinct labels than its table in LDS holds (``region_slots``), down to one
+            label per pixel, sends what finds no slot to the global tables directly; nothing is dropped or counted twice, and no
+            probe sequence is longer than the table.
+        9.  Integer additions and integer minima / maxima only: bit-identical from call to call, whatever the order of arrival.
+        Inside the kernel ("Region statistics"): one workgroup per tile of ``region_tile`` x ``region_tile`` (64) pixels; a
+        thread sums the run of equal labels down its 16 pixels of a column in registers, folds it into a table of ``region_slots``
+        (64) labels in LDS, and the tile's table goes to the global tables with one integer atomic per label and quantity."""
+        raise NotImplementedError
+
+    def region_histogram(self, labels, values, max_label, within=None):
+        """The 256-bin histogram of a uint8 plane over every region of a label image (F17; csrc/region.hip).  Returns (hist int32
+        [max_label + 1, 256], meta int32 [1]) on the device; no host read.
+
+        1.  labels, max_label, within, "counted" and meta: items 1, 3 and 4 of region_statistics.
+        2.  values: uint8 [H, W], any strides (TypeError for another dtype).
+        3.  hist[L][v] = the number of counted pixels of row L with value v; the table is indexed in 64 bits ((max_label + 1) * 256
+            may pass 2^31).  H * W = 0 gives zeros.
+        4.  Exact for every input, as item 8 of region_statistics: pixels whose label finds no slot add to hist directly.
+        5.  Partial counts are 16-bit bins in LDS, two per dword; a tile has 4096 pixels, so a tile of one label and one value does
+            not overflow one.
+        6.  Integer additions only: bit-identical from call to call."""
+        raise NotImplementedError
+
+    def region_quantiles(self, hist, q10k):
+        """Quantiles of the rows of a table of 256-bin histograms (F17; csrc/region.hip).  Returns uint8 [R, len(q10k)] on the device;
+        no host read.
+
+        1.  hist: int32 [R, 256], contiguous, counts >= 0, every row's total n < 2^31 (region_histogram's are).
+        2.  q10k: 1 to REGION_MAX_QUANTILES = 8 integers in 0..10000 (ValueError otherwise; the library returns CGC_EINVAL and
+            launches nothing).
+        3.  With v[0] <= ... <= v[n-1] the row's values sorted, the result is v[k], k = min(n - 1, floor(n * q10k / 10000)) --
+            rank_filter's rule (item 5 there), the product taken in 64 bits: a bin of 2^31 - 1 at q10k = 9999 is not an overflow.
+            q10k = 0 is the row's minimum, 10000 its maximum, 5000 the median (the upper one when n is even).
+        4.  n = 0 gives 0.  R = 0 gives an empty output.
+        5.  One wave per row, four bins per lane, rank_filter's scan in registers; no atomics: bit-identical from call to call."""
+        raise NotImplementedError
+
     def edge_renorm(self, rowptr, col, n, p, val_out):
         """Level-1 ``_re_norm_adj`` (model/network.py:183-191) on a 0/1 CSR that holds its diagonal:
         val[k] = p if col[k]==row else (1/(c+1e-15))*(1-p), c = number of off-diagonal entries of the row."""
@@ -902,7 +962,9 @@ class HipKernels(KernelSpec):
         self.rank_tile_rows = int(self.lib.cgc_rank_tile_rows())              # rows of the tiles of rank_filter (tests)
         assert int(self.lib.cgc_rank_max_radius()) == RANK_MAX_RADIUS and int(self.lib.cgc_rank_entropy_max_radius()) == ENTROPY_MAX_RADIUS
         self.adjacency_tile = int(self.lib.cgc_adjacency_tile_side())          # side of the tiles region_adjacency folds in LDS (tests)
-        self.scan_chunk = int(self.lib.cgc_scan_chunk_pixels())                # ... and of od_moments / angle_histogram
+        self.region_tile = int(self.lib.cgc_region_tile_side())                # side of the tiles of region_statistics / region_histogram (tests)
+        self.region_slots = int(self.lib.cgc_region_table_slots())             # labels such a tile folds in LDS (tests)
+        self.scan_chunk = int(self.lib.cgc_scan_chunk_pixels())               # ... and of od_moments / angle_histogram
         self._dirs_checked = (None, None)                                      # angle_histogram's last direction table and its C array
         self._exp_checked = (None, None)                                       # od_recolor's last exponential table and its C array
         assert int(self.lib.cgc_angle_bins()) == ANGLE_BINS
@@ -1542,6 +1604,77 @@ class HipKernels(KernelSpec):
         self._chk(self.lib.cgc_adjacency_merge(_ptr(keys), _ptr(perm), _ptr(cnts), _ptr(sums), ctypes.c_int64(nrec), _ptr(mws), npairs,
                                                _ptr(pairs), _ptr(count), _ptr(min_sum), self._stream()), 'cgc_adjacency_merge')
         return pairs, count, min_sum
+
+    @staticmethod
+    def _check_max_label(fn, max_label):
+        if isinstance(max_label, bool) or not isinstance(max_label, int) or not 0 <= max_label < 2 ** 31 - 1:
+            raise ValueError('%s: max_label must be an integer in 0..2^31 - 2, got %r' % (fn, max_label))
+
+    @staticmethod
+    def _check_q10k(q10k):
+        """The refusals of region_quantiles that need no tensor: returns the quantiles as a C array."""
+        try:
+            q10k = list(q10k)
+        except TypeError:
+            raise ValueError('region_quantiles: q10k must be a sequence of integers in 0..10000, got %r' % (q10k,))
+        if not 1 <= len(q10k) <= REGION_MAX_QUANTILES:
+            raise ValueError('region_quantiles: q10k takes 1 to %d quantiles, got %d' % (REGION_MAX_QUANTILES, len(q10k)))
+        for q in q10k:
+            if isinstance(q, bool) or not isinstance(q, int) or not 0 <= q <= 10000:
+                raise ValueError('region_quantiles: q10k must hold integers in 0..10000, got %r' % (q,))
+        return (ctypes.c_int * len(q10k))(*q10k)
+
+    def _region_inputs(self, labels, values, within, max_label):
+        """labels as contiguous int32 (any integer dtype is taken; what does not fit int32 stays outside [0, max_label]), values and
+        within contiguous: after the refusals, may copy."""
+        assert not labels.is_floating_point() and labels.dtype != torch.bool
+        if labels.dtype == torch.int64:
+            labels = labels.clamp(-1, max_label + 1)
+        labels, values, within = self._image(labels.to(torch.int32)), self._image(values), self._image(within)
+        assert values.shape == labels.shape and (within is None or within.shape == labels.shape)
+        return labels, values, within
+
+    def region_statistics(self, labels, values, max_label, within=None):
+        HipKernels._check_max_label('region_statistics', max_label)
+        if values.dtype not in REGION_VALUE_DTYPES:
+            raise TypeError('region_statistics: values must be uint8, int8, int16 or int32, got %s' % values.dtype)
+        labels, values, within = self._region_inputs(labels, values, within, max_label)
+        H, W = labels.shape
+        dev = labels.device
+        i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+        R = max_label + 1
+        ints = torch.empty(5, R, **i32)                                         # count, min, max, argmin, argmax
+        wide = torch.empty(1 if values.dtype == torch.int32 else 2, R, **i64)    # sum, sumsq
+        sumsq = wide[1] if wide.shape[0] == 2 else None
+        meta = torch.empty(1, **i32)
+        ws = torch.empty(int(self.lib.cgc_region_ws_bytes(max_label)), dtype=torch.uint8, device=dev)
+        vbytes, vsigned = REGION_VALUE_DTYPES[values.dtype]
+        self._chk(self.lib.cgc_region_moments(_ptr(labels), _ptr(values), vbytes, vsigned, *_within_args(within), H, W, max_label, _ptr(ws),
+                                              _ptr(ints[0]), _ptr(wide[0]), _ptr(sumsq), _ptr(ints[1]), _ptr(ints[2]), _ptr(ints[3]),
+                                              _ptr(ints[4]), _ptr(meta), self._stream()), 'cgc_region_moments')
+        return (ints[0], wide[0], sumsq, ints[1], ints[2], ints[3], ints[4]), meta
+
+    def region_histogram(self, labels, values, max_label, within=None):
+        HipKernels._check_max_label('region_histogram', max_label)
+        if values.dtype != torch.uint8:
+            raise TypeError('region_histogram: values must be uint8, got %s' % values.dtype)
+        labels, values, within = self._region_inputs(labels, values, within, max_label)
+        H, W = labels.shape
+        hist = torch.empty(max_label + 1, 256, dtype=torch.int32, device=labels.device)
+        meta = torch.empty(1, dtype=torch.int32, device=labels.device)
+        self._chk(self.lib.cgc_region_histogram(_ptr(labels), _ptr(values), *_within_args(within), H, W, max_label, _ptr(hist), _ptr(meta),
+                                                self._stream()), 'cgc_region_histogram')
+        return hist, meta
+
+    def region_quantiles(self, hist, q10k):
+        q = HipKernels._check_q10k(q10k)
+        self._dev(hist)
+        assert hist.dtype == torch.int32 and hist.dim() == 2 and hist.shape[1] == 256
+        hist = hist.contiguous()
+        out = torch.empty(hist.shape[0], len(q), dtype=torch.uint8, device=hist.device)
+        self._chk(self.lib.cgc_region_quantiles(_ptr(hist), ctypes.c_int64(hist.shape[0]), q, len(q), _ptr(out), self._stream()),
+                  'cgc_region_quantiles')
+        return out
 
     def edge_renorm(self, rowptr, col, n, p, val_out):
         self._dev(rowptr, col, val_out)

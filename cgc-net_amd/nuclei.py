@@ -76,6 +76,19 @@ kernels.KernelSpec.region_adjacency), and ``voronoi_graph`` builds on it the oth
 ``expand_labels`` are the discrete Voronoi partition of the instance mask, and two nuclei are joined iff their cells share a border.
 Its ``edge_index`` goes into ``graph_item(..., edge_index=...)`` in place of the radius graph on centroids.
 
+``region_statistics``, ``region_histogram`` and ``region_quantiles`` join the planes of the image stage to the instance mask
+(csrc/region.hip; kernels.KernelSpec.region_statistics, region_histogram, region_quantiles): per label value the count, sum, sum of
+squares, minimum and maximum of a plane with the positions of both, its 256-bin histogram, and quantiles read off it -- one pass over
+the pixels, exact integers, bit-identical from call to call, with ``within`` as everywhere else.  "The mean haematoxylin of nucleus
+37" is ``region_mean_std(region_statistics(L, plane))[0][37]``, its median entropy ``region_quantiles(L, entropy_u8, 0.5)[37]``;
+the ``max`` and ``argmax`` of ``region_statistics(L, distance_transform(L != 0))`` are the inscribed radius squared of every nucleus
+and its centre.  ``ring_labels`` is the cytoplasm ring around every nucleus, and ``stain_features`` the node features the reference
+stops short of: mean, spread, median and quantile range of haematoxylin and eosin per nucleus and, if wanted, per ring, row for row
+beside the sixteen gray-level columns (the network's input width is a constructor argument):
+    features, cen, kept = nucleus_features(L, gray, max_label=n)
+    x = torch.cat([features, stain_features(L, tile, kept, ring=6, max_label=n)], 1)
+    graph_item(x, cen, y)
+
 ``nucleus_features(labels, gray)`` returns the reference's ``feature`` / ``coordinate`` arrays of one image (csrc/nuclei.hip; the
 arithmetic item by item: kernels.KernelSpec.nucleus_features), ``graph_item`` turns them into the ``Data`` that
 ``_read_one_raw_graph`` builds, and ``save_reference_files`` writes them where the reference's dataset preparation reads them.
@@ -85,6 +98,7 @@ Differences from the reference, all stated: an image without a surviving nucleus
 (``ValueError``; the reference resizes, which is the identity then).  OpenCV, scikit-image and xtract-features are restated from their
 documented behaviour, not linked: see DESIGN.md, "Nucleus features".
 """
+import collections
 import math
 import numbers
 import operator
@@ -1475,6 +1489,194 @@ def normalize_stains(image, stains=None, order='bgr', target_stains=None, target
     out = recolor(image, a, order)
     if return_info:
         return out, dict(stains=np.array(S, dtype=np.float64), maxima=maxima, bins=bins, n=n, matrix=a)
+    return out
+
+
+RegionStats = collections.namedtuple('RegionStats', ('count', 'sum', 'sumsq', 'min', 'max', 'argmin', 'argmax'))
+REGION_MAX_QUANTILES = kernels.REGION_MAX_QUANTILES
+STAIN_FEATURE_NAMES = tuple('%s%s_%s' % (where, stain, what) for where in ('', 'ring_') for stain in ('hematoxylin', 'eosin')
+                            for what in ('mean', 'std', 'median', 'range'))
+STAIN_FEATURE_QUANTILES = (1000, 5000, 9000)      # as q10k: the range column is the 90 % minus the 10 % quantile
+
+
+def _region_args(fn, labels, values, max_label, within, dtypes):
+    """The refusals the region functions share, then the label range: returns (max_label, values with bool as uint8).  Without
+    ``max_label`` the range is read from the labels (one host sync)."""
+    _check_image(fn, 'labels', labels, _INT_DTYPES)
+    _check_image(fn, 'values', values, dtypes)
+    if tuple(values.shape) != tuple(labels.shape) or values.device != labels.device:
+        raise ValueError('%s: values must have the shape and device of labels (got %s on %s and %s on %s)'
+                         % (fn, tuple(values.shape), values.device, tuple(labels.shape), labels.device))
+    _check_within(fn, within, labels)
+    return _label_top(fn, labels, max_label), values.view(torch.uint8) if values.dtype == torch.bool else values
+
+
+def _label_top(fn, labels, max_label):
+    """``max_label`` checked, or read from the labels (one host sync; negative labels raise there).  The kernel table narrows the
+    labels to int32 itself; an int64 value that does not fit stays outside [0, max_label] and is refused with the rest."""
+    if max_label is not None:
+        if isinstance(max_label, bool) or not isinstance(max_label, numbers.Integral):
+            raise ValueError('%s: max_label must be an integer (got %r)' % (fn, max_label))
+        hi = int(max_label)
+        if hi < 0:
+            raise ValueError('%s: max_label must not be negative (got %d)' % (fn, hi))
+    elif labels.numel() == 0:
+        hi = 0
+    else:
+        lo, hi = torch.stack([labels.min(), labels.max()]).to(torch.int64).tolist()      # host sync: the label range
+        if lo < 0:
+            raise ValueError('%s: negative labels in the label image' % fn)
+    if hi >= INT32_MAX:
+        raise ValueError('%s: label values must lie below 2^31 - 1 (largest: %d)' % (fn, hi))
+    return hi
+
+
+def _refuse_labels(fn, refused, max_label):
+    if refused:
+        raise ValueError('%s: %d pixels carry a label outside [0, %d]' % (fn, refused, max_label))
+
+
+def region_statistics(labels, values, max_label=None, within=None):
+    """Count, sum, sum of squares, extrema and their positions of ``values`` over every region of a label image (csrc/region.hip; the
+    contract item by item: kernels.KernelSpec.region_statistics).  labels: 2-D tensor of any integer dtype on the GPU, any strides;
+    values: bool / uint8 / int8 / int16 / int32, same shape and device (TypeError for another dtype, ValueError for another shape);
+    ``within`` (bool / integer, same shape): only its non-zero pixels are counted.  Returns the named tuple ``RegionStats(count int32,
+    sum int64, sumsq int64, min int32, max int32, argmin int32, argmax int32)``, every table [max_label + 1] and indexed by label
+    value -- row 0 is the background, a region like any other.  ``sumsq`` is None for int32 values (it would not fit int64).
+    ``argmin`` / ``argmax`` are raster indices y * W + x; of equal values the smallest index is reported.  A label without a counted
+    pixel has count 0, sum 0, sumsq 0, min = max = 0 and argmin = argmax = -1.  Exact integers, bit-identical from call to call.
+
+    The ``max`` and ``argmax`` of ``region_statistics(L, distance_transform(L != 0))`` are the inscribed radius squared of every
+    nucleus and its centre: how thick it is, and where.
+
+    Host syncs: the read of the label range unless ``max_label`` is given (negative labels raise ValueError; the tables are indexed by
+    label value, so sparse ids cost memory in proportion to the largest), and the one read of ``meta``: pixels whose label lies
+    outside [0, max_label] raise ValueError."""
+    hi, values = _region_args('region_statistics', labels, values, max_label, within, _INT32_DTYPES)
+    with torch.cuda.device(labels.device):
+        tables, meta = kernels.get().region_statistics(labels, values, hi, within)
+    _refuse_labels('region_statistics', int(meta.item()), hi)      # host sync: the refused pixels
+    return RegionStats(*tables)
+
+
+def _region_histogram(fn, labels, values, max_label, within):
+    hi, values = _region_args(fn, labels, values, max_label, within, (torch.bool, torch.uint8))
+    with torch.cuda.device(labels.device):
+        hist, meta = kernels.get().region_histogram(labels, values, hi, within)
+    return hist, meta, hi
+
+
+def region_histogram(labels, values, max_label=None, within=None):
+    """The 256-bin histogram of a uint8 or bool plane over every region of a label image (kernels.KernelSpec.region_histogram): int32
+    [max_label + 1, 256], hist[L][v] = the pixels of label L with value v -- with ``within`` only those where it is non-zero.
+    Arguments as region_statistics; its row L is ``histogram(values, within=labels == L)``, all rows in one pass.
+
+    Host syncs: as region_statistics."""
+    hist, meta, hi = _region_histogram('region_histogram', labels, values, max_label, within)
+    _refuse_labels('region_histogram', int(meta.item()), hi)       # host sync: the refused pixels
+    return hist
+
+
+def _q10k_list(fn, q):
+    """(q10k of every quantile, was q a single number)."""
+    single = isinstance(q, numbers.Real) or not isinstance(q, (list, tuple))
+    qs = [rank_q10k(v) for v in ((q,) if single else q)]
+    if not 1 <= len(qs) <= REGION_MAX_QUANTILES:
+        raise ValueError('%s: q takes 1 to %d quantiles (got %d)' % (fn, REGION_MAX_QUANTILES, len(qs)))
+    return qs, single
+
+
+def region_quantiles(labels, values, q, max_label=None, within=None):
+    """Quantiles of a uint8 or bool plane over every region: uint8 [max_label + 1, len(q)], or [max_label + 1] for a single number
+    ``q``.  With n the pixels of a region and v[0] <= ... <= v[n-1] their values sorted, the result is v[min(n - 1, floor(n * q10k /
+    10000))], q10k = rank_q10k(q) -- rank_filter's rule: 0 is the minimum, 1 the maximum, 1/2 the median (the upper one when n is
+    even); 0 for a region without a pixel.  ``q``: a real number in [0, 1] or a list / tuple of at most 8 (ValueError otherwise).  One
+    histogram pass and one wave per region (kernels.KernelSpec.region_histogram, region_quantiles); other arguments as
+    region_statistics.
+
+    Host syncs: as region_statistics."""
+    qs, single = _q10k_list('region_quantiles', q)
+    hist, meta, hi = _region_histogram('region_quantiles', labels, values, max_label, within)
+    with torch.cuda.device(hist.device):
+        out = kernels.get().region_quantiles(hist, qs)
+    _refuse_labels('region_quantiles', int(meta.item()), hi)       # host sync: the refused pixels
+    return out[:, 0] if single else out
+
+
+def region_mean_std(stats):
+    """(mean, std) float32 [max_label + 1] of a ``RegionStats`` with ``sumsq``: mean = sum / count and the population standard
+    deviation sqrt(max(0, sumsq / count - mean^2)), computed in float64 on the device from the integer tables and rounded once; rows
+    with count 0 give 0.  A constant region gives std exactly 0.  ValueError for statistics of int32 values, which carry no sumsq.
+
+    Host syncs: none."""
+    if not isinstance(stats, RegionStats):
+        raise TypeError('region_mean_std takes the RegionStats of region_statistics')
+    if stats.sumsq is None:
+        raise ValueError('region_mean_std needs sumsq: statistics of int32 values carry none')
+    n = stats.count.to(torch.float64)
+    some = n > 0
+    n = torch.where(some, n, 1.0)
+    mean = stats.sum.to(torch.float64) / n
+    var = (stats.sumsq.to(torch.float64) / n - mean * mean).clamp_(min=0.0)
+    zero = torch.zeros_like(mean)
+    return torch.where(some, mean, zero).to(torch.float32), torch.where(some, var.sqrt(), zero).to(torch.float32)
+
+
+def ring_labels(labels, distance, within=None):
+    """The cytoplasm ring of every nucleus: ``expand_labels(labels, distance, within=within)`` with the pixels of the nuclei
+    themselves set to 0 -- each ring pixel carries the label of its nearest nucleus, for statistics around the nucleus
+    (``region_statistics(ring_labels(L, 6), plane)``).  Arguments as expand_labels' Euclidean growth.
+
+    Host syncs: none."""
+    grown = expand_labels(labels, distance, within=within)
+    return torch.where(labels != 0, torch.zeros_like(grown), grown)
+
+
+def stain_features(labels, tile, kept_labels, stains=None, order='bgr', ring=0, max_label=None):
+    """Stain features per nucleus, to put beside ``nucleus_features``' sixteen gray-level columns: float32 [len(kept_labels), 8], or
+    16 with ``ring`` > 0; ``STAIN_FEATURE_NAMES`` names the columns.  labels: 2-D integer instance mask on the GPU; tile: the uint8
+    [H, W, 3] H&E tile it was made from (``stains``, ``order``: as separate_stains); kept_labels: 1-D int32 or int64 tensor on the
+    same device, e.g. the third output of nucleus_features -- row k describes label kept_labels[k].  For the haematoxylin and the
+    eosin plane of ``separate_stains`` (levels of 1 / 64 of a natural-log unit) the columns are the mean, the population standard
+    deviation (region_mean_std), the median and the 10 % to 90 % quantile range (region_quantiles) over the nucleus' pixels.  With
+    ``ring`` > 0 the same eight columns follow for ``ring_labels(labels, ring)``, the cytoplasm around each nucleus; a nucleus
+    without a ring pixel has zeros there.
+
+    Host syncs: the label range unless ``max_label`` is given, and one read that brings the refused pixels and the check of
+    kept_labels: labels or kept_labels outside [0, max_label] raise ValueError."""
+    fn = 'stain_features'
+    _check_image(fn, 'labels', labels, _INT_DTYPES)
+    _check_color(fn, tile)
+    if tuple(tile.shape[:2]) != tuple(labels.shape) or tile.device != labels.device:
+        raise ValueError('%s: tile must have the height, width and device of labels (got %s on %s and %s on %s)'
+                         % (fn, tuple(tile.shape[:2]), tile.device, tuple(labels.shape), labels.device))
+    if not torch.is_tensor(kept_labels) or kept_labels.dtype not in (torch.int32, torch.int64):
+        raise TypeError('%s: kept_labels must be an int32 or int64 tensor' % fn)
+    if kept_labels.dim() != 1 or kept_labels.device != labels.device:
+        raise ValueError('%s: kept_labels must be 1-D and on the device of labels' % fn)
+    if isinstance(ring, bool) or not isinstance(ring, numbers.Real) or not ring >= 0:
+        raise ValueError('%s: ring must be a distance >= 0 (got %r)' % (fn, ring))
+    if order not in STAIN_ORDERS:
+        raise ValueError("order must be 'bgr' or 'rgb', got %r" % (order,))
+    hi = _label_top(fn, labels, max_label)
+    planes = separate_stains(tile, stains, order, planes=(0, 1))
+    with torch.cuda.device(labels.device):
+        k = kernels.get()
+        columns, meta = [], None
+        for regions in (labels,) + ((ring_labels(labels, ring),) if ring > 0 else ()):
+            for plane in planes:
+                tables, m = k.region_statistics(regions, plane, hi)
+                meta = m if meta is None else meta                  # the rings carry labels of the mask (or 0): one check covers both
+                mean, std = region_mean_std(RegionStats(*tables))
+                q = k.region_quantiles(k.region_histogram(regions, plane, hi)[0], STAIN_FEATURE_QUANTILES).to(torch.float32)
+                columns += [mean, std, q[:, 1], q[:, 2] - q[:, 0]]
+    table = torch.stack(columns, dim=1)
+    kept = kept_labels.to(torch.int64)
+    out = table[kept.clamp(0, hi)]
+    refused, bad_kept = torch.stack([meta[0].to(torch.int64), ((kept < 0) | (kept > hi)).sum()]).tolist()      # host sync
+    _refuse_labels(fn, refused, hi)
+    if bad_kept:
+        raise ValueError('%s: %d of kept_labels lie outside [0, %d]' % (fn, bad_kept, hi))
     return out
 
 

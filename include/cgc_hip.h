@@ -78,8 +78,11 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *  21: DenseJK: cgc_jk_lstm_fwd, cgc_jk_lstm_bwd, cgc_jk_lstm_bwd_params and cgc_jk_lstm_bwd_flat refuse an npad that is not a
  *      multiple of 64 (CGC_EINVAL, nothing launched); they took any npad >= n before
  *  22: rank filters (quantile, quantile range, local entropy over a square, disk or diamond): cgc_rank_max_radius,
- *      cgc_rank_entropy_max_radius, cgc_rank_tile_rows, cgc_rank_tile_cols, cgc_rank_entropy_term, cgc_rank_filter, CGC_RANK_* */
-#define CGC_ABI_VERSION 22
+ *      cgc_rank_entropy_max_radius, cgc_rank_tile_rows, cgc_rank_tile_cols, cgc_rank_entropy_term, cgc_rank_filter, CGC_RANK_*
+ *  23: region statistics (per label value: count, sum, sum of squares, extrema with positions; 256-bin histograms; quantiles off
+ *      them): cgc_region_tile_side, cgc_region_table_slots, cgc_region_ws_bytes, cgc_region_moments, cgc_region_histogram,
+ *      cgc_region_quantiles */
+#define CGC_ABI_VERSION 23
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -467,6 +470,37 @@ int cgc_rank_tile_cols(int radius);
 int cgc_rank_entropy_term(int c);
 int cgc_rank_filter(const uint8_t* img, const void* within_or_null, int within_bytes, int H, int W, int kind, int radius, int op,
                     int q_lo, int q_hi, void* out, cgc_stream_t stream);
+
+/* ---- F17 (behind F5/F6 and every plane of F10..F16, beside F13): statistics of a second plane over the regions of a label image
+ * (csrc/region.hip).  The contract item by item: cgc-net_amd/kernels.py KernelSpec.region_statistics / region_histogram /
+ * region_quantiles.  labels int32 [H, W], contiguous, H * W < 2^31; tables are indexed by label value 0 .. max_label (0 <= max_label <
+ * 2^31 - 1), row 0 -- the background -- being a region like any other.  within_or_null [H, W] of within_bytes (1, 2, 4 or 8) bytes per
+ * element, of which only "is zero" is read.  A pixel p is counted in row L iff labels[p] == L and within is null or non-zero at p.  A
+ * pixel whose label lies outside [0, max_label] is counted nowhere; *meta (int32 on the device) = the number of such pixels, whatever
+ * within says there.
+ *   cgc_region_moments: values [H, W] of value_bytes / value_signed = 1 / 0 (uint8), 1 / 1 (int8), 2 / 1 (int16) or 4 / 1 (int32).
+ *     ws = cgc_region_ws_bytes(max_label) bytes.  Out, each [max_label + 1]: count int32; sum int64; sumsq int64 (may be null; must be
+ *     null for 4-byte values); min, max int32; argmin, argmax int32 = the raster index y W + x of the extremum, of equal values the
+ *     smallest index.  An empty row has count = sum = sumsq = min = max = 0 and argmin = argmax = -1.
+ *   cgc_region_histogram: values uint8.  hist int32 [max_label + 1, 256], indexed in 64 bits: hist[L][v] = the counted pixels of row L
+ *     with value v.
+ *   cgc_region_quantiles: hist int32 [rows, 256], 16-byte aligned, every row's total n < 2^31; q10k: nq (1..8) integers in 0..10000 in
+ *     HOST memory.  out uint8 [rows, nq] = v[min(n - 1, floor(n * q10k / 10000))] of the row's values sorted (F16's rule, the product
+ *     in 64 bits), 0 where n = 0.  One wave per row.
+ *   cgc_region_tile_side (64), cgc_region_table_slots (64): the tile one workgroup owns and the labels it folds in LDS, for tests; a
+ *     tile with more labels than that sends the rest to the global tables directly -- exact for every input.
+ * Integer adds and integer minima / maxima of (value, index) keys only: outputs are bit-identical from call to call.  No loop waits
+ * for another thread.  Bad dims, max_label, value_bytes / value_signed, within_bytes (with a within), nq or q10k out of range, sumsq
+ * with 4-byte values, or a null pointer where one is needed: CGC_EINVAL, nothing launched.  H * W = 0: the tables of empty rows. */
+int cgc_region_tile_side(void);
+int cgc_region_table_slots(void);
+int64_t cgc_region_ws_bytes(int max_label);
+int cgc_region_moments(const int* labels, const void* values, int value_bytes, int value_signed, const void* within_or_null,
+                       int within_bytes, int H, int W, int max_label, void* ws, int* count, int64_t* sum, int64_t* sumsq_or_null, int* min,
+                       int* max, int* argmin, int* argmax, int* meta, cgc_stream_t stream);
+int cgc_region_histogram(const int* labels, const uint8_t* values, const void* within_or_null, int within_bytes, int H, int W,
+                         int max_label, int* hist, int* meta, cgc_stream_t stream);
+int cgc_region_quantiles(const int* hist, int64_t rows, const int* q10k, int nq, uint8_t* out, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
