@@ -14,6 +14,8 @@
 //   k_region_finish    keys -> min, max, argmin, argmax; the values of an empty row
 // HISTOGRAM: hipMemsetAsync, then k_region_hist -- the same tile, table and walk, with 256 16-bit bins per slot (two per dword; a bin
 // holds at most the 4096 pixels of a tile) and one LDS atomic per counted pixel; a claimed slot is flushed as 256 consecutive counters.
+// COOCCURRENCE (KernelSpec.region_cooccurrence; DESIGN.md, "Region co-occurrence"): hipMemsetAsync, then one k_region_cooc per offset
+// -- k_region_hist with a pair of pixels (anchor, partner) where the histogram has one, and a bin per pair of levels.
 // OVERFLOW.  region_slot() probes at most REGION_PROBES <= REGION_SLOTS slots and never waits: a label that finds neither itself nor
 // an empty slot there is sent to the global tables directly (a run at a time in MOMENTS, a pixel at a time in HISTOGRAM).  Both routes
 // end in the same integer atomics on the same global words, so which pixels take which route -- it depends on the order in which lanes
@@ -41,6 +43,12 @@ constexpr int REGION_INIT_BLOCKS = 4096;
 constexpr unsigned long long REGION_NO_MIN = ~0ull, REGION_NO_MAX = 0ull;
 static_assert(REGION_PROBES <= REGION_SLOTS, "a probe sequence is bounded by the slot count");
 static_assert(REGION_TILE * REGION_TILE < (1 << 16), "a 16-bit bin holds a whole tile of one label and one value");
+constexpr int COOC_MAX_OFFSET = 16;                              // largest |dy|, |dx| of COOCCURRENCE (exported)
+constexpr int COOC_MAX_OFFSETS = 8;                              // offsets per call (exported)
+constexpr int COOC_MAX_LEVELS = 16;
+constexpr int COOC_MAX_PIXELS = 1 << 30;                         // a symmetric diagonal bin holds at most 2 H W, which must fit int32
+static_assert(2 * REGION_TILE * REGION_TILE < (1 << 16), "a 16-bit bin holds a whole tile of symmetric pairs of one label and one level");
+static_assert(COOC_MAX_LEVELS * COOC_MAX_LEVELS <= 256, "a co-occurrence table fits the 256 bins of a slot");
 static_assert(REGION_TILE == CGC_WAVE && REGION_BAND * (CGC_BLOCK / CGC_WAVE) == REGION_TILE, "a wave is one row of a tile, four bands");
 
 typedef unsigned long long u64;
@@ -288,6 +296,89 @@ static inline int region_blocks(int64_t rows) {
   return (int)(b < REGION_INIT_BLOCKS ? b : REGION_INIT_BLOCKS);
 }
 
+struct CoocLut {
+  uint32_t w[64];                        // the level of value v: byte v & 3 of dword v >> 2
+};
+
+struct RegionCooc {
+  int key[REGION_SLOTS];
+  uint32_t bins[REGION_SLOTS * 128];      // slot s, bin a * levels + b: as RegionHist's value
+  uint32_t level[64];                    // the lut, for lookups by lane
+};
+
+// One offset (dy, dx) of COOCCURRENCE: k_region_hist with a pair of pixels where the histogram has one.  The anchor p is the thread's
+// pixel, the partner q = p + (dy, dx) is loaded from global memory through an address clamped into the image; whether q lies inside the
+// image is decided from its coordinates, never from what the clamped address returned.  The tile that holds p counts the pair, wherever
+// q lies.  `out` is the table of this offset, tables + k * levels^2; a row is `row_stride` = noff * levels^2 counters further on.
+template <bool WITHIN>
+__global__ void __launch_bounds__(CGC_BLOCK) k_region_cooc(const int* __restrict__ labels, const uint8_t* __restrict__ values,
+                                                           const void* __restrict__ within, int wbytes, int H, int W, int tiles_x,
+                                                           int max_label, CoocLut lut, int levels, int dy, int dx, int symmetric,
+                                                           int count_refused, int* out, int64_t row_stride, int* meta) {
+  __shared__ RegionCooc t;
+  for (int i = threadIdx.x; i < REGION_SLOTS; i += CGC_BLOCK) t.key[i] = REGION_EMPTY;
+  for (int i = threadIdx.x; i < REGION_SLOTS * 128; i += CGC_BLOCK) t.bins[i] = 0;
+  if (threadIdx.x < 64) t.level[threadIdx.x] = lut.w[threadIdx.x];
+  RegionColumn<uint8_t, WITHIN> c;
+  c.load(labels, values, within, wbytes, H, W, tiles_x, max_label);
+  // the partners: same column for all 16, rows y0 + dy ..
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int qx = tx * REGION_TILE + (threadIdx.x & (REGION_TILE - 1)) + dx;
+  const int qy0 = ty * REGION_TILE + (threadIdx.x / REGION_TILE) * REGION_BAND + dy;
+  const int qxc = qx < 0 ? 0 : (qx < W ? qx : W - 1);
+  int plab[REGION_BAND], pval[REGION_BAND];
+  unsigned pon = 0;
+#pragma unroll
+  for (int k = 0; k < REGION_BAND; ++k) {
+    const int qy = qy0 + k;
+    const int qyc = qy < 0 ? 0 : (qy < H ? qy : H - 1);
+    const int64_t i = (int64_t)qyc * W + qxc;
+    plab[k] = labels[i];
+    pval[k] = (int)values[i];
+    if (WITHIN) pon |= (unsigned)image_nonzero(within, wbytes, i) << k;
+  }
+  unsigned pair = 0;                                              // bit k: anchor k and its partner are a counted pair
+#pragma unroll
+  for (int k = 0; k < REGION_BAND; ++k) {
+    const int qy = qy0 + k;
+    const bool inside = qx >= 0 && qx < W && qy >= 0 && qy < H;
+    pair |= (unsigned)(inside && plab[k] == c.lab[k] && (!WITHIN || (pon >> k & 1u))) << k;
+  }
+  pair &= c.counted;
+  __syncthreads();
+  const uint8_t* level = reinterpret_cast<const uint8_t*>(t.level);
+  int cl = REGION_EMPTY, cs = -1;                                 // the label of the pair above and its slot
+#pragma unroll
+  for (int k = 0; k < REGION_BAND; ++k) {
+    if (!(pair >> k & 1u)) continue;
+    const int L = c.lab[k];
+    const int a = level[c.val[k]], b = level[pval[k]];
+    const int ab = a * levels + b, ba = b * levels + a;            // < levels^2 <= 256: the host checked every entry of the lut
+    if (L != cl) {
+      cl = L;
+      cs = region_slot(t.key, L);
+    }
+    if (cs >= 0) {
+      atomicAdd(&t.bins[cs * 128 + (ab >> 1)], 1u << ((ab & 1) * 16));
+      if (symmetric) atomicAdd(&t.bins[cs * 128 + (ba >> 1)], 1u << ((ba & 1) * 16));
+    } else {
+      int* row = out + (int64_t)L * row_stride;
+      atomicAdd(&row[ab], 1);
+      if (symmetric) atomicAdd(&row[ba], 1);
+    }
+  }
+  if (count_refused && c.refused != 0) atomicAdd(meta, (int)__builtin_popcount(c.refused));
+  __syncthreads();
+  const int v = threadIdx.x;                                      // CGC_BLOCK == 256: a thread flushes one bin of every claimed slot
+  if (v >= levels * levels) return;                               // after the last barrier
+  for (int s = 0; s < REGION_SLOTS; ++s) {
+    const int L = t.key[s];                                       // uniform
+    if (L == REGION_EMPTY) continue;
+    const int n = (int)(t.bins[s * 128 + (v >> 1)] >> ((v & 1) * 16) & 0xffffu);
+    if (n != 0) atomicAdd(&out[(int64_t)L * row_stride + v], n);
+  }
+}
+
 template <typename T>
 void launch_moments(const int* labels, const void* values, const void* within, int wbytes, int H, int W, int max_label,
                     const RegionTables& g, int* meta, hipStream_t st) {
@@ -360,6 +451,49 @@ extern "C" int cgc_region_histogram(const int* labels, const uint8_t* values, co
     hipLaunchKernelGGL(k_region_hist<false>, grid, dim3(CGC_BLOCK), 0, st, labels, values, within_or_null, 0, H, W, tiles_x, max_label, hist,
                        meta);
   CGC_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}
+
+extern "C" int cgc_region_cooc_max_offset(void) { return COOC_MAX_OFFSET; }
+extern "C" int cgc_region_cooc_max_offsets(void) { return COOC_MAX_OFFSETS; }
+
+extern "C" int cgc_region_cooccurrence(const int* labels, const uint8_t* values, const void* within_or_null, int within_bytes, int H, int W,
+                                       int max_label, const uint8_t* lut256_host, int levels, const int* offsets_host, int noff,
+                                       int symmetric, int* tables, int* meta, cgc_stream_t stream) {
+  if (bad_region(H, W, max_label, within_or_null, within_bytes) || (int64_t)H * W >= COOC_MAX_PIXELS) return CGC_EINVAL;
+  if (tables == nullptr || meta == nullptr || lut256_host == nullptr || offsets_host == nullptr) return CGC_EINVAL;
+  if (levels < 2 || levels > COOC_MAX_LEVELS || noff < 1 || noff > COOC_MAX_OFFSETS) return CGC_EINVAL;
+  CoocLut lut{};
+  for (int v = 0; v < 256; ++v) {
+    if (lut256_host[v] >= levels) return CGC_EINVAL;
+    lut.w[v >> 2] |= (uint32_t)lut256_host[v] << ((v & 3) * 8);
+  }
+  for (int k = 0; k < noff; ++k) {
+    const int dy = offsets_host[2 * k], dx = offsets_host[2 * k + 1];
+    if (dy < -COOC_MAX_OFFSET || dy > COOC_MAX_OFFSET || dx < -COOC_MAX_OFFSET || dx > COOC_MAX_OFFSET || (dy == 0 && dx == 0))
+      return CGC_EINVAL;
+  }
+  const bool empty = (int64_t)H * W == 0;
+  if (!empty && (labels == nullptr || values == nullptr)) return CGC_EINVAL;
+  hipStream_t st = as_stream(stream);
+  const int bins = levels * levels;
+  const int64_t row_stride = (int64_t)noff * bins;
+  hipError_t e = hipMemsetAsync(tables, 0, ((size_t)max_label + 1) * (size_t)row_stride * sizeof(int), st);
+  if (e == hipSuccess) e = hipMemsetAsync(meta, 0, sizeof(int), st);
+  if (e != hipSuccess) return (int)e;
+  if (empty) return 0;
+  const int tiles_x = ceil_div(W, REGION_TILE);
+  const dim3 grid((unsigned)((int64_t)tiles_x * ceil_div(H, REGION_TILE)));
+  for (int k = 0; k < noff; ++k) {                                // one launch per offset; the first counts the refused pixels
+    const int dy = offsets_host[2 * k], dx = offsets_host[2 * k + 1];
+    if (within_or_null != nullptr)
+      hipLaunchKernelGGL(k_region_cooc<true>, grid, dim3(CGC_BLOCK), 0, st, labels, values, within_or_null, within_bytes, H, W, tiles_x,
+                         max_label, lut, levels, dy, dx, (int)(symmetric != 0), (int)(k == 0), tables + (int64_t)k * bins, row_stride, meta);
+    else
+      hipLaunchKernelGGL(k_region_cooc<false>, grid, dim3(CGC_BLOCK), 0, st, labels, values, within_or_null, 0, H, W, tiles_x, max_label,
+                         lut, levels, dy, dx, (int)(symmetric != 0), (int)(k == 0), tables + (int64_t)k * bins, row_stride, meta);
+    CGC_RETURN_IF_LAUNCH_FAILED();
+  }
   return 0;
 }
 

@@ -41,6 +41,10 @@ RANK_ENTROPY_TERMS = 962   # T[0..961]
 RANK_OPS = {'quantile': 0, 'range': 1, 'entropy': 2}              # CGC_RANK_QUANTILE / _RANGE / _ENTROPY
 ADJ_MAX_PIXELS = 2 ** 29   # region_adjacency: a pair's count can reach 4 H W and must fit int32
 REGION_MAX_QUANTILES = 8   # region_quantiles: quantiles read off one histogram per launch
+COOC_MAX_OFFSET = 16       # region_cooccurrence: largest |dy|, |dx| (cgc_region_cooc_max_offset)
+COOC_MAX_OFFSETS = 8       # ... offsets per call (cgc_region_cooc_max_offsets)
+COOC_MAX_LEVELS = 16       # ... levels: levels^2 bins are the 256 16-bit bins of a slot in LDS
+COOC_MAX_PIXELS = 2 ** 30  # ... a symmetric diagonal bin holds at most 2 H W and must fit int32
 REGION_VALUE_DTYPES = {torch.uint8: (1, 0), torch.int8: (1, 1), torch.int16: (2, 1), torch.int32: (4, 1)}      # (bytes, signed)
 WS_JUMP_BATCH = 8        # pointer jumps of watershed_flood per host read: resolves parent chains of up to 2^7 pixels in one read
 
@@ -587,6 +591,35 @@ class KernelSpec(object):
         6.  Integer additions only: bit-identical from call to call."""
         raise NotImplementedError
 
+    def region_cooccurrence(self, labels, values, max_label, lut, levels, offsets, symmetric, within=None):
+        """The grey-level co-occurrence tables (GLCM) of a uint8 plane over every region of a label image, at several offsets (F18,
+        beside region_histogram; csrc/region.hip).  Returns (tables int32 [max_label + 1, len(offsets), levels * levels], meta int32
+        [1]) on the device; no host read.
+
+        1.  labels, max_label, within, the refused pixels and meta: items 1, 3 and 4 of region_statistics.  meta[0] counts every pixel
+            whose label lies outside [0, max_label] once per call, not once per offset.  H * W < 2^30, so that a symmetric diagonal
+            bin of at most 2 H W fits int32 (the library returns CGC_EINVAL for a larger image and launches nothing).
+        2.  values: uint8 [H, W], any strides (TypeError for another dtype).
+        3.  levels: an integer in 2..16.  lut: 256 integers in 0 .. levels - 1 on the host; the level of a pixel is lut[v].  An entry
+            >= levels is a ValueError (CGC_EINVAL, nothing launched).  The table travels by value in the kernel argument: nothing
+            of the caller's is read after the call returns.
+        4.  offsets: 1 to 8 pairs (dy, dx) of integers, |dy| and |dx| <= 16, (0, 0) not allowed (ValueError; CGC_EINVAL, nothing
+            launched).
+        5.  For offset k, anchor p = (y, x) and partner q = (y + dy, x + dx), the pair is counted in row R iff p and q lie inside the
+            image, labels[p] == labels[q] == R, 0 <= R <= max_label, and within is None or non-zero at both p and q.  Row 0, the
+            background, is a region like any other; a caller who does not want it passes within = labels != 0.
+        6.  A counted pair with levels (a, b) adds 1 to tables[R][k][a * levels + b]; with symmetric it also adds 1 to
+            tables[R][k][b * levels + a], so a pair with a == b adds 2 to the diagonal (skimage's symmetric=True).  The table is
+            indexed in 64 bits.  H * W = 0 gives zeros.
+        7.  Exact for every input, as item 8 of region_statistics: the pairs of a label that finds no slot in the tile's table in
+            LDS add to tables directly.  The tile that holds the anchor counts the pair, wherever the partner lies; a partner is
+            read through an address clamped into the image, and whether it lies inside is decided from its coordinates.
+        8.  Partial counts are 16-bit bins in LDS, two per dword; a tile has 4096 anchors, so a tile of one label and one level,
+            symmetric, puts 8192 into one bin and does not overflow it.
+        9.  Integer additions only: bit-identical from call to call.
+        Inside the kernel ("Region co-occurrence"): one launch per offset over region_histogram's tile, table and walk."""
+        raise NotImplementedError
+
     def region_quantiles(self, hist, q10k):
         """Quantiles of the rows of a table of 256-bin histograms (F17; csrc/region.hip).  Returns uint8 [R, len(q10k)] on the device;
         no host read.
@@ -964,6 +997,8 @@ class HipKernels(KernelSpec):
         self.adjacency_tile = int(self.lib.cgc_adjacency_tile_side())          # side of the tiles region_adjacency folds in LDS (tests)
         self.region_tile = int(self.lib.cgc_region_tile_side())                # side of the tiles of region_statistics / region_histogram (tests)
         self.region_slots = int(self.lib.cgc_region_table_slots())             # labels such a tile folds in LDS (tests)
+        self.region_cooc_max_offset = int(self.lib.cgc_region_cooc_max_offset())      # largest |dy|, |dx| of region_cooccurrence
+        self.region_cooc_max_offsets = int(self.lib.cgc_region_cooc_max_offsets())    # offsets per call
         self.scan_chunk = int(self.lib.cgc_scan_chunk_pixels())               # ... and of od_moments / angle_histogram
         self._dirs_checked = (None, None)                                      # angle_histogram's last direction table and its C array
         self._exp_checked = (None, None)                                       # od_recolor's last exponential table and its C array
@@ -1665,6 +1700,48 @@ class HipKernels(KernelSpec):
         self._chk(self.lib.cgc_region_histogram(_ptr(labels), _ptr(values), *_within_args(within), H, W, max_label, _ptr(hist), _ptr(meta),
                                                 self._stream()), 'cgc_region_histogram')
         return hist, meta
+
+    @staticmethod
+    def _check_cooc(lut, levels, offsets):
+        """The refusals of region_cooccurrence that need no tensor: returns (the lut as 256 C bytes, the offsets as a C array)."""
+        fn = 'region_cooccurrence'
+        if isinstance(levels, bool) or not isinstance(levels, int) or not 2 <= levels <= COOC_MAX_LEVELS:
+            raise ValueError('%s: levels must be an integer in 2..%d, got %r' % (fn, COOC_MAX_LEVELS, levels))
+        try:
+            lut = [operator.index(v) for v in lut]
+        except TypeError:
+            raise ValueError('%s: lut must be a sequence of 256 integers below levels' % fn)
+        if len(lut) != 256:
+            raise ValueError('%s: lut must hold 256 entries, got %d' % (fn, len(lut)))
+        if any(not 0 <= v < levels for v in lut):
+            raise ValueError('%s: every entry of lut must lie in 0..%d' % (fn, levels - 1))
+        try:
+            offsets = [(operator.index(dy), operator.index(dx)) for dy, dx in offsets]
+        except (TypeError, ValueError):
+            raise ValueError('%s: offsets must be a sequence of pairs (dy, dx) of integers, got %r' % (fn, offsets))
+        if not 1 <= len(offsets) <= COOC_MAX_OFFSETS:
+            raise ValueError('%s: offsets takes 1 to %d offsets, got %d' % (fn, COOC_MAX_OFFSETS, len(offsets)))
+        for dy, dx in offsets:
+            if (dy, dx) == (0, 0) or abs(dy) > COOC_MAX_OFFSET or abs(dx) > COOC_MAX_OFFSET:
+                raise ValueError('%s: an offset must not be (0, 0) and |dy|, |dx| must not pass %d, got %r' % (fn, COOC_MAX_OFFSET, (dy, dx)))
+        return (ctypes.c_uint8 * 256)(*lut), (ctypes.c_int * (2 * len(offsets)))(*[v for o in offsets for v in o])
+
+    def region_cooccurrence(self, labels, values, max_label, lut, levels, offsets, symmetric, within=None):
+        HipKernels._check_max_label('region_cooccurrence', max_label)
+        lut, offs = HipKernels._check_cooc(lut, levels, offsets)
+        if values.dtype != torch.uint8:
+            raise TypeError('region_cooccurrence: values must be uint8, got %s' % values.dtype)
+        labels, values, within = self._region_inputs(labels, values, within, max_label)
+        H, W = labels.shape
+        if H * W >= COOC_MAX_PIXELS:
+            raise ValueError('region_cooccurrence takes images of fewer than 2^30 pixels (got %d x %d): a count must fit int32' % (H, W))
+        noff = len(offs) // 2
+        tables = torch.empty(max_label + 1, noff, levels * levels, dtype=torch.int32, device=labels.device)
+        meta = torch.empty(1, dtype=torch.int32, device=labels.device)
+        self._chk(self.lib.cgc_region_cooccurrence(_ptr(labels), _ptr(values), *_within_args(within), H, W, max_label, lut, levels, offs,
+                                                   noff, 1 if symmetric else 0, _ptr(tables), _ptr(meta), self._stream()),
+                  'cgc_region_cooccurrence')
+        return tables, meta
 
     def region_quantiles(self, hist, q10k):
         q = HipKernels._check_q10k(q10k)

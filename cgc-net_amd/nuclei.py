@@ -89,6 +89,15 @@ beside the sixteen gray-level columns (the network's input width is a constructo
     x = torch.cat([features, stain_features(L, tile, kept, ring=6, max_label=n)], 1)
     graph_item(x, cen, y)
 
+``region_cooccurrence`` is the second-order statistic beside them (csrc/region.hip; kernels.KernelSpec.region_cooccurrence): per
+label value and offset the grey-level co-occurrence table of any uint8 plane, over the pixel pairs that lie in the same region, at up
+to 8 offsets of up to 16 pixels and 2 to 16 levels (``level_lut``) -- exact integers again, with ``within`` at both pixels of a pair.
+``cooccurrence_properties`` reads the Haralick properties off the tables (contrast, dissimilarity, homogeneity, ASM, energy,
+correlation, entropy), and ``texture_features`` is the chromatin texture of every nucleus: their mean and range over the four
+directions ``COOC_DIRECTIONS`` on the haematoxylin plane, twelve columns beside the others.  The four GLCM columns among
+``nucleus_features``' sixteen keep the reference's form (gray plane, one offset, 256 levels, a crop that includes the neighbours):
+    x = torch.cat([features, stain_features(L, tile, kept, max_label=n), texture_features(L, tile, kept, hi=159, max_label=n)], 1)
+
 ``nucleus_features(labels, gray)`` returns the reference's ``feature`` / ``coordinate`` arrays of one image (csrc/nuclei.hip; the
 arithmetic item by item: kernels.KernelSpec.nucleus_features), ``graph_item`` turns them into the ``Data`` that
 ``_read_one_raw_graph`` builds, and ``save_reference_files`` writes them where the reference's dataset preparation reads them.
@@ -1677,6 +1686,217 @@ def stain_features(labels, tile, kept_labels, stains=None, order='bgr', ring=0, 
     _refuse_labels(fn, refused, hi)
     if bad_kept:
         raise ValueError('%s: %d of kept_labels lie outside [0, %d]' % (fn, bad_kept, hi))
+    return out
+
+
+COOC_MAX_OFFSET = kernels.COOC_MAX_OFFSET
+COOC_MAX_OFFSETS = kernels.COOC_MAX_OFFSETS
+COOC_MAX_LEVELS = kernels.COOC_MAX_LEVELS
+COOC_DIRECTIONS = ((0, 1), (1, 1), (1, 0), (1, -1))      # Haralick et al. 1973: 0, 45, 90 and 135 degrees at distance 1
+COOC_PROPERTIES = ('contrast', 'dissimilarity', 'homogeneity', 'ASM', 'energy', 'correlation', 'entropy')
+TEXTURE_PROPERTIES = ('contrast', 'dissimilarity', 'homogeneity', 'energy', 'correlation', 'entropy')
+TEXTURE_FEATURE_NAMES = tuple('hematoxylin_%s_%s' % (prop, what) for prop in TEXTURE_PROPERTIES for what in ('mean', 'range'))
+
+
+def _check_levels(fn, levels):
+    if isinstance(levels, bool) or not isinstance(levels, numbers.Integral) or not 2 <= levels <= COOC_MAX_LEVELS:
+        raise ValueError('%s: levels must be an integer in 2..%d (got %r)' % (fn, COOC_MAX_LEVELS, levels))
+    return int(levels)
+
+
+def level_lut(levels, lo=0, hi=255):
+    """The table that quantises a uint8 plane to ``levels`` (2..16) grey levels for region_cooccurrence: a tuple of 256 ints.  v <= lo
+    maps to 0, v >= hi to levels - 1, and between them the level is floor((v - lo) * levels / (hi - lo + 1)), in exact integers; 0 <=
+    lo < hi <= 255 (ValueError otherwise).  The default (lo = 0, hi = 255) is v * levels >> 8 when ``levels`` is a power of two.
+
+    Host syncs: none (no tensor is touched)."""
+    levels = _check_levels('level_lut', levels)
+    for name, v in (('lo', lo), ('hi', hi)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError('level_lut: %s must be an integer (got %r)' % (name, v))
+    lo, hi = int(lo), int(hi)
+    if not 0 <= lo < hi <= 255:
+        raise ValueError('level_lut: 0 <= lo < hi <= 255 is required (got lo = %d, hi = %d)' % (lo, hi))
+    return tuple(0 if v <= lo else levels - 1 if v >= hi else (v - lo) * levels // (hi - lo + 1) for v in range(256))
+
+
+def cooc_directions(distance=1):
+    """The four directions of COOC_DIRECTIONS at ``distance`` (an integer in 1..16): ((0, d), (d, d), (d, 0), (d, -d)).
+
+    Host syncs: none."""
+    if isinstance(distance, bool) or not isinstance(distance, numbers.Integral) or not 1 <= distance <= COOC_MAX_OFFSET:
+        raise ValueError('cooc_directions: distance must be an integer in 1..%d (got %r)' % (COOC_MAX_OFFSET, distance))
+    return tuple((dy * int(distance), dx * int(distance)) for dy, dx in COOC_DIRECTIONS)
+
+
+def _cooc_lut(fn, lut, levels):
+    """``lut`` as a list for the launch argument: None is level_lut(levels); a tensor on the GPU cannot be one."""
+    if lut is None:
+        return level_lut(levels)
+    if torch.is_tensor(lut):
+        if lut.device.type != 'cpu':
+            raise TypeError('%s: lut is a launch argument and must live on the host (got a tensor on %s)' % (fn, lut.device))
+        if lut.dtype == torch.bool or lut.is_floating_point() or lut.is_complex():
+            raise ValueError('%s: lut must hold integers (got %s)' % (fn, lut.dtype))
+        lut = lut.reshape(-1).tolist() if lut.dim() == 1 else [None]
+    elif isinstance(lut, np.ndarray):
+        if lut.dtype.kind not in 'iu':
+            raise ValueError('%s: lut must hold integers (got %s)' % (fn, lut.dtype))
+        lut = lut.tolist() if lut.ndim == 1 else [None]
+    elif not isinstance(lut, (list, tuple)):
+        raise TypeError('%s: lut must be None, a list, a tuple, a numpy array or a CPU tensor (got %s)' % (fn, type(lut).__name__))
+    if len(lut) != 256:
+        raise ValueError('%s: lut must be 256 integers, one per value of the plane' % fn)
+    return lut
+
+
+def _cooc_tables(fn, labels, values, offsets, levels, lut, symmetric, max_label, within):
+    """The checks, every one before a launch, and the launch: (tables [R, K, levels, levels], meta, max_label)."""
+    levels = _check_levels(fn, levels)
+    lut = _cooc_lut(fn, lut, levels)
+    try:
+        offsets = list(offsets)
+    except TypeError:
+        raise ValueError('%s: offsets must be a sequence of pairs (dy, dx) (got %r)' % (fn, offsets))
+    kernels.HipKernels._check_cooc(lut, levels, offsets)
+    _check_image(fn, 'labels', labels, _INT_DTYPES)
+    if labels.shape[0] * labels.shape[1] >= kernels.COOC_MAX_PIXELS:
+        raise ValueError('%s: images of 2^30 pixels or more are not supported (%d x %d): a count must fit int32'
+                         % ((fn,) + tuple(labels.shape)))
+    hi, values = _region_args(fn, labels, values, max_label, within, (torch.bool, torch.uint8))
+    with torch.cuda.device(labels.device):
+        tables, meta = kernels.get().region_cooccurrence(labels, values, hi, lut, levels, offsets, bool(symmetric), within)
+    return tables.view(hi + 1, len(offsets), levels, levels), meta, hi
+
+
+def region_cooccurrence(labels, values, offsets=COOC_DIRECTIONS, levels=16, lut=None, symmetric=True, max_label=None, within=None):
+    """The grey-level co-occurrence tables (GLCM) of a uint8 or bool plane over every region of a label image (csrc/region.hip; the
+    contract item by item: kernels.KernelSpec.region_cooccurrence): int32 [max_label + 1, len(offsets), levels, levels].  Entry [R, k,
+    a, b] is the number of pixel pairs p, q = p + offsets[k] that both lie inside the image, both carry label R, both lie where
+    ``within`` is non-zero (if given), and whose levels are a at p and b at q; with ``symmetric`` every pair is also counted the
+    other way round, so the table equals its transpose and a pair of equal levels adds 2 to the diagonal (skimage's
+    ``graycomatrix(..., symmetric=True)``).  ``offsets``: 1 to 8 pairs (dy, dx), |dy| and |dx| <= 16, not (0, 0); ``levels``: 2..16;
+    ``lut``: None (``level_lut(levels)``) or 256 integers below ``levels`` as a list, tuple, numpy array or CPU tensor -- the level
+    of a pixel is lut[v]; a tensor on the GPU is a TypeError, because the table is a launch argument.  Row 0, the background, is a
+    region like any other: ``within=labels != 0`` leaves it out.  Images of 2^30 pixels or more are refused (a count must fit
+    int32).  Other arguments as region_statistics.  Exact integers, bit-identical from call to call.
+
+    Host syncs: as region_statistics."""
+    tables, meta, hi = _cooc_tables('region_cooccurrence', labels, values, offsets, levels, lut, symmetric, max_label, within)
+    _refuse_labels('region_cooccurrence', int(meta.item()), hi)    # host sync: the refused pixels
+    return tables
+
+
+def _check_props(fn, props):
+    try:
+        props = tuple(props)
+    except TypeError:
+        raise ValueError('%s: props must be a sequence of names out of %r' % (fn, COOC_PROPERTIES))
+    if not props or any(p not in COOC_PROPERTIES for p in props):
+        raise ValueError('%s: props must be names out of %r, at least one (got %r)' % (fn, COOC_PROPERTIES, props))
+    return props
+
+
+def cooccurrence_properties(tables, props=COOC_PROPERTIES):
+    """The Haralick properties of co-occurrence tables: float32 [R, K, len(props)] for integer tables [R, K, levels, levels] (those
+    of region_cooccurrence), computed in float64 on the tables' device from the integers and rounded once.  With n the total of a
+    table and P = C / n: contrast = sum P (i - j)^2; dissimilarity = sum P |i - j|; homogeneity = sum P / (1 + (i - j)^2); ASM = sum
+    P^2; energy = sqrt(ASM); entropy = -sum over P > 0 of P log2 P; correlation = sum P (i - mu_i)(j - mu_j) / (sigma_i sigma_j) in
+    the centred form.  Correlation is 1 where either marginal of the integer table has a single non-zero level (skimage's rule for
+    sigma = 0, decided from the integers, with no threshold).  A table with n = 0 gives 0 for every property.
+
+    Host syncs: none."""
+    fn = 'cooccurrence_properties'
+    if not torch.is_tensor(tables) or tables.dtype not in _INT_DTYPES:
+        raise TypeError('%s takes the integer tables of region_cooccurrence' % fn)
+    if tables.dim() != 4 or tables.shape[2] != tables.shape[3] or tables.shape[2] < 1:
+        raise ValueError('%s: tables must be [R, K, levels, levels] (got %s)' % (fn, tuple(tables.shape)))
+    props = _check_props(fn, props)
+    f64 = dict(dtype=torch.float64, device=tables.device)
+    lv = tables.shape[2]
+    c = tables.to(torch.float64)
+    n = c.sum((2, 3))
+    some = n > 0
+    p = c / torch.where(some, n, torch.ones_like(n))[:, :, None, None]
+    i = torch.arange(lv, **f64)
+    d = i[:, None] - i[None, :]
+    out = {}
+    if 'contrast' in props:
+        out['contrast'] = (p * (d * d)).sum((2, 3))
+    if 'dissimilarity' in props:
+        out['dissimilarity'] = (p * d.abs()).sum((2, 3))
+    if 'homogeneity' in props:
+        out['homogeneity'] = (p / (1.0 + d * d)).sum((2, 3))
+    if 'ASM' in props or 'energy' in props:
+        out['ASM'] = (p * p).sum((2, 3))
+        out['energy'] = out['ASM'].sqrt()
+    if 'entropy' in props:
+        out['entropy'] = -torch.where(p > 0, p * torch.log2(torch.where(p > 0, p, torch.ones_like(p))), torch.zeros_like(p)).sum((2, 3))
+    if 'correlation' in props:
+        pi, pj = p.sum(3), p.sum(2)                                  # the marginals over the anchor's and the partner's level
+        di, dj = i - (pi * i).sum(2, keepdim=True), i - (pj * i).sum(2, keepdim=True)
+        var = (pi * di * di).sum(2) * (pj * dj * dj).sum(2)
+        cov = (p * di[:, :, :, None] * dj[:, :, None, :]).sum((2, 3))
+        flat = ((tables.sum(3) != 0).sum(2) <= 1) | ((tables.sum(2) != 0).sum(2) <= 1)      # one level only: sigma = 0 exactly
+        out['correlation'] = torch.where(flat, torch.ones_like(cov), cov / torch.where(flat, torch.ones_like(var), var).sqrt())
+    zero = torch.zeros_like(n)
+    return torch.stack([torch.where(some, out[name], zero) for name in props], dim=2).to(torch.float32)
+
+
+def texture_features(labels, tile, kept_labels, stains=None, order='bgr', planes=(0,), levels=16, lo=0, hi=None, distance=1,
+                     max_label=None):
+    """Chromatin texture per nucleus, to put beside ``nucleus_features`` and ``stain_features``: float32 [len(kept_labels), 12 *
+    len(planes)]; ``TEXTURE_FEATURE_NAMES`` names the columns for ``planes=(0,)``, the haematoxylin plane.  labels, tile, stains,
+    order, kept_labels: as stain_features; ``planes``: as separate_stains.  Per plane of ``separate_stains`` the symmetric
+    co-occurrence tables of every nucleus are taken at the four directions ``cooc_directions(distance)`` over the pixel pairs inside
+    the nucleus (``within = labels != 0``: the background is skipped), at ``levels`` levels of ``level_lut(levels, lo, hi)``; for
+    each of contrast, dissimilarity, homogeneity, energy, correlation and entropy (cooccurrence_properties, float32) two columns
+    follow: the mean over the four directions, ((p0 + p1) + (p2 + p3)) / 4 in float32, and their range, max - min -- the two
+    rotation-robust summaries of Haralick et al. 1973.  A nucleus without a pair in a direction contributes 0 there.
+
+    The stain planes are in levels of 1 / 64 of a natural-log unit and rarely pass about 160, so the default ``hi=None``, 255,
+    leaves the upper levels nearly empty: the caller chooses ``hi`` for the stain (``hi=159`` for haematoxylin).  No value is read
+    off the tile: a ``hi`` that followed the tile would make the columns incomparable between tiles.
+        x = torch.cat([features, stain_features(L, tile, kept, max_label=n), texture_features(L, tile, kept, hi=159, max_label=n)], 1)
+
+    Host syncs: the label range unless ``max_label`` is given, and one read that brings the refused pixels and the check of
+    kept_labels: labels or kept_labels outside [0, max_label] raise ValueError."""
+    fn = 'texture_features'
+    _check_image(fn, 'labels', labels, _INT_DTYPES)
+    _check_color(fn, tile)
+    if tuple(tile.shape[:2]) != tuple(labels.shape) or tile.device != labels.device:
+        raise ValueError('%s: tile must have the height, width and device of labels (got %s on %s and %s on %s)'
+                         % (fn, tuple(tile.shape[:2]), tile.device, tuple(labels.shape), labels.device))
+    if not torch.is_tensor(kept_labels) or kept_labels.dtype not in (torch.int32, torch.int64):
+        raise TypeError('%s: kept_labels must be an int32 or int64 tensor' % fn)
+    if kept_labels.dim() != 1 or kept_labels.device != labels.device:
+        raise ValueError('%s: kept_labels must be 1-D and on the device of labels' % fn)
+    if order not in STAIN_ORDERS:
+        raise ValueError("order must be 'bgr' or 'rgb', got %r" % (order,))
+    _check_planes(planes)
+    lut = level_lut(levels, lo, 255 if hi is None else hi)
+    offsets = cooc_directions(distance)
+    if labels.shape[0] * labels.shape[1] >= kernels.COOC_MAX_PIXELS:
+        raise ValueError('%s: images of 2^30 pixels or more are not supported (%d x %d)' % ((fn,) + tuple(labels.shape)))
+    top = _label_top(fn, labels, max_label)
+    stain_planes = separate_stains(tile, stains, order, planes=planes)
+    with torch.cuda.device(labels.device):
+        k = kernels.get()
+        inside = labels != 0
+        columns, meta = [], None
+        for plane in stain_planes:
+            tables, m = k.region_cooccurrence(labels, plane, top, lut, levels, offsets, True, inside)
+            meta = m if meta is None else meta                      # the same labels every time: one check covers all planes
+            props = cooccurrence_properties(tables.view(top + 1, len(offsets), levels, levels), TEXTURE_PROPERTIES)
+            mean = ((props[:, 0] + props[:, 1]) + (props[:, 2] + props[:, 3])) * 0.25      # float32, in this order
+            columns.append(torch.stack([mean, props.max(1)[0] - props.min(1)[0]], dim=2).reshape(top + 1, 2 * len(TEXTURE_PROPERTIES)))
+    table = torch.cat(columns, dim=1)
+    kept = kept_labels.to(torch.int64)
+    out = table[kept.clamp(0, top)]
+    refused, bad_kept = torch.stack([meta[0].to(torch.int64), ((kept < 0) | (kept > top)).sum()]).tolist()      # host sync
+    _refuse_labels(fn, refused, top)
+    if bad_kept:
+        raise ValueError('%s: %d of kept_labels lie outside [0, %d]' % (fn, bad_kept, top))
     return out
 
 

@@ -81,8 +81,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *      cgc_rank_entropy_max_radius, cgc_rank_tile_rows, cgc_rank_tile_cols, cgc_rank_entropy_term, cgc_rank_filter, CGC_RANK_*
  *  23: region statistics (per label value: count, sum, sum of squares, extrema with positions; 256-bin histograms; quantiles off
  *      them): cgc_region_tile_side, cgc_region_table_slots, cgc_region_ws_bytes, cgc_region_moments, cgc_region_histogram,
- *      cgc_region_quantiles */
-#define CGC_ABI_VERSION 23
+ *      cgc_region_quantiles
+ *  24: region co-occurrence (per label value and offset: the grey-level co-occurrence table of a uint8 plane over pairs of pixels of
+ *      one region): cgc_region_cooc_max_offset, cgc_region_cooc_max_offsets, cgc_region_cooccurrence */
+#define CGC_ABI_VERSION 24
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -501,6 +503,25 @@ int cgc_region_moments(const int* labels, const void* values, int value_bytes, i
 int cgc_region_histogram(const int* labels, const uint8_t* values, const void* within_or_null, int within_bytes, int H, int W,
                          int max_label, int* hist, int* meta, cgc_stream_t stream);
 int cgc_region_quantiles(const int* hist, int64_t rows, const int* q10k, int nq, uint8_t* out, cgc_stream_t stream);
+
+/* ---- F18 (beside F17, csrc/region.hip): grey-level co-occurrence tables of a uint8 plane over the regions of a label image.  The
+ * contract item by item: cgc-net_amd/kernels.py KernelSpec.region_cooccurrence.  labels, max_label, within_or_null, the refused pixels
+ * and *meta as F17 (*meta counts a refused pixel once per call, not once per offset); H * W < 2^30, so that a symmetric diagonal bin
+ * of at most 2 H W fits int32.  values uint8 [H, W]; the level of a pixel is lut256_host[v], 256 bytes in HOST memory, every entry <
+ * levels, levels in 2..16; the table travels by value, the buffer may be freed when the call returns.  offsets_host: noff (1 ..
+ * cgc_region_cooc_max_offsets() = 8) pairs (dy, dx) in HOST memory, |dy|, |dx| <= cgc_region_cooc_max_offset() = 16, not (0, 0).
+ * For offset k, anchor p = (y, x) and partner q = (y + dy, x + dx) the pair is counted in row R iff p and q lie inside the image,
+ * labels[p] == labels[q] == R, 0 <= R <= max_label, and within is null or non-zero at both.  tables int32 [max_label + 1, noff,
+ * levels * levels], indexed in 64 bits: a counted pair with levels (a, b) adds 1 to bin a * levels + b and, with symmetric != 0, 1 to
+ * bin b * levels + a (2 on the diagonal: skimage's symmetric=True).  One launch per offset; pairs of a label that finds no slot in
+ * the tile's LDS table add to `tables` directly: exact for every input, integer adds only, bit-identical from call to call.
+ * Bad dims, max_label, within_bytes, levels, a lut entry >= levels, noff, an offset out of range or (0, 0), H * W >= 2^30 or a null
+ * pointer where one is needed: CGC_EINVAL, nothing launched.  H * W = 0: zeros. */
+int cgc_region_cooc_max_offset(void);
+int cgc_region_cooc_max_offsets(void);
+int cgc_region_cooccurrence(const int* labels, const uint8_t* values, const void* within_or_null, int within_bytes, int H, int W,
+                            int max_label, const uint8_t* lut256_host, int levels, const int* offsets_host, int noff, int symmetric,
+                            int* tables, int* meta, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
