@@ -68,7 +68,9 @@ __device__ __forceinline__ float group_max(float v, int lpr) {
 __device__ __forceinline__ float act_fwd(float x, int act) {
   switch (act) {
     case CGC_ACT_RELU: return x > 0.f ? x : 0.f;
-    case CGC_ACT_ELU: return x > 0.f ? x : expf(x) - 1.f;
+    // expm1f, as nn.ELU: expf(x) - 1.f carries the rounding of a number near 1 (6e-8 absolute) into a result near x, and the entries of
+    // an L2-normalised row of width F are ~1/sqrt(F) -- 1e-4 relative at the smallest ones, which BatchNorm then scales up
+    case CGC_ACT_ELU: return x > 0.f ? x : expm1f(x);
     case CGC_ACT_LEAKYRELU: return x > 0.f ? x : 0.01f * x;
     default: return x;
   }

@@ -654,7 +654,11 @@ int cgc_reduce_batched(const float* ws, float* out, int outer, int parts, int nu
  * backward reductions (cgc_bn_bwd_reduce, cgc_colsum, ...).  The FORWARD statistics (sum of o, sum of o^2 per column, o = act(hn))
  * are accumulated in double from the first addition on -- the variance is a difference of the two, and on the coarsened levels
  * std << |mean| -- and their slots hold doubles: cgc_stats_ws_floats(n,F) floats of workspace (8-byte aligned) for
- * cgc_l2norm_act_stats / cgc_l2norm_act_bn / cgc_sage_wide_fwd / cgc_sage_narrow_fwd. */
+ * cgc_l2norm_act_stats / cgc_l2norm_act_bn / cgc_sage_wide_fwd / cgc_sage_narrow_fwd.
+ * Envelope: cgc_l2norm_act_stats, cgc_l2norm_act_bn, cgc_bn_act_apply, cgc_bn_bwd_reduce, cgc_bn_act_l2_bwd, cgc_colsum and
+ * cgc_softmax_bwd hold a row's columns in the lanes' registers: F (C) <= 2048, otherwise CGC_EINVAL and nothing is launched or
+ * written.  cgc_softmax_fwd, the dense adjacency transforms and cgc_adj_prep_fwd / cgc_adj_prep_bwd take any width (rows wider than
+ * 2048 floats, or wider than 512 floats that cannot be read with 16-byte loads, on a three-pass streaming route). */
 int cgc_stats_blocks(int n, int F);
 int64_t cgc_stats_ws_floats(int n, int F);
 int cgc_l2norm_act_stats(const float* h, int n, int F, int normalize, int act, float* hn, float* rinv,

@@ -1,7 +1,8 @@
 """GPU: every C-ABI entry point (through HipKernels) against the torch restatement of the kernel contract
 (oracle/flat_ref.py) on the same seeded inputs.  Index work must be bit-exact; fp32 work within 1e-4 relative
 (sum-order differences only).  Shapes cover: ragged graphs, widths that are / are not multiples of 4 (16-byte lanes
-vs scalar lanes), rows narrower and wider than a wavefront, empty rows, duplicates, isolated nodes."""
+vs scalar lanes), rows narrower and wider than a wavefront, empty rows, duplicates, isolated nodes.
+The per-element check of the row kernels (csrc/rowops.hip) against float64 is tests/test_rowops_fp64_gpu.py."""
 import numpy as np
 import pytest
 import torch
