@@ -16,6 +16,9 @@
 // holds at most the 4096 pixels of a tile) and one LDS atomic per counted pixel; a claimed slot is flushed as 256 consecutive counters.
 // COOCCURRENCE (KernelSpec.region_cooccurrence; DESIGN.md, "Region co-occurrence"): hipMemsetAsync, then one k_region_cooc per offset
 // -- k_region_hist with a pair of pixels (anchor, partner) where the histogram has one, and a bin per pair of levels.
+// GEOMETRY (KernelSpec.region_geometry; DESIGN.md, "Region geometry"): k_geometry_init, k_region_geometry -- the same tile and table;
+// the labels alone, staged in LDS with a frame of one position; runs folded by closed forms in tile coordinates, quads classified
+// where their four positions differ -- and k_geometry_finish for the extents of empty rows.
 // OVERFLOW.  region_slot() probes at most REGION_PROBES <= REGION_SLOTS slots and never waits: a label that finds neither itself nor
 // an empty slot there is sent to the global tables directly (a run at a time in MOMENTS, a pixel at a time in HISTOGRAM).  Both routes
 // end in the same integer atomics on the same global words, so which pixels take which route -- it depends on the order in which lanes
@@ -379,6 +382,246 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_region_cooc(const int* __restrict
   }
 }
 
+// GEOMETRY (KernelSpec.region_geometry; DESIGN.md, "Region geometry"): the shape of every region from the label image alone.  A pixel
+// *belongs* to row L as it is counted above; a position outside the image, with a refused label or outside `within` belongs to none.
+constexpr int GEOM_NONE = REGION_EMPTY;
+constexpr int GEOM_DIRS = 8;                                     // directions (a, b) of the extents a x + b y; every b >= 0 (exported order)
+constexpr int GEOM_MAX_SIDE = 32767;                             // sum x^2 over 2^31 pixels stays inside int64 (exported)
+constexpr int GEOM_SIDE = REGION_TILE + 2;                       // a tile and the frame of one position its quads reach into
+
+struct GeomTables {
+  int* count;                            // [R]
+  u64 *sy, *sx, *syy, *sxy, *sxx;        // [R] each, image coordinates
+  int* ext;                              // [R, 8, 2] min, max of a x + b y
+  int* quad;                             // [R, 4] n1, n2, nd, n3
+  int* border;                           // [R]
+};
+
+struct GeomTile {                        // sums and extents in tile coordinates, shifted to the image at the flush
+  int key[REGION_SLOTS];
+  int cnt[REGION_SLOTS], border[REGION_SLOTS];
+  uint32_t sy[REGION_SLOTS], sx[REGION_SLOTS], syy[REGION_SLOTS], sxy[REGION_SLOTS], sxx[REGION_SLOTS];      // at most 4096 * 63 * 63
+  int ext[REGION_SLOTS][GEOM_DIRS][2];
+  int quad[REGION_SLOTS][4];
+};
+
+__device__ __forceinline__ int geom_a(int d) { return d == 0 ? 1 : d == 1 ? 2 : d == 2 ? 1 : d == 3 ? 1 : d == 4 ? 0 : d == 5 ? -1 : d == 6 ? -1 : -2; }
+__device__ __forceinline__ int geom_b(int d) { return d == 0 ? 0 : d == 1 ? 1 : d == 2 ? 1 : d == 3 ? 2 : d == 4 ? 1 : d == 5 ? 2 : d == 6 ? 1 : 1; }
+
+// A minimum or maximum into a word that only ever falls (rises).  The word is read first and the atomic is skipped where it would
+// change nothing: whatever the read returns was written by somebody, so the final value is beyond it.  A whole image of background
+// would otherwise send sixteen atomics per tile to the one cache line that holds its extents.
+template <int SCOPE>
+__device__ __forceinline__ void geom_min(int* p, int v) {
+  if (v < __hip_atomic_load(p, __ATOMIC_RELAXED, SCOPE)) atomicMin(p, v);
+}
+template <int SCOPE>
+__device__ __forceinline__ void geom_max(int* p, int v) {
+  if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, SCOPE)) atomicMax(p, v);
+}
+
+// One tile.  The label every position of the tile and of a frame of one position around it belongs to (GEOM_NONE: to none) is staged
+// in LDS, so that runs and quads are walked by loops over k, not by unrolled copies of their bodies: a fold is 23 atomics and a slot
+// lookup, and sixteen copies of it per thread do not fit the instruction cache.
+template <bool WITHIN>
+__global__ void __launch_bounds__(CGC_BLOCK) k_region_geometry(const int* __restrict__ labels, const void* __restrict__ within, int wbytes,
+                                                               int H, int W, int tiles_x, int max_label, GeomTables g, int* meta) {
+  __shared__ GeomTile t;
+  __shared__ int e[GEOM_SIDE][GEOM_SIDE];                          // position (ly, lx) of the tile, -1 .. REGION_TILE, at [ly + 1][lx + 1]
+  for (int i = threadIdx.x; i < REGION_SLOTS; i += CGC_BLOCK) {
+    t.key[i] = REGION_EMPTY;
+    t.cnt[i] = t.border[i] = 0;
+    t.sy[i] = t.sx[i] = t.syy[i] = t.sxy[i] = t.sxx[i] = 0;
+  }
+  for (int i = threadIdx.x; i < REGION_SLOTS * GEOM_DIRS; i += CGC_BLOCK) {
+    (&t.ext[0][0][0])[2 * i] = 0x7fffffff;
+    (&t.ext[0][0][0])[2 * i + 1] = (int)0x80000000;
+  }
+  (&t.quad[0][0])[threadIdx.x] = 0;                               // CGC_BLOCK == REGION_SLOTS * 4
+  if (threadIdx.x < GEOM_SIDE) e[0][threadIdx.x] = e[threadIdx.x][0] = GEOM_NONE;      // row and column -1: only the image's frame is ever read
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int ox = tx * REGION_TILE, oy = ty * REGION_TILE;
+  const int lx = threadIdx.x & (REGION_TILE - 1), ly0 = (threadIdx.x / REGION_TILE) * REGION_BAND;
+  const int x = ox + lx, y0 = oy + ly0;
+  const bool last_band = ly0 + REGION_BAND == REGION_TILE, last_lane = lx == REGION_TILE - 1;
+  // The row position (py, px) belongs to.  The address is clamped into the image; whether the position lies inside is decided from
+  // its coordinates.  `bad`: inside, and the label is outside [0, max_label].
+  auto belongs = [&](int py, int px, bool& bad) -> int {
+    const int64_t i = (int64_t)(py < H ? py : H - 1) * W + (px < W ? px : W - 1);
+    const int L = labels[i];
+    const bool on = !WITHIN || image_nonzero(within, wbytes, i);
+    const bool inside = py < H && px < W;
+    bad = inside && (L < 0 || L > max_label);
+    return inside && !bad && on ? L : GEOM_NONE;
+  };
+  unsigned on = 0, brk = 0, refused = 0;                          // bit k: pixel k belongs somewhere; not where pixel k - 1 does; is refused
+  {
+    int prev = GEOM_NONE;
+    bool bad;
+#pragma unroll
+    for (int k = 0; k < REGION_BAND; ++k) {
+      const int L = belongs(y0 + k, x, bad);
+      refused |= (unsigned)bad << k;
+      on |= (unsigned)(L != GEOM_NONE) << k;
+      brk |= (unsigned)(L != prev) << k;
+      prev = L;
+      e[ly0 + k + 1][lx + 1] = L;
+    }
+    if (last_band) e[REGION_TILE + 1][lx + 1] = belongs(oy + REGION_TILE, x, bad);      // the row below the tile
+    if (last_lane) {                                              // the column to its right
+#pragma unroll
+      for (int k = 0; k < REGION_BAND; ++k) e[ly0 + k + 1][REGION_TILE + 1] = belongs(y0 + k, x + 1, bad);
+      if (last_band) e[REGION_TILE + 1][REGION_TILE + 1] = belongs(oy + REGION_TILE, x + 1, bad);
+    }
+  }
+  __syncthreads();
+
+  // pixels: the runs of one label down the thread's 16 pixels, rows ya .. yb of the tile, by their closed forms
+  unsigned starts = on & brk;
+  for (int r = 0; r < REGION_BAND && starts != 0; ++r) {
+    const int ka = __builtin_ctz(starts);
+    starts &= starts - 1;
+    const int kb = __builtin_ctz((starts | ~on) & (~0u << ka)) - 1;      // the run ends before the next start or pixel of no row; ~on has bit 16
+    const int L = e[ly0 + ka + 1][lx + 1];
+    const int n = kb - ka + 1, ya = ly0 + ka, yb = ly0 + kb;
+    const int rsy = n * (ya + yb) / 2;
+    const int rsyy = (yb * (yb + 1) * (2 * yb + 1) - (ya - 1) * ya * (2 * ya - 1)) / 6;
+    const int rb = x == 0 || x == W - 1 ? n : (int)(oy + ya == 0) + (int)(oy + yb == H - 1 && H > 1);
+    const int s = region_slot(t.key, L);
+    if (s >= 0) {
+      atomicAdd(&t.cnt[s], n);
+      if (rb != 0) atomicAdd(&t.border[s], rb);
+      atomicAdd(&t.sy[s], (uint32_t)rsy);
+      atomicAdd(&t.sx[s], (uint32_t)(n * lx));
+      atomicAdd(&t.syy[s], (uint32_t)rsyy);
+      atomicAdd(&t.sxy[s], (uint32_t)(rsy * lx));
+      atomicAdd(&t.sxx[s], (uint32_t)(n * lx * lx));
+#pragma unroll
+      for (int d = 0; d < GEOM_DIRS; ++d) {                       // b >= 0: the run's extents are attained at its two ends
+        geom_min<__HIP_MEMORY_SCOPE_WORKGROUP>(&t.ext[s][d][0], geom_a(d) * lx + geom_b(d) * ya);
+        geom_max<__HIP_MEMORY_SCOPE_WORKGROUP>(&t.ext[s][d][1], geom_a(d) * lx + geom_b(d) * yb);
+      }
+    } else {                                                      // no slot: the same atomics on the global tables, in image coordinates
+      const int64_t sy = (int64_t)rsy + (int64_t)n * oy, syy = (int64_t)rsyy + 2 * (int64_t)oy * rsy + (int64_t)n * oy * oy;
+      atomicAdd(&g.count[L], n);
+      if (rb != 0) atomicAdd(&g.border[L], rb);
+      atomicAdd(&g.sy[L], (u64)sy);
+      atomicAdd(&g.sx[L], (u64)((int64_t)n * x));
+      atomicAdd(&g.syy[L], (u64)syy);
+      atomicAdd(&g.sxy[L], (u64)(sy * x));
+      atomicAdd(&g.sxx[L], (u64)((int64_t)n * x * x));
+      int* ext = g.ext + (int64_t)L * (GEOM_DIRS * 2);
+#pragma unroll
+      for (int d = 0; d < GEOM_DIRS; ++d) {
+        geom_min<__HIP_MEMORY_SCOPE_AGENT>(&ext[2 * d], geom_a(d) * x + geom_b(d) * (oy + ya));
+        geom_max<__HIP_MEMORY_SCOPE_AGENT>(&ext[2 * d + 1], geom_a(d) * x + geom_b(d) * (oy + yb));
+      }
+    }
+  }
+
+  // quads: pass 0, those whose top-left corner is one of the thread's pixels -- and, in the tiles of the top edge, the one above
+  // them in row -1; pass 1, for the first lane of the tiles of the left edge, the same in column -1
+  int cl = GEOM_NONE, cs = -1;                                    // the label last looked up and its slot
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass == 0 ? x >= W : !(tx == 0 && lx == 0)) continue;
+    const int qx = pass == 0 ? lx : -1;
+    const int k0 = ty == 0 && ly0 == 0 ? -1 : 0;
+    int tl = e[ly0 + k0 + 1][qx + 1], tr = e[ly0 + k0 + 1][qx + 2];
+    for (int k = k0; k < REGION_BAND; ++k) {
+      const int bl = e[ly0 + k + 2][qx + 1], br = e[ly0 + k + 2][qx + 2];
+      if (y0 + k < H && !(tl == tr && tl == bl && tl == br)) {     // the pattern of every row present in the quad
+        const int p[4] = {tl, tr, bl, br};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int L = p[i];
+          bool first = L != GEOM_NONE;
+          unsigned m = 0;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (j < i && p[j] == L) first = false;
+            m |= (unsigned)(p[j] == L) << j;
+          }
+          if (!first) continue;
+          const int c = __builtin_popcount(m);                    // 1 .. 3: the four are not all equal
+          const int cls = c == 1 ? 0 : c == 3 ? 3 : (m == 9u || m == 6u) ? 2 : 1;
+          if (L != cl) {
+            cl = L;
+            cs = region_slot(t.key, L);
+          }
+          if (cs >= 0) atomicAdd(&t.quad[cs][cls], 1);
+          else atomicAdd(&g.quad[(int64_t)L * 4 + cls], 1);
+        }
+      }
+      tl = bl;
+      tr = br;
+    }
+  }
+  if (refused != 0) atomicAdd(meta, (int)__builtin_popcount(refused));
+  __syncthreads();
+
+  // flush: a wave per quarter of a slot's words, shifted to image coordinates
+  const int s = threadIdx.x & (REGION_SLOTS - 1), part = threadIdx.x / REGION_SLOTS;
+  const int L = t.key[s];
+  if (L == REGION_EMPTY) return;                                  // after the last barrier
+  if (part == 0) {
+    const int64_t n = t.cnt[s], sy = t.sy[s], sx = t.sx[s];
+    if (n == 0) return;                                           // a slot claimed by a quad alone
+    atomicAdd(&g.count[L], (int)n);
+    if (t.border[s] != 0) atomicAdd(&g.border[L], t.border[s]);
+    atomicAdd(&g.sy[L], (u64)(sy + n * oy));
+    atomicAdd(&g.sx[L], (u64)(sx + n * ox));
+    atomicAdd(&g.syy[L], (u64)((int64_t)t.syy[s] + 2 * oy * sy + n * oy * oy));
+    atomicAdd(&g.sxy[L], (u64)((int64_t)t.sxy[s] + ox * sy + oy * sx + n * ox * oy));
+    atomicAdd(&g.sxx[L], (u64)((int64_t)t.sxx[s] + 2 * ox * sx + n * ox * ox));
+  } else if (part == 3) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (t.quad[s][c] != 0) atomicAdd(&g.quad[(int64_t)L * 4 + c], t.quad[s][c]);
+  } else if (t.cnt[s] != 0) {                                      // a slot claimed by a quad alone has no extents
+    int* ext = g.ext + (int64_t)L * (GEOM_DIRS * 2);
+    // A row that fills half a tile is likely to fill others (the background does): their extents meet on one cache line, and the
+    // read first spares it most of the atomics.  A nucleus has its line to itself, and the read would only be a round trip more.
+    const bool shared = t.cnt[s] >= REGION_TILE * REGION_TILE / 2;
+#pragma unroll
+    for (int i = 0; i < GEOM_DIRS / 2; ++i) {
+      const int d = (part - 1) * (GEOM_DIRS / 2) + i;
+      const int shift = geom_a(d) * ox + geom_b(d) * oy;
+      const int lo = t.ext[s][d][0] + shift, hi = t.ext[s][d][1] + shift;
+      if (shared) {
+        geom_min<__HIP_MEMORY_SCOPE_AGENT>(&ext[2 * d], lo);
+        geom_max<__HIP_MEMORY_SCOPE_AGENT>(&ext[2 * d + 1], hi);
+      } else {
+        atomicMin(&ext[2 * d], lo);
+        atomicMax(&ext[2 * d + 1], hi);
+      }
+    }
+  }
+}
+static_assert(CGC_BLOCK == REGION_SLOTS * 4, "the flush of k_region_geometry gives a slot four threads, one per wave");
+
+__global__ void __launch_bounds__(CGC_BLOCK) k_geometry_init(int rows, GeomTables g, int* meta) {
+  for (int64_t r = (int64_t)blockIdx.x * CGC_BLOCK + threadIdx.x; r < rows; r += (int64_t)gridDim.x * CGC_BLOCK) {
+    g.count[r] = g.border[r] = 0;
+    g.sy[r] = g.sx[r] = g.syy[r] = g.sxy[r] = g.sxx[r] = 0;
+#pragma unroll
+    for (int d = 0; d < GEOM_DIRS; ++d) {
+      g.ext[r * (GEOM_DIRS * 2) + 2 * d] = 0x7fffffff;
+      g.ext[r * (GEOM_DIRS * 2) + 2 * d + 1] = (int)0x80000000;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) g.quad[r * 4 + c] = 0;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) *meta = 0;
+}
+
+__global__ void __launch_bounds__(CGC_BLOCK) k_geometry_finish(int rows, const int* __restrict__ count, int* __restrict__ ext) {      // the extents of an empty row
+  for (int64_t r = (int64_t)blockIdx.x * CGC_BLOCK + threadIdx.x; r < rows; r += (int64_t)gridDim.x * CGC_BLOCK) {
+    if (count[r] != 0) continue;
+#pragma unroll
+    for (int i = 0; i < GEOM_DIRS * 2; ++i) ext[r * (GEOM_DIRS * 2) + i] = 0;
+  }
+}
+
 template <typename T>
 void launch_moments(const int* labels, const void* values, const void* within, int wbytes, int H, int W, int max_label,
                     const RegionTables& g, int* meta, hipStream_t st) {
@@ -494,6 +737,36 @@ extern "C" int cgc_region_cooccurrence(const int* labels, const uint8_t* values,
                          lut, levels, dy, dx, (int)(symmetric != 0), (int)(k == 0), tables + (int64_t)k * bins, row_stride, meta);
     CGC_RETURN_IF_LAUNCH_FAILED();
   }
+  return 0;
+}
+
+extern "C" int cgc_region_geometry_max_side(void) { return GEOM_MAX_SIDE; }
+
+extern "C" int cgc_region_geometry(const int* labels, const void* within_or_null, int within_bytes, int H, int W, int max_label, int* count,
+                                   int64_t* sums, int* extents, int* quads, int* border, int* meta, cgc_stream_t stream) {
+  if (bad_region(H, W, max_label, within_or_null, within_bytes)) return CGC_EINVAL;
+  if (H > GEOM_MAX_SIDE || W > GEOM_MAX_SIDE || ((int64_t)H + 1) * ((int64_t)W + 1) >= ((int64_t)1 << 31)) return CGC_EINVAL;
+  if (count == nullptr || sums == nullptr || extents == nullptr || quads == nullptr || border == nullptr || meta == nullptr) return CGC_EINVAL;
+  const bool empty = (int64_t)H * W == 0;
+  if (!empty && labels == nullptr) return CGC_EINVAL;
+  hipStream_t st = as_stream(stream);
+  const int rows = max_label + 1;
+  u64* s = reinterpret_cast<u64*>(sums);                          // [5, rows]: sy, sx, syy, sxy, sxx
+  const GeomTables g{count, s, s + rows, s + 2 * (int64_t)rows, s + 3 * (int64_t)rows, s + 4 * (int64_t)rows, extents, quads, border};
+  hipLaunchKernelGGL(k_geometry_init, dim3(region_blocks(rows)), dim3(CGC_BLOCK), 0, st, rows, g, meta);
+  CGC_RETURN_IF_LAUNCH_FAILED();
+  if (!empty) {
+    const int tiles_x = ceil_div(W, REGION_TILE);
+    const dim3 grid((unsigned)((int64_t)tiles_x * ceil_div(H, REGION_TILE)));
+    if (within_or_null != nullptr)
+      hipLaunchKernelGGL(k_region_geometry<true>, grid, dim3(CGC_BLOCK), 0, st, labels, within_or_null, within_bytes, H, W, tiles_x, max_label, g,
+                         meta);
+    else
+      hipLaunchKernelGGL(k_region_geometry<false>, grid, dim3(CGC_BLOCK), 0, st, labels, within_or_null, 0, H, W, tiles_x, max_label, g, meta);
+    CGC_RETURN_IF_LAUNCH_FAILED();
+  }
+  hipLaunchKernelGGL(k_geometry_finish, dim3(region_blocks(rows)), dim3(CGC_BLOCK), 0, st, rows, count, extents);
+  CGC_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
 

@@ -45,6 +45,8 @@ COOC_MAX_OFFSET = 16       # region_cooccurrence: largest |dy|, |dx| (cgc_region
 COOC_MAX_OFFSETS = 8       # ... offsets per call (cgc_region_cooc_max_offsets)
 COOC_MAX_LEVELS = 16       # ... levels: levels^2 bins are the 256 16-bit bins of a slot in LDS
 COOC_MAX_PIXELS = 2 ** 30  # ... a symmetric diagonal bin holds at most 2 H W and must fit int32
+GEOMETRY_MAX_SIDE = 32767  # region_geometry: largest H, W (cgc_region_geometry_max_side): sum x^2 over 2^31 pixels fits int64
+GEOMETRY_DIRECTIONS = ((1, 0), (2, 1), (1, 1), (1, 2), (0, 1), (-1, 2), (-1, 1), (-2, 1))      # (a, b) of the extents a x + b y
 REGION_VALUE_DTYPES = {torch.uint8: (1, 0), torch.int8: (1, 1), torch.int16: (2, 1), torch.int32: (4, 1)}      # (bytes, signed)
 WS_JUMP_BATCH = 8        # pointer jumps of watershed_flood per host read: resolves parent chains of up to 2^7 pixels in one read
 
@@ -620,6 +622,36 @@ class KernelSpec(object):
         Inside the kernel ("Region co-occurrence"): one launch per offset over region_histogram's tile, table and walk."""
         raise NotImplementedError
 
+    def region_geometry(self, labels, max_label, within=None):
+        """The shape of every region of a label image, from the labels alone (F19, beside region_statistics; csrc/region.hip): one
+        segmented integer reduction.  Returns ((count int32 [R], sums int64 [5, R], extents int32 [R, 8, 2], quads int32 [R, 4], border
+        int32 [R]), meta int32 [1]) with R = max_label + 1, all on the device; no host read.
+
+        1.  labels, max_label, within, "a pixel *belongs* to row L" (= is counted there), the refused pixels and meta: items 1, 3 and
+            4 of region_statistics.  Row 0, the background, is a region like any other.  Also H, W <= GEOMETRY_MAX_SIDE = 32767, so
+            that sum x^2 over 2^31 pixels stays inside int64, and (H + 1)(W + 1) < 2^31, so that a quad count fits int32 (ValueError;
+            the library returns CGC_EINVAL and launches nothing).
+        2.  count = the number of the row's pixels.
+        3.  sums = sy, sx, syy, sxy, sxx over the row's pixels, in image coordinates: y = row, x = column.
+        4.  extents[L][k] = (minimum, maximum) of a x + b y over the row's pixel centres, (a, b) = GEOMETRY_DIRECTIONS[k] = (1,0)
+            (2,1) (1,1) (1,2) (0,1) (-1,2) (-1,1) (-2,1).  Directions (1,0) and (0,1) are the bounding box.
+        5.  quads = n1, n2, nd, n3.  A quad is a 2 x 2 window with top-left corner (y, x), y in -1 .. H-1 and x in -1 .. W-1; positions
+            outside the image belong to no row.  For a row present in the quad, the pattern of which of the four positions belong
+            to it is counted under exactly one of: n1 one pixel, n2 two that share an edge, nd the two of a diagonal, n3 three.  A
+            quad adds to every row that occurs in it, so to at most four.  Quads that lie in the row entirely are not stored: n4 =
+            (4 count - n1 - 2 n2 - 2 nd - 3 n3) / 4 exactly.
+        6.  border = the number of the row's pixels with y in {0, H-1} or x in {0, W-1}.
+        7.  An empty row has zeros everywhere, extents (0, 0): a caller masks by count == 0.  H * W = 0 gives empty rows only.
+        8.  Exact for every input, as item 8 of region_statistics: what finds no slot in the tile's table in LDS -- a run of pixels,
+            a quad's pattern -- goes to the global tables with the same integer atomics.
+        9.  Integer additions, minima and maxima only: bit-identical from call to call.
+        Inside the kernel ("Region geometry"): region_statistics' tile, column walk and table.  A run of one label down a
+        thread's 16 pixels is summed in registers in tile coordinates (32 bits in LDS) and shifted to image coordinates at the flush;
+        its extents are attained at its two ends.  The tile that holds a quad's top-left corner counts it, the tiles on the top and
+        left edge also own row and column -1; the column to the right and the row below are read through clamped addresses and
+        "inside the image" is decided from coordinates.  Only quads whose four positions differ are classified."""
+        raise NotImplementedError
+
     def region_quantiles(self, hist, q10k):
         """Quantiles of the rows of a table of 256-bin histograms (F17; csrc/region.hip).  Returns uint8 [R, len(q10k)] on the device;
         no host read.
@@ -999,6 +1031,7 @@ class HipKernels(KernelSpec):
         self.region_slots = int(self.lib.cgc_region_table_slots())             # labels such a tile folds in LDS (tests)
         self.region_cooc_max_offset = int(self.lib.cgc_region_cooc_max_offset())      # largest |dy|, |dx| of region_cooccurrence
         self.region_cooc_max_offsets = int(self.lib.cgc_region_cooc_max_offsets())    # offsets per call
+        self.region_geometry_max_side = int(self.lib.cgc_region_geometry_max_side())  # largest H, W of region_geometry
         self.scan_chunk = int(self.lib.cgc_scan_chunk_pixels())               # ... and of od_moments / angle_histogram
         self._dirs_checked = (None, None)                                      # angle_histogram's last direction table and its C array
         self._exp_checked = (None, None)                                       # od_recolor's last exponential table and its C array
@@ -1742,6 +1775,32 @@ class HipKernels(KernelSpec):
                                                    noff, 1 if symmetric else 0, _ptr(tables), _ptr(meta), self._stream()),
                   'cgc_region_cooccurrence')
         return tables, meta
+
+    @staticmethod
+    def _check_geometry_dims(fn, H, W):
+        if H > GEOMETRY_MAX_SIDE or W > GEOMETRY_MAX_SIDE:
+            raise ValueError('%s takes images of sides up to %d (got %d x %d): the coordinate sums must fit int64' % (fn, GEOMETRY_MAX_SIDE, H, W))
+        if (H + 1) * (W + 1) >= 2 ** 31:
+            raise ValueError('%s takes images with (H + 1)(W + 1) < 2^31 (got %d x %d): a quad count must fit int32' % (fn, H, W))
+
+    def region_geometry(self, labels, max_label, within=None):
+        HipKernels._check_max_label('region_geometry', max_label)
+        HipKernels._check_geometry_dims('region_geometry', *labels.shape)
+        assert not labels.is_floating_point() and labels.dtype != torch.bool
+        if labels.dtype == torch.int64:                                         # as _region_inputs: what does not fit int32 stays refused
+            labels = labels.clamp(-1, max_label + 1)
+        labels, within = self._image(labels.to(torch.int32)), self._image(within)
+        assert within is None or within.shape == labels.shape
+        H, W = labels.shape
+        dev = labels.device
+        R = max_label + 1
+        ints = torch.empty(R * 22, dtype=torch.int32, device=dev)                  # count, border, quads, extents
+        count, border, quads, extents = ints[:R], ints[R:2 * R], ints[2 * R:6 * R].view(R, 4), ints[6 * R:].view(R, 8, 2)
+        sums = torch.empty(5, R, dtype=torch.int64, device=dev)
+        meta = torch.empty(1, dtype=torch.int32, device=dev)
+        self._chk(self.lib.cgc_region_geometry(_ptr(labels), *_within_args(within), H, W, max_label, _ptr(count), _ptr(sums), _ptr(extents),
+                                               _ptr(quads), _ptr(border), _ptr(meta), self._stream()), 'cgc_region_geometry')
+        return (count, sums, extents, quads, border), meta
 
     def region_quantiles(self, hist, q10k):
         q = HipKernels._check_q10k(q10k)

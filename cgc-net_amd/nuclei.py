@@ -98,6 +98,15 @@ directions ``COOC_DIRECTIONS`` on the haematoxylin plane, twelve columns beside 
 ``nucleus_features``' sixteen keep the reference's form (gray plane, one offset, 256 levels, a crop that includes the neighbours):
     x = torch.cat([features, stain_features(L, tile, kept, max_label=n), texture_features(L, tile, kept, hi=159, max_label=n)], 1)
 
+``region_geometry`` is the shape beside them, from the label image alone (csrc/region.hip; kernels.KernelSpec.region_geometry): per
+label value the pixel count, the coordinate sums up to second order, the extents in eight directions, the bit-quad counts and the
+pixels on the image frame -- exact integers once more.  ``region_shape`` reads the usual properties off them (centroid, moments,
+axes, eccentricity, orientation, bounding box, crack and bit-quad perimeter, circularity, Euler numbers, Feret widths, the area of the
+enclosing 16-gon), ``shape_features`` is thirteen columns of them per nucleus, and ``clear_border`` drops the nuclei the tile cuts.
+Nine of ``nucleus_features``' sixteen columns are shape too and keep the reference's form (a crop in which neighbours count as
+foreground, one contour that may belong to a neighbour); these describe the pixels of their own label only, also where nuclei touch:
+    x = torch.cat([features, stain_features(...), texture_features(...), shape_features(L, kept, max_label=n)], 1)
+
 ``nucleus_features(labels, gray)`` returns the reference's ``feature`` / ``coordinate`` arrays of one image (csrc/nuclei.hip; the
 arithmetic item by item: kernels.KernelSpec.nucleus_features), ``graph_item`` turns them into the ``Data`` that
 ``_read_one_raw_graph`` builds, and ``save_reference_files`` writes them where the reference's dataset preparation reads them.
@@ -1897,6 +1906,192 @@ def texture_features(labels, tile, kept_labels, stains=None, order='bgr', planes
     _refuse_labels(fn, refused, top)
     if bad_kept:
         raise ValueError('%s: %d of kept_labels lie outside [0, %d]' % (fn, bad_kept, top))
+    return out
+
+
+GEOMETRY_DIRECTIONS = kernels.GEOMETRY_DIRECTIONS
+GEOMETRY_MAX_SIDE = kernels.GEOMETRY_MAX_SIDE
+RegionGeometry = collections.namedtuple('RegionGeometry', ('count', 'sy', 'sx', 'syy', 'sxy', 'sxx', 'extents', 'quads', 'border'))
+RegionShape = collections.namedtuple('RegionShape', (
+    'area', 'centroid_y', 'centroid_x', 'var_y', 'var_x', 'cov', 'major_axis', 'minor_axis', 'eccentricity', 'orientation', 'bbox',
+    'bbox_fill', 'perimeter_crack', 'perimeter', 'circularity', 'euler4', 'euler8', 'equivalent_diameter', 'feret_max', 'feret_min',
+    'polygon_area', 'convexity16', 'border'))
+SHAPE_FEATURE_NAMES = ('area', 'major_axis', 'minor_axis', 'eccentricity', 'orientation', 'perimeter', 'circularity', 'convexity16',
+                       'feret_max', 'feret_min', 'bbox_fill', 'holes', 'touches_border')
+
+
+def _geometry_tables(fn, labels, max_label, within):
+    """The refusals of the geometry functions, then the launch: (RegionGeometry, meta, max_label); meta is not read."""
+    _check_image(fn, 'labels', labels, _INT_DTYPES)
+    _check_within(fn, within, labels)
+    kernels.HipKernels._check_geometry_dims(fn, *labels.shape)
+    hi = _label_top(fn, labels, max_label)
+    with torch.cuda.device(labels.device):
+        (count, sums, extents, quads, border), meta = kernels.get().region_geometry(labels, hi, within)
+    return RegionGeometry(count, sums[0], sums[1], sums[2], sums[3], sums[4], extents, quads, border), meta, hi
+
+
+def region_geometry(labels, max_label=None, within=None):
+    """The shape of every region of a label image as exact integer tables (csrc/region.hip; the contract item by item:
+    kernels.KernelSpec.region_geometry).  labels, max_label, within: as region_statistics; sides of at most 32767 pixels and (H + 1)(W
+    + 1) < 2^31 (ValueError).  Returns the named tuple ``RegionGeometry``, every table indexed by label value -- row 0 is the
+    background, a region like any other:
+
+      count    int32 [R]        the region's pixels
+      sy, sx, syy, sxy, sxx     int64 [R] each: sums of the pixels' coordinates and of their products, y = row, x = column
+      extents  int32 [R, 8, 2]  minimum and maximum of a x + b y over the pixel centres for (a, b) in ``GEOMETRY_DIRECTIONS``;
+                                directions (1, 0) and (0, 1) are the bounding box
+      quads    int32 [R, 4]     n1, n2, nd, n3: the 2 x 2 windows (over the image and a frame of one pixel that belongs to nobody) in
+                                which the region has one pixel, two that share an edge, the two of a diagonal, three
+      border   int32 [R]        the region's pixels in the first or last row or column of the image
+
+    A label without a pixel has zeros everywhere -- its extents (0, 0) are no coordinates: mask by ``count == 0``.  Unlike nine of
+    ``nucleus_features``' columns, which keep the reference's crop (neighbours count as foreground there), every number describes the
+    pixels of that label and nothing else.  ``region_shape`` turns the tables into the usual properties.  Exact integers,
+    bit-identical from call to call.
+
+    Host syncs: as region_statistics."""
+    geometry, meta, hi = _geometry_tables('region_geometry', labels, max_label, within)
+    _refuse_labels('region_geometry', int(meta.item()), hi)        # host sync: the refused pixels
+    return geometry
+
+
+def region_shape(geometry):
+    """Shape properties of every region from a ``RegionGeometry``: the named tuple ``RegionShape`` of tables [R], float32 unless said
+    otherwise, computed in float64 on the tables' device from the integers and rounded once.  Rows with count 0 are 0 everywhere.  The
+    definitions, tied to no library's version (n = count; n1, n2, nd, n3 = quads; x = column, y = row):
+
+      area                  n
+      centroid_y, _x        sy / n, sx / n
+      var_y, var_x, cov     the second central moments.  With the sums shifted to the bounding box's corner (in int64; nothing is
+                            subtracted at image-coordinate magnitude) A = n suu - su^2, B = n svv - sv^2, C = n suv - su sv: var_x =
+                            A / n^2, var_y = B / n^2, cov = C / n^2.  The products are exact while they stay below 2^53 (any nucleus).
+      major_axis, minor_axis  4 sqrt(l1), 4 sqrt(l2) of the eigenvalues l1 >= l2 of the covariance: with D = sqrt((A - B)^2 + 4 C^2),
+                            l1 = (A + B + D) / (2 n^2) and l2 = max(0, A + B - D) / (2 n^2) -- the axes of the ellipse with these moments
+      eccentricity          sqrt(1 - l2 / l1) = sqrt(2 D / (A + B + D)), 0 where l1 = 0
+      orientation           atan2(2 cov, var_x - var_y) / 2 = atan2(2 C, A - B) / 2: the angle of the major axis from +x towards +y (y
+                            points down the image), in (-pi/2, pi/2]; 0 where both arguments are 0 (a disc, a square, one pixel)
+      bbox                  int32 [R, 4]: (y0, x0, y1 + 1, x1 + 1); bbox_fill = n / ((y1 + 1 - y0)(x1 + 1 - x0))
+      perimeter_crack       int32: n1 + n2 + n3 + 2 nd, the number of pixel edges between the region and everything else, the image
+                            frame included
+      perimeter             n2 + (n1 + n3 + 2 nd) / sqrt(2), the bit-quad estimate; circularity = 4 pi n / perimeter^2
+      euler4, euler8        int32: (n1 - n3 + 2 nd) / 4 and (n1 - n3 - 2 nd) / 4, components minus holes for 4- and 8-connectivity
+      equivalent_diameter   sqrt(4 n / pi)
+      feret_max, feret_min  the largest and smallest of the eight widths (max_k - min_k + |a| + |b|) / sqrt(a^2 + b^2) of the pixel
+                            SQUARES (not centres) across ``GEOMETRY_DIRECTIONS``
+      polygon_area          the area of the 16-gon cut out by the sixteen support lines of the pixel squares in these directions and
+                            their opposites: consecutive lines (in angular order) are intersected, the shoelace formula gives the area
+      convexity16           n / polygon_area.  The 16-gon CONTAINS the convex hull, so this is a lower bound of solidity (area over
+                            hull area), not solidity: equal for shapes whose hull has edges in these directions only
+      border                int32: as in the geometry
+
+    Host syncs: none."""
+    if not isinstance(geometry, RegionGeometry):
+        raise TypeError('region_shape takes the RegionGeometry of region_geometry')
+    g = geometry
+    f64, i64 = torch.float64, torch.int64
+    ni = g.count.to(i64)
+    some = ni > 0
+    n = torch.where(some, ni, torch.ones_like(ni)).to(f64)
+    ext = g.extents.to(i64)
+    x0, x1, y0, y1 = ext[:, 0, 0], ext[:, 0, 1], ext[:, 4, 0], ext[:, 4, 1]
+    su, sv = g.sx - ni * x0, g.sy - ni * y0                          # int64, shifted to the corner of the bounding box
+    suu = g.sxx - 2 * x0 * g.sx + ni * x0 * x0
+    svv = g.syy - 2 * y0 * g.sy + ni * y0 * y0
+    suv = g.sxy - x0 * g.sy - y0 * g.sx + ni * x0 * y0
+    su, sv, suu, svv, suv = (t.to(f64) for t in (su, sv, suu, svv, suv))
+    nn = n * n
+    A, B, C = n * suu - su * su, n * svv - sv * sv, n * suv - su * sv
+    D = ((A - B) * (A - B) + 4.0 * (C * C)).sqrt()
+    top = A + B + D
+    l1, l2 = top / (2.0 * nn), (A + B - D).clamp(min=0.0) / (2.0 * nn)
+    ecc = torch.where(top > 0, (2.0 * D / torch.where(top > 0, top, torch.ones_like(top))).clamp(max=1.0).sqrt(), torch.zeros_like(top))
+    q = g.quads.to(i64)
+    n1, n2, nd, n3 = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    diag = n1 + n3 + 2 * nd
+    perimeter = n2.to(f64) + diag.to(f64) / math.sqrt(2.0)
+    area = ni.to(f64)
+    box = ((y1 + 1 - y0) * (x1 + 1 - x0)).to(f64)
+    # the sixteen support lines a x + b y <= h of the pixel squares, in angular order, relative to the corner of the bounding box
+    ab = torch.tensor(GEOMETRY_DIRECTIONS, dtype=i64, device=ext.device)
+    a, b = ab[:, 0], ab[:, 1]
+    half = (a.abs() + b.abs()).to(f64) * 0.5
+    corner = a[None] * x0[:, None] + b[None] * y0[:, None]
+    lo, hi = (ext[:, :, 0] - corner).to(f64), (ext[:, :, 1] - corner).to(f64)
+    widths = (hi - lo + 2.0 * half) / (a * a + b * b).to(f64).sqrt()
+    h = torch.cat([hi + half, half - lo], dim=1)                    # [R, 16]
+    a16, b16 = torch.cat([a, -a]).to(f64), torch.cat([b, -b]).to(f64)
+    a_n, b_n, h_n = a16.roll(-1), b16.roll(-1), h.roll(-1, 1)       # every determinant a b' - b a' of consecutive lines is 1
+    px, py = h * b_n - b16 * h_n, a16 * h_n - h * a_n
+    polygon = 0.5 * (px * py.roll(-1, 1) - px.roll(-1, 1) * py).sum(1)
+    one = torch.ones_like(area)
+
+    def f32(t):
+        return torch.where(some, t, torch.zeros_like(t)).to(torch.float32)
+
+    def i32(t):
+        return torch.where(some if t.dim() == 1 else some[:, None], t, torch.zeros_like(t)).to(torch.int32)
+
+    return RegionShape(
+        area=f32(area), centroid_y=f32(y0.to(f64) + sv / n), centroid_x=f32(x0.to(f64) + su / n), var_y=f32(B / nn), var_x=f32(A / nn),
+        cov=f32(C / nn), major_axis=f32(4.0 * l1.sqrt()), minor_axis=f32(4.0 * l2.sqrt()), eccentricity=f32(ecc),
+        orientation=f32(torch.atan2(2.0 * C, A - B) * 0.5), bbox=i32(torch.stack([y0, x0, y1 + 1, x1 + 1], dim=1)), bbox_fill=f32(area / box),
+        perimeter_crack=i32(n1 + n2 + n3 + 2 * nd), perimeter=f32(perimeter),
+        circularity=f32(4.0 * math.pi * area / torch.where(some, perimeter * perimeter, one)), euler4=i32((n1 - n3 + 2 * nd) // 4),
+        euler8=i32((n1 - n3 - 2 * nd) // 4), equivalent_diameter=f32((4.0 * area / math.pi).sqrt()), feret_max=f32(widths.max(1)[0]),
+        feret_min=f32(widths.min(1)[0]), polygon_area=f32(polygon), convexity16=f32(area / torch.where(some, polygon, one)),
+        border=i32(g.border.to(i64)))
+
+
+def _shape_table(shape):
+    """float32 [R, len(SHAPE_FEATURE_NAMES)] of a RegionShape."""
+    s = shape
+    some = (s.area > 0).to(torch.float32)
+    return torch.stack([s.area, s.major_axis, s.minor_axis, s.eccentricity, s.orientation, s.perimeter, s.circularity, s.convexity16,
+                        s.feret_max, s.feret_min, s.bbox_fill, (1 - s.euler8).to(torch.float32) * some,
+                        (s.border > 0).to(torch.float32)], dim=1)
+
+
+def shape_features(labels, kept_labels, max_label=None, within=None):
+    """Shape features per nucleus, to put beside ``nucleus_features``, ``stain_features`` and ``texture_features``: float32
+    [len(kept_labels), 13]; ``SHAPE_FEATURE_NAMES`` names the columns.  labels: 2-D integer instance mask on the GPU; kept_labels: as
+    stain_features -- row k describes label kept_labels[k]; within: as region_geometry.  The columns are ``region_shape``'s area,
+    major_axis, minor_axis, eccentricity, orientation, perimeter, circularity, convexity16, feret_max, feret_min and bbox_fill, then
+    ``holes`` = 1 - euler8 (the holes of a connected nucleus, counted with 4-connected background) and ``touches_border`` = 1 where
+    the nucleus has a pixel on the image frame (its shape is cut: tiled pipelines drop such rows), else 0.  A label without a pixel
+    gives a row of zeros.  Each row describes the pixels of its own label only, also where nuclei touch:
+
+        x = torch.cat([features, stain_features(L, tile, kept, max_label=n), texture_features(L, tile, kept, hi=159, max_label=n),
+                       shape_features(L, kept, max_label=n)], 1)
+
+    Host syncs: the label range unless ``max_label`` is given, and one read that brings the refused pixels and the check of
+    kept_labels: labels or kept_labels outside [0, max_label] raise ValueError."""
+    fn = 'shape_features'
+    _check_image(fn, 'labels', labels, _INT_DTYPES)
+    if not torch.is_tensor(kept_labels) or kept_labels.dtype not in (torch.int32, torch.int64):
+        raise TypeError('%s: kept_labels must be an int32 or int64 tensor' % fn)
+    if kept_labels.dim() != 1 or kept_labels.device != labels.device:
+        raise ValueError('%s: kept_labels must be 1-D and on the device of labels' % fn)
+    geometry, meta, hi = _geometry_tables(fn, labels, max_label, within)
+    table = _shape_table(region_shape(geometry))
+    kept = kept_labels.to(torch.int64)
+    out = table[kept.clamp(0, hi)]
+    refused, bad_kept = torch.stack([meta[0].to(torch.int64), ((kept < 0) | (kept > hi)).sum()]).tolist()      # host sync
+    _refuse_labels(fn, refused, hi)
+    if bad_kept:
+        raise ValueError('%s: %d of kept_labels lie outside [0, %d]' % (fn, bad_kept, hi))
+    return out
+
+
+def clear_border(labels, max_label=None):
+    """``labels`` with every region that has a pixel in the first or last row or column of the image set to 0 (region_geometry's
+    ``border`` > 0): the nuclei a tile cuts.  The other labels keep their values; nothing is renumbered.  Same dtype and shape.
+
+    Host syncs: as region_statistics (the label range unless ``max_label`` is given; the refused pixels)."""
+    geometry, meta, hi = _geometry_tables('clear_border', labels, max_label, None)
+    cut = geometry.border > 0
+    out = torch.where(cut[labels.clamp(0, hi).to(torch.int64)], torch.zeros_like(labels), labels)
+    _refuse_labels('clear_border', int(meta.item()), hi)           # host sync: the refused pixels
     return out
 
 

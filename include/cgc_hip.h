@@ -83,8 +83,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *      them): cgc_region_tile_side, cgc_region_table_slots, cgc_region_ws_bytes, cgc_region_moments, cgc_region_histogram,
  *      cgc_region_quantiles
  *  24: region co-occurrence (per label value and offset: the grey-level co-occurrence table of a uint8 plane over pairs of pixels of
- *      one region): cgc_region_cooc_max_offset, cgc_region_cooc_max_offsets, cgc_region_cooccurrence */
-#define CGC_ABI_VERSION 24
+ *      one region): cgc_region_cooc_max_offset, cgc_region_cooc_max_offsets, cgc_region_cooccurrence
+ *  25: region geometry (per label value: count, coordinate sums, extents in eight directions, bit-quad counts, pixels on the image
+ *      frame): cgc_region_geometry_max_side, cgc_region_geometry */
+#define CGC_ABI_VERSION 25
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -522,6 +524,26 @@ int cgc_region_cooc_max_offsets(void);
 int cgc_region_cooccurrence(const int* labels, const uint8_t* values, const void* within_or_null, int within_bytes, int H, int W,
                             int max_label, const uint8_t* lut256_host, int levels, const int* offsets_host, int noff, int symmetric,
                             int* tables, int* meta, cgc_stream_t stream);
+
+/* ---- F19 (beside F17, csrc/region.hip): the shape of every region of a label image, from the labels alone.  The contract item by
+ * item: cgc-net_amd/kernels.py KernelSpec.region_geometry.  labels, max_label, within_or_null, "a pixel belongs to row L", the refused
+ * pixels and *meta as F17.  H, W <= cgc_region_geometry_max_side() = 32767 (sum x^2 over 2^31 pixels fits int64) and (H + 1)(W + 1) <
+ * 2^31 (a quad count fits int32).  Per label value 0 .. max_label, R = max_label + 1 rows:
+ *   count   int32 [R]         the row's pixels
+ *   sums    int64 [5, R]      sy, sx, syy, sxy, sxx over the row's pixels, y = row and x = column of the image
+ *   extents int32 [R, 8, 2]   minimum and maximum of a x + b y over the row's pixel centres, (a, b) = (1,0) (2,1) (1,1) (1,2) (0,1)
+ *                             (-1,2) (-1,1) (-2,1); (1,0) and (0,1) are the bounding box
+ *   quads   int32 [R, 4]      n1, n2, nd, n3: over the 2 x 2 windows with top-left corner (y, x), y in -1 .. H-1, x in -1 .. W-1
+ *                             (positions outside the image belong to no row), the windows in which the row has one pixel, two that
+ *                             share an edge, the two of a diagonal, three; a window adds to every row that occurs in it
+ *   border  int32 [R]         the row's pixels with y in {0, H-1} or x in {0, W-1}
+ * An empty row has zeros everywhere, extents (0, 0).  H * W = 0: empty rows only.  What finds no slot in a tile's LDS table goes to
+ * the tables directly: exact for every input; integer adds, minima and maxima only, bit-identical from call to call.
+ * Bad dims, max_label, within_bytes, a side above 32767, (H + 1)(W + 1) >= 2^31 or a null pointer where one is needed: CGC_EINVAL,
+ * nothing launched. */
+int cgc_region_geometry_max_side(void);
+int cgc_region_geometry(const int* labels, const void* within_or_null, int within_bytes, int H, int W, int max_label, int* count,
+                        int64_t* sums, int* extents, int* quads, int* border, int* meta, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
