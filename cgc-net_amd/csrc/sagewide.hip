@@ -693,7 +693,8 @@ extern "C" int cgc_sage_wide_fwd(const float* agg, int lda, const float* W, cons
     }
     const int ntw8 = F <= 8 * 5 * 32 ? 5 : 7, Fp = 8 * ntw8 * 32;
     const size_t lds8 = sizeof(float) * ((size_t)2 * ks * Fp + 512 + 256);
-    if (F <= 8 * 7 * 32 && lds8 <= 156 * 1024 && n >= 64 && (long long)n * ldh * 4 < (1LL << 31)) {
+    // ks = 16 never fits: 4 * (2 * 16 * 1280 + 768) = 166912 bytes > 156 KB at the smallest Fp, so K in 21..32 always takes k_sage_wide_fwd
+    if (ks <= 10 && F <= 8 * 7 * 32 && lds8 <= 156 * 1024 && n >= 64 && (long long)n * ldh * 4 < (1LL << 31)) {
       int wg8 = row_tiles < 256 ? row_tiles : 256;
       if (stats && wg8 > cap) wg8 = cap > 0 ? cap : 1;
 #define SW8_ONE(KS_, NTW_, ACT_)                                                                                                       \
@@ -711,9 +712,9 @@ extern "C" int cgc_sage_wide_fwd(const float* agg, int lda, const float* W, cons
     else SW8_ONE(KS_, NTW_, CGC_ACT_IDENTITY);                                                                                         \
   } while (0)
       if (ntw8 == 5) {
-        if (ks == 8) SW8_LAUNCH(8, 5); else if (ks == 10) SW8_LAUNCH(10, 5); else SW8_LAUNCH(16, 5);
+        if (ks == 8) SW8_LAUNCH(8, 5); else SW8_LAUNCH(10, 5);
       } else {
-        if (ks == 8) SW8_LAUNCH(8, 7); else if (ks == 10) SW8_LAUNCH(10, 7); else SW8_LAUNCH(16, 7);
+        if (ks == 8) SW8_LAUNCH(8, 7); else SW8_LAUNCH(10, 7);
       }
 #undef SW8_LAUNCH
 #undef SW8_ONE

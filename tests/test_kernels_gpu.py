@@ -821,7 +821,8 @@ def test_wide_sage_row_norms_from_the_quadratic_form():
 @pytest.mark.parametrize('mode,act,normalize', [(2, 1, True), (1, 3, True), (0, 2, False), (2, 2, True)])
 def test_fused_narrow_sage_backward(n, fin, F, mode, act, normalize):
     """cgc_sage_narrow_bwd (BN / activation / L2 backward + d agg + d W + d b in one kernel, dh never written) against the
-    composition bn_act_l2_bwd -> matmuls of the contract; strided dy / agg windows, a zero row (norm clamp), all BN modes."""
+    composition bn_act_l2_bwd -> matmuls of the contract; strided dy / agg windows, a zero row (norm clamp), all BN modes.  With that
+    row its 1e12 factor sets the scale of `dW | db` here: tests/test_sage_fp64_gpu.py pins them element by element without it."""
     k = hip()
     h = rnd(n, F, seed=n + F)
     h[min(3, n - 1)] = 0.0
