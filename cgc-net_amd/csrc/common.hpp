@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/cgc_hip.h"
 
 #define CGC_WAVE 64
@@ -81,6 +83,17 @@ __device__ __forceinline__ float act_bwd(float x, int act) {  // d act / d x eva
     case CGC_ACT_ELU: return x > 0.f ? 1.f : expf(x);
     case CGC_ACT_LEAKYRELU: return x > 0.f ? 1.f : 0.01f;
     default: return 1.f;
+  }
+}
+
+// the run-time activation code lifted into a compile-time constant: f(std::integral_constant<int, ACT>()), outside the caller's loops
+template <class F>
+__host__ __device__ __forceinline__ void with_act(int act, F&& f) {
+  switch (act) {
+    case CGC_ACT_RELU: f(std::integral_constant<int, CGC_ACT_RELU>()); break;
+    case CGC_ACT_ELU: f(std::integral_constant<int, CGC_ACT_ELU>()); break;
+    case CGC_ACT_LEAKYRELU: f(std::integral_constant<int, CGC_ACT_LEAKYRELU>()); break;
+    default: f(std::integral_constant<int, CGC_ACT_IDENTITY>()); break;
   }
 }
 

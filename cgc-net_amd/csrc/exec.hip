@@ -83,8 +83,6 @@ extern "C" int cgc_transpose(const float* src, int lds, int rows, int cols, floa
   return 0;
 }
 
-int reduce_batch_sum_rows(const float* ws, float* out, int parts, int rows, int width, int ldo, float beta, hipStream_t stream);   // gemm.hip
-
 // ------------------------------------------------------------------------------------------------ host-side plumbing
 namespace {
 

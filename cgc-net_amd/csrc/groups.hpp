@@ -41,4 +41,9 @@ int sage_narrow_bwd_groups(const SnBwdPtrs* g, float* const* dwdb, int ng, int l
 int bn_act_apply_groups(const BnApplyPtrs* g, int ng, int n, int F, int act, int ldy, hipStream_t stream);
 int bn_bwd_reduce_groups(const BnRedPtrs* g, float* const* sums, int ng, int ldy, int n, int F, int act, hipStream_t stream);
 int launch_stats_finalize_groups(const StatsFinPtrs* g, int ng, int slots, int F, double count, hipStream_t stream);
-int launch_reduce_slots_f32_pair(const float* ws0, float* out0, const float* ws1, float* out1, int ng, int slots, int width, hipStream_t stream);
+int launch_stats_finalize(const float* ws, int slots, int F, double count, float eps, float momentum, float* running_mean,
+                          float* running_var, float* mean, float* istd, int64_t* nbt, hipStream_t stream);
+// out_i[c] = sum over the slots of ws_i[slot * width + c] for ng = 1 or 2 slot areas (rowops.hip; instantiated there for float)
+template <typename OUT, typename IN>
+int launch_reduce_slots(const IN* ws0, OUT* out0, const IN* ws1, OUT* out1, int ng, int slots, int width, hipStream_t stream);
+int reduce_batch_sum_rows(const float* ws, float* out, int parts, int rows, int width, int ldo, float beta, hipStream_t stream);   // gemm.hip

@@ -104,72 +104,48 @@ __device__ __forceinline__ void col_reduce_store_f64(double (&acc)[2][MAXJ][VEC]
 // load rounds (slots / 128 of them; it was slots / 64 with 8 groups) and little else -- 6 us -> 4 us for the ~450-slot
 // reductions of the narrow layers, of which a step has ~45.
 #define RS_GROUPS 32
-template <typename OUT, typename IN = float>
-__global__ __launch_bounds__(32 * RS_GROUPS) void k_reduce_slots(const IN* __restrict__ ws, int slots, int width, OUT* __restrict__ out) {
+// this thread's share of column `col` of the slots: slot rows grp, grp + RS_GROUPS, ... (slot stride in elements).  (Base and column
+// apart, as ints: handed over as one pointer, the column's sign extension stays live across the loop -- one more VGPR in <float>.)
+template <typename IN>
+__device__ __forceinline__ double slot_col_sum(const IN* __restrict__ ws, int col, int slots, int stride) {
+  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  int k = threadIdx.x >> 5;
+  for (; k + 3 * RS_GROUPS < slots; k += 4 * RS_GROUPS) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) a[u] += (double)ws[(size_t)(k + RS_GROUPS * u) * stride + col];
+  }
+  for (; k < slots; k += RS_GROUPS) a[0] += (double)ws[(size_t)k * stride + col];
+  return (a[0] + a[1]) + (a[2] + a[3]);
+}
+// the RS_GROUPS shares of column cl, folded in a fixed order
+__device__ __forceinline__ double slot_part_fold(const double (&part)[RS_GROUPS][32], int cl) {
+  double t[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int g = 0; g < RS_GROUPS; g += 4) { t[0] += part[g][cl]; t[1] += part[g + 1][cl]; t[2] += part[g + 2][cl]; t[3] += part[g + 3][cl]; }
+  return (t[0] + t[1]) + (t[2] + t[3]);
+}
+// up to two slot areas in one launch (blockIdx.y picks the pair)
+template <typename OUT, typename IN>
+__global__ __launch_bounds__(32 * RS_GROUPS) void k_reduce_slots(const IN* __restrict__ ws0, OUT* __restrict__ out0, const IN* __restrict__ ws1,
+                                                                OUT* __restrict__ out1, int slots, int width) {
+  const IN* __restrict__ ws = blockIdx.y ? ws1 : ws0;
+  OUT* __restrict__ out = blockIdx.y ? out1 : out0;
   __shared__ double part[RS_GROUPS][32];
   const int cl = threadIdx.x & 31, grp = threadIdx.x >> 5;
   const int c = blockIdx.x * 32 + cl;
   double s = 0.0;
-  if (c < width) {
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    int k = grp;
-    for (; k + 3 * RS_GROUPS < slots; k += 4 * RS_GROUPS) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) a[u] += (double)ws[(size_t)(k + RS_GROUPS * u) * width + c];
-    }
-    for (; k < slots; k += RS_GROUPS) a[0] += (double)ws[(size_t)k * width + c];
-    s = (a[0] + a[1]) + (a[2] + a[3]);
-  }
+  if (c < width) s = slot_col_sum(ws, c, slots, width);
   part[grp][cl] = s;
   __syncthreads();
-  if (grp == 0 && c < width) {
-    double t[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int g = 0; g < RS_GROUPS; g += 4) { t[0] += part[g][cl]; t[1] += part[g + 1][cl]; t[2] += part[g + 2][cl]; t[3] += part[g + 3][cl]; }
-    out[c] = (OUT)((t[0] + t[1]) + (t[2] + t[3]));
-  }
+  if (grp == 0 && c < width) out[c] = (OUT)slot_part_fold(part, cl);
 }
-#define REDUCE_SLOTS_GRID(width) dim3(ceil_div((width), 32))
-
-// the same for two slot areas in one launch (blockIdx.y picks the pair)
-__global__ __launch_bounds__(32 * RS_GROUPS) void k_reduce_slots_pair(const float* __restrict__ ws0, float* __restrict__ out0,
-                                                                     const float* __restrict__ ws1, float* __restrict__ out1, int slots, int width) {
-  const float* __restrict__ ws = blockIdx.y ? ws1 : ws0;
-  float* __restrict__ out = blockIdx.y ? out1 : out0;
-  __shared__ double part[RS_GROUPS][32];
-  const int cl = threadIdx.x & 31, grp = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + cl;
-  double s = 0.0;
-  if (c < width) {
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    int k = grp;
-    for (; k + 3 * RS_GROUPS < slots; k += 4 * RS_GROUPS) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) a[u] += (double)ws[(size_t)(k + RS_GROUPS * u) * width + c];
-    }
-    for (; k < slots; k += RS_GROUPS) a[0] += (double)ws[(size_t)k * width + c];
-    s = (a[0] + a[1]) + (a[2] + a[3]);
-  }
-  part[grp][cl] = s;
-  __syncthreads();
-  if (grp == 0 && c < width) {
-    double t[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int g = 0; g < RS_GROUPS; g += 4) { t[0] += part[g][cl]; t[1] += part[g + 1][cl]; t[2] += part[g + 2][cl]; t[3] += part[g + 3][cl]; }
-    out[c] = (float)((t[0] + t[1]) + (t[2] + t[3]));
-  }
-}
-int launch_reduce_slots_f32_pair(const float* ws0, float* out0, const float* ws1, float* out1, int ng, int slots, int width, hipStream_t stream) {
-  hipLaunchKernelGGL(k_reduce_slots_pair, dim3(ceil_div(width, 32), ng), dim3(32 * RS_GROUPS), 0, stream, ws0, out0, ws1, out1, slots, width);
+template <typename OUT, typename IN>
+int launch_reduce_slots(const IN* ws0, OUT* out0, const IN* ws1, OUT* out1, int ng, int slots, int width, hipStream_t stream) {
+  hipLaunchKernelGGL((k_reduce_slots<OUT, IN>), dim3(ceil_div(width, 32), ng), dim3(32 * RS_GROUPS), 0, stream, ws0, out0, ws1, out1, slots, width);
   CGC_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
-
-int launch_reduce_slots_f32(const float* ws, int slots, int width, float* out, hipStream_t stream) {
-  hipLaunchKernelGGL(k_reduce_slots<float>, REDUCE_SLOTS_GRID(width), dim3(32 * RS_GROUPS), 0, stream, ws, slots, width, out);
-  CGC_RETURN_IF_LAUNCH_FAILED();
-  return 0;
-}
+template int launch_reduce_slots<float, float>(const float*, float*, const float*, float*, int, int, int, hipStream_t);   // sagenarrow.hip
 
 struct ColCfg {
   int vec, maxj, lpr, blocks;
@@ -197,29 +173,6 @@ static ColCfg col_cfg(int n, int F, bool vec_ok) {
   return c;
 }
 
-#define DISPATCH_COL(KERNEL, cfg, smem_bytes, stream, ...)                                                   \
-  do {                                                                                                       \
-    dim3 g__((cfg).blocks), b__(CGC_BLOCK);                                                                  \
-    if ((cfg).vec == 4) {                                                                                    \
-      switch ((cfg).maxj) {                                                                                  \
-        case 1: hipLaunchKernelGGL((KERNEL<4, 1>), g__, b__, smem_bytes, stream, __VA_ARGS__); break;        \
-        case 2: hipLaunchKernelGGL((KERNEL<4, 2>), g__, b__, smem_bytes, stream, __VA_ARGS__); break;        \
-        case 4: hipLaunchKernelGGL((KERNEL<4, 4>), g__, b__, smem_bytes, stream, __VA_ARGS__); break;        \
-        case 5: hipLaunchKernelGGL((KERNEL<4, 5>), g__, b__, smem_bytes, stream, __VA_ARGS__); break;        \
-        default: hipLaunchKernelGGL((KERNEL<4, 8>), g__, b__, smem_bytes, stream, __VA_ARGS__); break;       \
-      }                                                                                                      \
-    } else {                                                                                                 \
-      switch ((cfg).maxj) {                                                                                  \
-        case 1: hipLaunchKernelGGL((KERNEL<1, 1>), g__, b__, smem_bytes, stream, __VA_ARGS__); break;        \
-        case 2: hipLaunchKernelGGL((KERNEL<1, 2>), g__, b__, smem_bytes, stream, __VA_ARGS__); break;        \
-        case 4: hipLaunchKernelGGL((KERNEL<1, 4>), g__, b__, smem_bytes, stream, __VA_ARGS__); break;        \
-        case 8: hipLaunchKernelGGL((KERNEL<1, 8>), g__, b__, smem_bytes, stream, __VA_ARGS__); break;        \
-        case 16: hipLaunchKernelGGL((KERNEL<1, 16>), g__, b__, smem_bytes, stream, __VA_ARGS__); break;      \
-        default: hipLaunchKernelGGL((KERNEL<1, 32>), g__, b__, smem_bytes, stream, __VA_ARGS__); break;      \
-      }                                                                                                      \
-    }                                                                                                        \
-  } while (0)
-
 #define DISPATCH_COL_Y(KERNEL, cfg, ny, smem_bytes, stream, ...)                                                   \
   do {                                                                                                       \
     dim3 g__((cfg).blocks, (ny)), b__(CGC_BLOCK);                                                                    \
@@ -242,7 +195,7 @@ static ColCfg col_cfg(int n, int F, bool vec_ok) {
       }                                                                                                      \
     }                                                                                                        \
   } while (0)
-
+#define DISPATCH_COL(KERNEL, cfg, smem_bytes, stream, ...) DISPATCH_COL_Y(KERNEL, cfg, 1, smem_bytes, stream, __VA_ARGS__)
 
 extern "C" int cgc_stats_blocks(int n, int F) {
   (void)F;
@@ -310,24 +263,33 @@ __global__ __launch_bounds__(256) void k_l2norm_act_stats(const float* __restric
     col_reduce_store_f64<VEC, MAXJ>(acc, F, lpr, reinterpret_cast<double*>(smem), reinterpret_cast<double*>(ws) + (size_t)blockIdx.x * 2 * F);
 }
 
+// the launch behind cgc_l2norm_act_stats / cgc_l2norm_act_bn (n > 0, F > 0): returns the number of slots the kernel fills, or 0 with
+// *err set when nothing ran
+static int launch_l2norm_act_stats(const float* h, int n, int F, int normalize, int act, float* hn, float* rinv, float* ws,
+                                   hipStream_t stream, int* err) {
+  const bool vec_ok = (F % 4 == 0) && aligned16(h) && aligned16(hn);
+  ColCfg cfg = col_cfg(n, F, vec_ok);
+  *err = CGC_EINVAL;
+  if (!cfg.ok) return 0;
+  const size_t smem = sizeof(float) * 3 * 2 * F;
+  DISPATCH_COL(k_l2norm_act_stats, cfg, smem, stream, h, n, F, cfg.lpr, normalize, act, hn, rinv, ws);
+  *err = (int)hipGetLastError();
+  return *err == (int)hipSuccess ? cfg.blocks : 0;
+}
+
 extern "C" int cgc_l2norm_act_stats(const float* h, int n, int F, int normalize, int act, float* hn, float* rinv,
                                     double* stats, float* ws, cgc_stream_t stream) {
   if (n <= 0 || F <= 0) {
     if (stats && F > 0) (void)hipMemsetAsync(stats, 0, sizeof(double) * 2 * F, as_stream(stream));
     return 0;
   }
-  const bool vec_ok = (F % 4 == 0) && aligned16(h) && aligned16(hn);
-  ColCfg cfg = col_cfg(n, F, vec_ok);
-  if (!cfg.ok) return CGC_EINVAL;
-  float* wsp = stats ? ws : nullptr;
   if (stats && !ws) return CGC_EINVAL;
-  const size_t smem = sizeof(float) * 3 * 2 * F;
-  DISPATCH_COL(k_l2norm_act_stats, cfg, smem, as_stream(stream), h, n, F, cfg.lpr, normalize, act, hn, rinv, wsp);
-  CGC_RETURN_IF_LAUNCH_FAILED();
+  int err = 0;
+  const int slots = launch_l2norm_act_stats(h, n, F, normalize, act, hn, rinv, stats ? ws : nullptr, as_stream(stream), &err);
+  if (slots == 0) return err;
   if (stats) {
-    hipLaunchKernelGGL((k_reduce_slots<double, double>), REDUCE_SLOTS_GRID(2 * F), dim3(32 * RS_GROUPS), 0, as_stream(stream),
-                       reinterpret_cast<const double*>(ws), cfg.blocks, 2 * F, stats);
-    CGC_RETURN_IF_LAUNCH_FAILED();
+    const double* wsd = reinterpret_cast<const double*>(ws);
+    return launch_reduce_slots(wsd, stats, wsd, stats, 1, slots, 2 * F, as_stream(stream));
   }
   return 0;
 }
@@ -335,14 +297,11 @@ extern "C" int cgc_l2norm_act_stats(const float* h, int n, int F, int normalize,
 // ------------------------------------------------------------------------------------------------
 // BatchNorm statistics -> mean / inverse std (+ running statistics)
 // ------------------------------------------------------------------------------------------------
-__global__ void k_bn_finalize(const double* __restrict__ stats, int F, double count, float eps, float momentum,
-                              float* running_mean, float* running_var, float* __restrict__ mean, float* __restrict__ istd,
-                              long long* nbt) {
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f == 0 && nbt != nullptr) *nbt += 1;       // nn.BatchNorm1d's num_batches_tracked
-  if (f >= F) return;
-  const double m = stats[f] / count;
-  double var = stats[F + f] / count - m * m;   // biased; the padded zero rows are part of `count`
+// column f from its sums s0 = sum o, s1 = sum o^2 over `count` rows
+__device__ __forceinline__ void bn_finalize_col(double s0, double s1, double count, float eps, float momentum, int f, float* running_mean,
+                                                float* running_var, float* __restrict__ mean, float* __restrict__ istd) {
+  const double m = s0 / count;
+  double var = s1 / count - m * m;             // biased; the padded zero rows are part of `count`
   if (var < 0.0) var = 0.0;
   mean[f] = (float)m;
   istd[f] = (float)(1.0 / sqrt(var + (double)eps));
@@ -351,6 +310,15 @@ __global__ void k_bn_finalize(const double* __restrict__ stats, int F, double co
     running_mean[f] = (1.f - momentum) * running_mean[f] + momentum * (float)m;
     running_var[f] = (1.f - momentum) * running_var[f] + momentum * (float)unbiased;
   }
+}
+
+__global__ void k_bn_finalize(const double* __restrict__ stats, int F, double count, float eps, float momentum,
+                              float* running_mean, float* running_var, float* __restrict__ mean, float* __restrict__ istd,
+                              long long* nbt) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f == 0 && nbt != nullptr) *nbt += 1;       // nn.BatchNorm1d's num_batches_tracked
+  if (f >= F) return;
+  bn_finalize_col(stats[f], stats[F + f], count, eps, momentum, f, running_mean, running_var, mean, istd);
 }
 
 extern "C" int cgc_bn_finalize(const double* stats, int F, double count, float eps, float momentum, float* running_mean,
@@ -378,8 +346,8 @@ extern "C" int cgc_bn_running_stats(const float* running_mean, const float* runn
   return 0;
 }
 
-// second stage of the statistics + finalize in one kernel: the column sums of the slots (same grouping and order as
-// k_reduce_slots<double>, so the same bits) and mean / istd / running statistics / num_batches_tracked of k_bn_finalize
+// second stage of the statistics + finalize in one kernel: the column sums of the slots (the helpers of k_reduce_slots: the same
+// grouping and order, so the same bits) and mean / istd / running statistics / num_batches_tracked of k_bn_finalize
 __global__ __launch_bounds__(32 * RS_GROUPS) void k_stats_finalize(const StatsFinPtrs p0, const StatsFinPtrs p1, int slots, int F, double count) {
   const StatsFinPtrs& p = blockIdx.y ? p1 : p0;
   const double* __restrict__ ws = reinterpret_cast<const double*>(p.ws);      // slots of doubles: [sum o | sum o^2] per slot
@@ -394,40 +362,11 @@ __global__ __launch_bounds__(32 * RS_GROUPS) void k_stats_finalize(const StatsFi
   const int f = blockIdx.x * 32 + cl;
   if (blockIdx.x == 0 && threadIdx.x == 0 && nbt != nullptr) *nbt += 1;       // nn.BatchNorm1d's num_batches_tracked
 #pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    double s = 0.0;
-    if (f < F) {
-      const double* col = ws + (size_t)q * F + f;
-      const size_t width = 2 * (size_t)F;
-      double a[4] = {0.0, 0.0, 0.0, 0.0};
-      int k = grp;
-      for (; k + 3 * RS_GROUPS < slots; k += 4 * RS_GROUPS) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) a[u] += col[(size_t)(k + RS_GROUPS * u) * width];
-      }
-      for (; k < slots; k += RS_GROUPS) a[0] += col[(size_t)k * width];
-      s = (a[0] + a[1]) + (a[2] + a[3]);
-    }
-    part[q][grp][cl] = s;
-  }
+  for (int q = 0; q < 2; ++q) part[q][grp][cl] = f < F ? slot_col_sum(ws, q * F + f, slots, 2 * F) : 0.0;
   __syncthreads();
   if (grp != 0 || f >= F) return;
-  double t0[4] = {0.0, 0.0, 0.0, 0.0}, t1[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int g = 0; g < RS_GROUPS; g += 4)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { t0[u] += part[0][g + u][cl]; t1[u] += part[1][g + u][cl]; }
-  const double s0 = (t0[0] + t0[1]) + (t0[2] + t0[3]), s1 = (t1[0] + t1[1]) + (t1[2] + t1[3]);
-  const double m = s0 / count;
-  double var = s1 / count - m * m;             // biased; the padded zero rows are part of `count`
-  if (var < 0.0) var = 0.0;
-  mean[f] = (float)m;
-  istd[f] = (float)(1.0 / sqrt(var + (double)eps));
-  if (running_mean != nullptr) {
-    const double unbiased = var * count / (count > 1.0 ? count - 1.0 : 1.0);
-    running_mean[f] = (1.f - momentum) * running_mean[f] + momentum * (float)m;
-    running_var[f] = (1.f - momentum) * running_var[f] + momentum * (float)unbiased;
-  }
+  const double s0 = slot_part_fold(part[0], cl), s1 = slot_part_fold(part[1], cl);
+  bn_finalize_col(s0, s1, count, eps, momentum, f, running_mean, running_var, mean, istd);
 }
 
 int launch_stats_finalize_groups(const StatsFinPtrs* g, int ng, int slots, int F, double count, hipStream_t stream) {
@@ -451,13 +390,9 @@ extern "C" int cgc_l2norm_act_bn(const float* h, int n, int F, int normalize, in
   if (ws == nullptr || mean == nullptr || istd == nullptr) return CGC_EINVAL;
   int slots = 0;
   if (n > 0) {
-    const bool vec_ok = (F % 4 == 0) && aligned16(h) && aligned16(hn);
-    ColCfg cfg = col_cfg(n, F, vec_ok);
-    if (!cfg.ok) return CGC_EINVAL;
-    const size_t smem = sizeof(float) * 3 * 2 * F;
-    DISPATCH_COL(k_l2norm_act_stats, cfg, smem, as_stream(stream), h, n, F, cfg.lpr, normalize, act, hn, rinv, ws);
-    CGC_RETURN_IF_LAUNCH_FAILED();
-    slots = cfg.blocks;
+    int err = 0;
+    slots = launch_l2norm_act_stats(h, n, F, normalize, act, hn, rinv, ws, as_stream(stream), &err);
+    if (slots == 0) return err;
   }
   return launch_stats_finalize(ws, slots, F, count, eps, momentum, running_mean, running_var, mean, istd, num_batches_tracked, as_stream(stream));
 }
@@ -528,12 +463,7 @@ __global__ __launch_bounds__(256) void k_bn_act_apply(const BnApplyPtrs p0, cons
       }
     }
   };
-  switch (act) {
-    case CGC_ACT_RELU: rows(std::integral_constant<int, CGC_ACT_RELU>()); break;
-    case CGC_ACT_ELU: rows(std::integral_constant<int, CGC_ACT_ELU>()); break;
-    case CGC_ACT_LEAKYRELU: rows(std::integral_constant<int, CGC_ACT_LEAKYRELU>()); break;
-    default: rows(std::integral_constant<int, CGC_ACT_IDENTITY>()); break;
-  }
+  with_act(act, rows);
 }
 
 // the same result written to a second destination as well (y2 [n, F], row stride ldy2; NULL: none): a layer's output goes into the
@@ -621,7 +551,7 @@ int bn_bwd_reduce_groups(const BnRedPtrs* g, float* const* sums, int ng, int ldy
   const size_t smem = sizeof(float) * 3 * 2 * F;
   DISPATCH_COL_Y(k_bn_bwd_reduce, cfg, ng, smem, stream, g[0], g[ng - 1], ldy, n, F, cfg.lpr, act);
   CGC_RETURN_IF_LAUNCH_FAILED();
-  return launch_reduce_slots_f32_pair(g[0].ws, sums[0], g[ng - 1].ws, sums[ng - 1], ng, cfg.blocks, 2 * F, stream);
+  return launch_reduce_slots<float, float>(g[0].ws, sums[0], g[ng - 1].ws, sums[ng - 1], ng, cfg.blocks, 2 * F, stream);
 }
 extern "C" int cgc_bn_bwd_reduce(const float* dy, int ldy, const float* hn, int n, int F, int act, const float* mean,
                                  const float* istd, float* sums, float* ws, cgc_stream_t stream) {
@@ -793,10 +723,7 @@ extern "C" int cgc_bn_act_l2_bwd(const float* dy, int ldy, const float* hn, cons
   DISPATCH_COL(k_bn_act_l2_bwd, cfg, smem, as_stream(stream), dy, ldy, hn, rinv, n, F, cfg.lpr, act, normalize, mode, mean, istd,
                gamma, sums, inv_count, dh, dh_colsum ? ws : (float*)nullptr);
   CGC_RETURN_IF_LAUNCH_FAILED();
-  if (dh_colsum) {
-    hipLaunchKernelGGL(k_reduce_slots<float>, REDUCE_SLOTS_GRID(F), dim3(32 * RS_GROUPS), 0, as_stream(stream), ws, cfg.blocks, F, dh_colsum);
-    CGC_RETURN_IF_LAUNCH_FAILED();
-  }
+  if (dh_colsum) return launch_reduce_slots<float, float>(ws, dh_colsum, ws, dh_colsum, 1, cfg.blocks, F, as_stream(stream));
   return 0;
 }
 
@@ -842,9 +769,7 @@ extern "C" int cgc_colsum(const float* x, int ld, int n, int F, float* out, floa
   const size_t smem = sizeof(float) * 3 * F;
   DISPATCH_COL(k_colsum, cfg, smem, as_stream(stream), x, ld, n, F, cfg.lpr, ws);
   CGC_RETURN_IF_LAUNCH_FAILED();
-  hipLaunchKernelGGL(k_reduce_slots<float>, REDUCE_SLOTS_GRID(F), dim3(32 * RS_GROUPS), 0, as_stream(stream), ws, cfg.blocks, F, out);
-  CGC_RETURN_IF_LAUNCH_FAILED();
-  return 0;
+  return launch_reduce_slots<float, float>(ws, out, ws, out, 1, cfg.blocks, F, as_stream(stream));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1023,10 +948,7 @@ extern "C" int cgc_softmax_bwd(const float* S, const float* dS, int n, int C, in
   const size_t smem = dx_colsum ? sizeof(float) * 3 * C : 0;
   DISPATCH_COL(k_softmax_bwd, cfg, smem, as_stream(stream), S, dS, n, C, ld, cfg.lpr, dx, dx_colsum ? ws : (float*)nullptr);
   CGC_RETURN_IF_LAUNCH_FAILED();
-  if (dx_colsum) {
-    hipLaunchKernelGGL(k_reduce_slots<float>, REDUCE_SLOTS_GRID(C), dim3(32 * RS_GROUPS), 0, as_stream(stream), ws, cfg.blocks, C, dx_colsum);
-    CGC_RETURN_IF_LAUNCH_FAILED();
-  }
+  if (dx_colsum) return launch_reduce_slots<float, float>(ws, dx_colsum, ws, dx_colsum, 1, cfg.blocks, C, as_stream(stream));
   return 0;
 }
 
@@ -1130,6 +1052,9 @@ extern "C" int cgc_segment_max_bwd(const float* dout, const int* arg, int B, int
 // ------------------------------------------------------------------------------------------------
 // dense adjacency (levels 2-3): A / clamp(rowsum,1)   and   _re_norm_adj, each with its backward
 // ------------------------------------------------------------------------------------------------
+// (These two are k_adj_prep_fwd / k_adj_prep_bwd with p < 0 term for term, and stay kernels of their own: through k_adj_prep_fwd the
+// forward gives the same bits but measured 83.6 / 83.3 us against 81.9 / 81.4 on [32, 1140, 1140] (36 VGPRs instead of 26); in k_adj_prep_bwd
+// <dOut, An> compiles to an FMA chain, here to packed multiplies (v_pk_mul_f32) and additions -- dA differs in the last bit.)
 template <int VEC>
 __global__ __launch_bounds__(256) void k_dense_rownorm_fwd(const float* __restrict__ A, int R, int C, int lpr, float* __restrict__ out,
                                                            float* __restrict__ invd, float* __restrict__ ge1) {

@@ -162,8 +162,6 @@ __global__ __launch_bounds__(256) void k_sage_narrow_bwd(const SnBwdPtrs p0, con
   }
 }
 
-int launch_reduce_slots_f32(const float* ws, int slots, int width, float* out, hipStream_t stream);   // rowops.hip
-
 static int sn_grid(int n) {
   const int tiles = ceil_div(n, 32);
   int g = ceil_div(tiles, 4);
@@ -188,21 +186,17 @@ int sage_narrow_bwd_groups(const SnBwdPtrs* g, float* const* dwdb, int ng, int l
   const float inv_count = (float)(1.0 / count);
   const int fs = (F + 1) / 2;
   const SnBwdPtrs& g1 = g[ng - 1];
-#define SN_LAUNCH(FS_, ACT_)                                                                                                       \
-  hipLaunchKernelGGL((k_sage_narrow_bwd<FS_, ACT_>), dim3(grid, ng), dim3(256), 0, st, g[0], g1, ldy, n, F, act, normalize, mode, inv_count, \
-                     lda, fin, ldd, tiles)
-#define SN_ACT(FS_)                                                                                        \
-  switch (act) {                                                                                           \
-    case CGC_ACT_RELU: SN_LAUNCH(FS_, CGC_ACT_RELU); break;                                                \
-    case CGC_ACT_ELU: SN_LAUNCH(FS_, CGC_ACT_ELU); break;                                                  \
-    case CGC_ACT_LEAKYRELU: SN_LAUNCH(FS_, CGC_ACT_LEAKYRELU); break;                                      \
-    default: SN_LAUNCH(FS_, CGC_ACT_IDENTITY); break;                                                      \
-  }
-  if (fs <= 8) { SN_ACT(8); } else if (fs <= 10) { SN_ACT(10); } else { SN_ACT(16); }
-#undef SN_ACT
-#undef SN_LAUNCH
+  auto launch = [&](auto fs_c) {
+    with_act(act, [&](auto act_c) {
+      hipLaunchKernelGGL((k_sage_narrow_bwd<decltype(fs_c)::value, decltype(act_c)::value>), dim3(grid, ng), dim3(256), 0, st, g[0], g1, ldy, n,
+                         F, act, normalize, mode, inv_count, lda, fin, ldd, tiles);
+    });
+  };
+  if (fs <= 8) launch(std::integral_constant<int, 8>());
+  else if (fs <= 10) launch(std::integral_constant<int, 10>());
+  else launch(std::integral_constant<int, 16>());
   CGC_RETURN_IF_LAUNCH_FAILED();
-  return launch_reduce_slots_f32_pair(g[0].ws, dwdb[0], g1.ws, dwdb[ng - 1], ng, grid, width, st);
+  return launch_reduce_slots<float, float>(g[0].ws, dwdb[0], g1.ws, dwdb[ng - 1], ng, grid, width, st);
 }
 
 // dy [n,F] (row stride ldy), hn [n,F], rinv [n], BatchNorm vectors and sums [2,F] exactly as cgc_bn_act_l2_bwd (mode 0 / 1 / 2);
@@ -317,7 +311,6 @@ __global__ __launch_bounds__(256) void k_sage_narrow_fwd(const SnFwdPtrs p0, con
   }
 }
 
-extern "C" int cgc_stats_blocks(int n, int F);
 // hn = l2norm(agg W + bias) (+ BatchNorm statistics) for up to two layers of equal shape in one launch each
 int sage_narrow_fwd_groups(const SnFwdPtrs* g, const SnFwdBn* bn, int ng, int lda, int n, int K, int F, int normalize, int act, int stats,
                            double count, hipStream_t st) {
@@ -335,18 +328,15 @@ int sage_narrow_fwd_groups(const SnFwdPtrs* g, const SnFwdBn* bn, int ng, int ld
     SnFwdPtrs a0 = g[0], a1 = g[ng - 1];
     if (!stats) a0.ws = a1.ws = nullptr;
     const int ks = (K + 1) / 2;
-#define SNF_LAUNCH(KS_, ACT_) \
-  hipLaunchKernelGGL((k_sage_narrow_fwd<KS_, ACT_>), dim3(grid, ng), dim3(256), 0, st, a0, a1, lda, n, K, F, normalize, act, tiles)
-#define SNF_ACT(KS_)                                                                                       \
-  switch (act) {                                                                                           \
-    case CGC_ACT_RELU: SNF_LAUNCH(KS_, CGC_ACT_RELU); break;                                               \
-    case CGC_ACT_ELU: SNF_LAUNCH(KS_, CGC_ACT_ELU); break;                                                 \
-    case CGC_ACT_LEAKYRELU: SNF_LAUNCH(KS_, CGC_ACT_LEAKYRELU); break;                                     \
-    default: SNF_LAUNCH(KS_, CGC_ACT_IDENTITY); break;                                                     \
-  }
-    if (ks <= 8) { SNF_ACT(8); } else if (ks <= 10) { SNF_ACT(10); } else { SNF_ACT(16); }
-#undef SNF_ACT
-#undef SNF_LAUNCH
+    auto launch = [&](auto ks_c) {
+      with_act(act, [&](auto act_c) {
+        hipLaunchKernelGGL((k_sage_narrow_fwd<decltype(ks_c)::value, decltype(act_c)::value>), dim3(grid, ng), dim3(256), 0, st, a0, a1, lda, n,
+                           K, F, normalize, act, tiles);
+      });
+    };
+    if (ks <= 8) launch(std::integral_constant<int, 8>());
+    else if (ks <= 10) launch(std::integral_constant<int, 10>());
+    else launch(std::integral_constant<int, 16>());
     CGC_RETURN_IF_LAUNCH_FAILED();
     slots = grid;
   }

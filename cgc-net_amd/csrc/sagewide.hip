@@ -18,6 +18,7 @@
 //   * persistent workgroups stride over the row tiles; at the end each leaves one slot row [2, F] of column sums, folded in a
 //     fixed order in fp64 by k_stats_finalize (rowops.hip): deterministic.
 #include "common.hpp"
+#include "groups.hpp"
 
 #define L2_EPS 1e-12f
 typedef float floatx16 __attribute__((ext_vector_type(16)));
@@ -630,10 +631,6 @@ __global__ __launch_bounds__(256, 3) void k_sage_wide_cols(const float* __restri
     }
   }
 }
-
-extern "C" int cgc_stats_blocks(int n, int F);
-int launch_stats_finalize(const float* ws, int slots, int F, double count, float eps, float momentum, float* running_mean,
-                          float* running_var, float* mean, float* istd, int64_t* nbt, hipStream_t stream);   // rowops.hip
 
 // hn [n,F] (row stride ldh) = l2norm(agg [n,K] (row stride lda) @ W [K,F] + bias) ; rinv [n] = 1/max(||.||,1e-12) (1 if !normalize);
 // stats != 0: additionally mean / istd / running statistics / num_batches_tracked as cgc_l2norm_act_bn (ws: its slot area).

@@ -34,6 +34,8 @@ CASES = [
     ('softmax_bwd         (2R+W)', 3 * MB, lambda: K.softmax_bwd(hn, dy, n, F, out, db)),
     ('adj_prep_fwd        (R+2W)', 3 * AMB, lambda: K.adj_prep_fwd(A, 32 * 1140, 1140, 0.4, At, An, invd, ge1)),
     ('adj_prep_bwd        (4R+W)', 5 * AMB, lambda: K.adj_prep_bwd(A, An, invd, ge1, gAn, gAt, 32 * 1140, 1140, 0.4, dA)),
+    ('dense_rownorm_fwd   (R+W)', 2 * AMB, lambda: K.dense_rownorm_fwd(A, 32 * 1140, 1140, An, invd, ge1)),
+    ('dense_rownorm_bwd   (2R+W)', 3 * AMB, lambda: K.dense_rownorm_bwd(gAn, An, invd, ge1, 32 * 1140, 1140, dA)),
     ('torch copy          (R+W)', 2 * MB, lambda: out.copy_(dy)),
 ]
 
