@@ -1,33 +1,40 @@
-// Region statistics of a label image on gfx950: per label value the count, sum, sum of squares, extrema with their positions
-// (MOMENTS) or the 256-bin histogram (HISTOGRAM) of a second plane over the label's pixels, and quantiles read off such histograms
-// (QUANTILES).  Contract item by item: cgc-net_amd/kernels.py KernelSpec.region_statistics / region_histogram / region_quantiles;
-// design and measurements: DESIGN.md, "Region statistics".
+// Tables of a label image on gfx950, indexed by label value.  MOMENTS (count, sum, sum of squares, extrema with their positions),
+// HISTOGRAM (the 256 bins of a uint8 plane) and QUANTILES read off such histograms: KernelSpec.region_statistics / region_histogram /
+// region_quantiles; DESIGN.md, "Region statistics".  COOCCURRENCE (pairs of levels per offset): KernelSpec.region_cooccurrence; "Region
+// co-occurrence".  GEOMETRY (count, second-order sums, extents, quads, frame pixels): KernelSpec.region_geometry; "Region geometry".
 //
-// A pixel p is *counted* in row L iff labels[p] == L, 0 <= L <= max_label, and within is null or non-zero at p.  A pixel whose label
-// lies outside [0, max_label] is counted nowhere and adds one to *meta, whatever `within` says there.
-// Launches of one MOMENTS call:
-//   k_region_init      count = sum = sumsq = 0, the two key tables of the workspace to "nothing yet", *meta = 0
-//   k_region_moments   one 64 x 64 tile per workgroup.  A thread owns 16 consecutive rows of one column: all its loads are issued
-//                      before the first is looked at, and a run of equal labels down the column is summed in registers.  A finished run
-//                      is folded into an LDS table keyed by label (REGION_SLOTS slots, LDS atomics); after a barrier every claimed slot
-//                      goes to the global tables with one integer atomic per quantity.
-//   k_region_finish    keys -> min, max, argmin, argmax; the values of an empty row
-// HISTOGRAM: hipMemsetAsync, then k_region_hist -- the same tile, table and walk, with 256 16-bit bins per slot (two per dword; a bin
-// holds at most the 4096 pixels of a tile) and one LDS atomic per counted pixel; a claimed slot is flushed as 256 consecutive counters.
-// COOCCURRENCE (KernelSpec.region_cooccurrence; DESIGN.md, "Region co-occurrence"): hipMemsetAsync, then one k_region_cooc per offset
-// -- k_region_hist with a pair of pixels (anchor, partner) where the histogram has one, and a bin per pair of levels.
-// GEOMETRY (KernelSpec.region_geometry; DESIGN.md, "Region geometry"): k_geometry_init, k_region_geometry -- the same tile and table;
-// the labels alone, staged in LDS with a frame of one position; runs folded by closed forms in tile coordinates, quads classified
-// where their four positions differ -- and k_geometry_finish for the extents of empty rows.
-// OVERFLOW.  region_slot() probes at most REGION_PROBES <= REGION_SLOTS slots and never waits: a label that finds neither itself nor
-// an empty slot there is sent to the global tables directly (a run at a time in MOMENTS, a pixel at a time in HISTOGRAM).  Both routes
-// end in the same integer atomics on the same global words, so which pixels take which route -- it depends on the order in which lanes
-// arrive -- changes no result: integer sums, and minima / maxima of 64-bit keys, are independent of order.  A tile in which every pixel
-// has its own label is an ordinary input: 64 labels fold, the rest go direct.
-// EXTREMA.  The value and its position travel as one key: min key = (v ^ 0x80000000) << 32 | i, combined by unsigned min; max key =
-// (v ^ 0x80000000) << 32 | ~i, combined by unsigned max -- of equal values the smallest raster index i wins in both, in a thread's
-// run (i grows down the column, strict comparisons), in LDS and in global memory.  No key equals the initial ~0 / 0: i < 2^31.
+// A pixel p is *counted* in row L (*belongs* to it) iff labels[p] == L, 0 <= L <= max_label, and within is null or non-zero at p.  A
+// pixel whose label lies outside [0, max_label] is *refused*: counted nowhere, one more in *meta (region_refused), `within` or not.
+//
+// WHAT THE FOUR TILE KERNELS SHARE, each written once:
+//   RegionSpot      where a thread stands: a 64 x 64 tile per workgroup, a wave is one row of it, a thread owns 16 rows of one column.
+//   region_index,   a position on any side of the image is read through an address clamped into it, so that no load sits behind a
+//   region_judge    branch; whether it is inside is decided from its coordinates, never from what the clamped address returned.
+//                   RegionColumn::fetch issues the 16 loads of a column (labels, values, `within`), ::judge looks at them afterwards.
+//   region_slot     an LDS table of REGION_SLOTS rows keyed by label, filled with LDS atomics and flushed after a barrier with one
+//                   integer atomic per word.  OVERFLOW: a label looks at no more than REGION_PROBES <= REGION_SLOTS slots and never
+//                   waits; one that finds neither itself nor an empty slot there goes to the global tables directly.  Both routes end
+//                   in the same integer atomics on the same global words, so which pixels take which route -- it depends on the order
+//                   in which lanes arrive -- changes no result: integer sums, minima and maxima are independent of order.  A tile in
+//                   which every pixel has its own label is an ordinary input: 64 labels fold, the rest go direct.
+//   RegionBins      the table of HISTOGRAM and COOCCURRENCE: 256 16-bit bins per slot, two per dword; the walk down a thread's pixels
+//                   that keeps the slot of the label above and probes only when the label changes; the flush, a thread per bin.
+//   region_call     the host side: the refusals that depend on the image alone, the empty image, the grid; region_launch picks WITHIN.
+// WHAT EACH MODE ADDS:
+//   MOMENTS         k_region_init, k_region_moments, k_region_finish.  A run of equal labels down the column is summed in registers
+//                   and folded a run at a time (region_add: the same five quantities in LDS, on the direct route and in the flush).
+//                   EXTREMA: the value and its position travel as one key: min key = (v ^ 0x80000000) << 32 | i under an unsigned
+//                   min, max key = (v ^ 0x80000000) << 32 | ~i under an unsigned max -- of equal values the smallest raster index i
+//                   wins in both, in a thread's run (i grows down the column, strict comparisons), in LDS and in global memory.  No
+//                   key equals the initial ~0 / 0: i < 2^31.
+//   HISTOGRAM       hipMemsetAsync, k_region_hist: the bin of a counted pixel is its value; a slot is flushed as 256 consecutive counters.
+//   COOCCURRENCE    hipMemsetAsync, then one k_region_cooc per offset: a second column, the partners, loaded at (dy, dx) from the
+//                   anchors; the bin of a counted pair is its pair of levels, both orders when symmetric.
+//   GEOMETRY        k_geometry_init, k_region_geometry, k_geometry_finish.  The label every position belongs to is staged in LDS with
+//                   a frame of one position; runs are folded by closed forms in tile coordinates and shifted to the image on the way
+//                   to global memory (geom_add: the flush and the direct route), quads classified where their four positions differ.
 #include <stdint.h>
+#include <type_traits>
 
 #include "common.hpp"
 #include "image_common.hpp"
@@ -86,43 +93,78 @@ __device__ __forceinline__ int region_slot(int* key, int L) {
   return -1;
 }
 
-// The 16 pixels of a thread: labels, values and the bits "counted" and "refused" (label outside [0, max_label]).  Addresses are clamped
-// into the image, so that no load needs a branch; what lies outside is neither counted nor refused.
+struct RegionImage {                     // what every tile kernel is given
+  const int* labels;
+  const void* within;                    // null: every pixel
+  int wbytes, H, W, tiles_x, max_label;
+};
+
+struct RegionSpot {                      // where a thread stands
+  int ty, tx, oy, ox;                    // the tile of the workgroup and its first pixel
+  int ly0, lx;                           // the first of the thread's 16 rows and its column, in the tile
+  int y0, x;                             // ... and in the image
+  bool last_band, last_lane;             // the thread's rows end the tile; its column does
+};
+__device__ __forceinline__ RegionSpot region_spot(int tiles_x) {
+  RegionSpot s;
+  s.ty = blockIdx.x / tiles_x, s.tx = blockIdx.x - s.ty * tiles_x;
+  s.oy = s.ty * REGION_TILE, s.ox = s.tx * REGION_TILE;
+  s.ly0 = (threadIdx.x / REGION_TILE) * REGION_BAND, s.lx = threadIdx.x & (REGION_TILE - 1);
+  s.y0 = s.oy + s.ly0, s.x = s.ox + s.lx;
+  s.last_band = s.ly0 + REGION_BAND == REGION_TILE, s.last_lane = s.lx == REGION_TILE - 1;
+  return s;
+}
+
+// The raster index position (py, px) is read through: clamped into the image on every side, so that no load needs a branch.
+__device__ __forceinline__ int64_t region_index(const RegionImage& im, int py, int px) {
+  const int yc = py < 0 ? 0 : (py < im.H ? py : im.H - 1), xc = px < 0 ? 0 : (px < im.W ? px : im.W - 1);
+  return (int64_t)yc * im.W + xc;
+}
+// What was read there: label L, and `on`, the bit of `within`.  Inside the image or not is decided from the coordinates; what lies
+// outside is neither counted nor refused.
+struct RegionVerdict { bool refused, counted; };
+template <bool WITHIN>
+__device__ __forceinline__ RegionVerdict region_judge(const RegionImage& im, int py, int px, int L, bool on) {
+  const bool inside = (unsigned)py < (unsigned)im.H && (unsigned)px < (unsigned)im.W;      // 0 <= py < H, 0 <= px < W
+  const bool bad = (unsigned)L > (unsigned)im.max_label;                                    // L < 0 or L > max_label
+  return {inside && bad, inside && !bad && (!WITHIN || on)};
+}
+
+// 16 positions of one column, (dy, dx) from the thread's own: labels, values and the bits "counted" and "refused".  Two passes, so
+// that a kernel can issue the loads of all its columns before it looks at the first: fetch() loads, judge() decides.
 template <typename T, bool WITHIN>
 struct RegionColumn {
   int lab[REGION_BAND], val[REGION_BAND];
-  unsigned counted, refused;
-  int first;                                                     // raster index of the thread's first pixel (meaningful if inside)
-  __device__ __forceinline__ void load(const int* __restrict__ labels, const T* __restrict__ values, const void* __restrict__ within,
-                                       int wbytes, int H, int W, int tiles_x, int max_label) {
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-    const int x = tx * REGION_TILE + (threadIdx.x & (REGION_TILE - 1));
-    const int y0 = ty * REGION_TILE + (threadIdx.x / REGION_TILE) * REGION_BAND;
-    const int xc = x < W ? x : W - 1;
-    unsigned on = 0;
+  unsigned on, counted, refused;                                 // bit k: `within` is non-zero at position k; it is counted; refused
+  int py0, px, first;                                            // the first position, and its raster index (meaningful if inside)
+  __device__ __forceinline__ void fetch(const RegionImage& im, const T* __restrict__ values, const RegionSpot& s, int dy, int dx) {
+    py0 = s.y0 + dy, px = s.x + dx, on = 0;
 #pragma unroll
     for (int k = 0; k < REGION_BAND; ++k) {
-      const int yc = y0 + k < H ? y0 + k : H - 1;
-      const int64_t i = (int64_t)yc * W + xc;
-      lab[k] = labels[i];
+      const int64_t i = region_index(im, py0 + k, px);
+      lab[k] = im.labels[i];
       val[k] = (int)values[i];
-      if (WITHIN) on |= (unsigned)image_nonzero(within, wbytes, i) << k;
+      if (WITHIN) on |= (unsigned)image_nonzero(im.within, im.wbytes, i) << k;
     }
+  }
+  __device__ __forceinline__ void judge(const RegionImage& im) {
     counted = refused = 0;
 #pragma unroll
     for (int k = 0; k < REGION_BAND; ++k) {
-      const bool inside = x < W && y0 + k < H;
-      const bool bad = lab[k] < 0 || lab[k] > max_label;
-      refused |= (unsigned)(inside && bad) << k;
-      counted |= (unsigned)(inside && !bad && (!WITHIN || (on >> k & 1u))) << k;
+      const RegionVerdict v = region_judge<WITHIN>(im, py0 + k, px, lab[k], on >> k & 1u);
+      refused |= (unsigned)v.refused << k;
+      counted |= (unsigned)v.counted << k;
     }
-    first = (int)((int64_t)y0 * W + x);                          // < H W < 2^31 whenever a bit of `counted` is set
+    first = (int)((int64_t)py0 * im.W + px);                     // < H W < 2^31 whenever a bit of `counted` is set
   }
 };
 
+__device__ __forceinline__ void region_refused(int* meta, unsigned refused) {      // bit k: the thread's pixel k is refused
+  if (refused != 0) atomicAdd(meta, (int)__builtin_popcount(refused));
+}
+
 struct RegionMoments {
-  int key[REGION_SLOTS];
-  int cnt[REGION_SLOTS];
+  int key[REGION_SLOTS], cnt[REGION_SLOTS];
   u64 sum[REGION_SLOTS], sq[REGION_SLOTS], kmin[REGION_SLOTS], kmax[REGION_SLOTS];
 };
 
@@ -131,10 +173,18 @@ struct RegionTables {
   u64 *sum, *sumsq, *kmin, *kmax;      // sumsq may be null
 };
 
+// The five quantities of a run or of a slot into row i of five tables, in LDS or in global memory.  Inlined, so that every caller's
+// atomics are those of its address space.
+__device__ __forceinline__ void region_add(const RegionTables& p, bool with_sq, int i, int n, u64 sum, u64 sq, u64 kmn, u64 kmx) {
+  atomicAdd(&p.count[i], n);
+  atomicAdd(&p.sum[i], sum);
+  if (with_sq) atomicAdd(&p.sumsq[i], sq);
+  atomicMin(&p.kmin[i], kmn);
+  atomicMax(&p.kmax[i], kmx);
+}
+
 template <typename T, bool WITHIN>
-__global__ void __launch_bounds__(CGC_BLOCK) k_region_moments(const int* __restrict__ labels, const T* __restrict__ values,
-                                                              const void* __restrict__ within, int wbytes, int H, int W, int tiles_x,
-                                                              int max_label, RegionTables g, int* meta) {
+__global__ void __launch_bounds__(CGC_BLOCK) k_region_moments(RegionImage im, const T* __restrict__ values, RegionTables g, int* meta) {
   __shared__ RegionMoments t;
   for (int i = threadIdx.x; i < REGION_SLOTS; i += CGC_BLOCK) {
     t.key[i] = REGION_EMPTY;
@@ -144,7 +194,8 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_region_moments(const int* __restr
     t.kmax[i] = REGION_NO_MAX;
   }
   RegionColumn<T, WITHIN> c;
-  c.load(labels, values, within, wbytes, H, W, tiles_x, max_label);
+  c.fetch(im, values, region_spot(im.tiles_x), 0, 0);
+  c.judge(im);
   __syncthreads();
   const bool with_sq = g.sumsq != nullptr;
 
@@ -154,19 +205,8 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_region_moments(const int* __restr
   auto fold = [&]() {
     const u64 kmn = region_min_key(vmin, imin), kmx = region_max_key(vmax, imax);
     const int s = region_slot(t.key, rl);
-    if (s >= 0) {
-      atomicAdd(&t.cnt[s], rc);
-      atomicAdd(&t.sum[s], (u64)rs);
-      if (with_sq) atomicAdd(&t.sq[s], (u64)rq);
-      atomicMin(&t.kmin[s], kmn);
-      atomicMax(&t.kmax[s], kmx);
-    } else {
-      atomicAdd(&g.count[rl], rc);
-      atomicAdd(&g.sum[rl], (u64)rs);
-      if (with_sq) atomicAdd(&g.sumsq[rl], (u64)rq);
-      atomicMin(&g.kmin[rl], kmn);
-      atomicMax(&g.kmax[rl], kmx);
-    }
+    if (s >= 0) region_add(RegionTables{t.cnt, t.sum, t.sq, t.kmin, t.kmax}, with_sq, s, rc, (u64)rs, (u64)rq, kmn, kmx);
+    else region_add(g, with_sq, rl, rc, (u64)rs, (u64)rq, kmn, kmx);
   };
 #pragma unroll
   for (int k = 0; k <= REGION_BAND; ++k) {
@@ -177,7 +217,7 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_region_moments(const int* __restr
       rl = REGION_EMPTY;
     }
     if (on) {
-      const int v = c.val[k < REGION_BAND ? k : 0], i = c.first + k * W;
+      const int v = c.val[k < REGION_BAND ? k : 0], i = c.first + k * im.W;
       if (rl == REGION_EMPTY) {
         rl = L;
         rc = 0;
@@ -192,16 +232,11 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_region_moments(const int* __restr
       if (v > vmax) vmax = v, imax = i;
     }
   }
-  if (c.refused != 0) atomicAdd(meta, (int)__builtin_popcount(c.refused));
+  region_refused(meta, c.refused);
   __syncthreads();
   for (int s = threadIdx.x; s < REGION_SLOTS; s += CGC_BLOCK) {
     const int L = t.key[s];
-    if (L == REGION_EMPTY) continue;
-    atomicAdd(&g.count[L], t.cnt[s]);
-    atomicAdd(&g.sum[L], t.sum[s]);
-    if (with_sq) atomicAdd(&g.sumsq[L], t.sq[s]);
-    atomicMin(&g.kmin[L], t.kmin[s]);
-    atomicMax(&g.kmax[L], t.kmax[s]);
+    if (L != REGION_EMPTY) region_add(g, with_sq, L, t.cnt[s], t.sum[s], t.sq[s], t.kmin[s], t.kmax[s]);
   }
 }
 
@@ -229,42 +264,67 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_region_finish(int rows, const int
   }
 }
 
-struct RegionHist {
+// The table of HISTOGRAM and COOCCURRENCE, in LDS: per slot 256 bins of 16 bits.  `out` is a global table of int32 counters whose row L
+// starts `row_stride` counters after row L - 1.
+struct RegionBins {
   int key[REGION_SLOTS];
-  uint32_t bins[REGION_SLOTS * 128];      // slot s, value v: the half v & 1 of dword 128 s + (v >> 1)
+  uint32_t bins[REGION_SLOTS * 128];      // slot s, bin b: the half b & 1 of dword 128 s + (b >> 1)
+  __device__ __forceinline__ void clear() {
+    for (int i = threadIdx.x; i < REGION_SLOTS; i += CGC_BLOCK) key[i] = REGION_EMPTY;
+    for (int i = threadIdx.x; i < REGION_SLOTS * 128; i += CGC_BLOCK) bins[i] = 0;
+  }
+  __device__ __forceinline__ void add(int s, int b) { atomicAdd(&bins[s * 128 + (b >> 1)], 1u << ((b & 1) * 16)); }
+  // Down a thread's 16 positions: where bit k of `mask` is set, label lab[k] gains one in each of the bins that bins_of(k, b) writes
+  // to b[0 .. its result - 1], one or two: in its slot, or, where it has none, in its row of `out` (the direct route).  The slot of
+  // the label above is kept; a label is looked up only where it changes.
+  template <typename BinsOf>
+  __device__ __forceinline__ void walk(const int (&lab)[REGION_BAND], unsigned mask, int* out, int64_t row_stride, BinsOf&& bins_of) {
+    int cl = REGION_EMPTY, cs = -1;
+#pragma unroll
+    for (int k = 0; k < REGION_BAND; ++k) {
+      if (!(mask >> k & 1u)) continue;
+      const int L = lab[k];
+      int b[2];
+      const int nb = bins_of(k, b);
+      if (L != cl) {
+        cl = L;
+        cs = region_slot(key, L);
+      }
+      if (cs >= 0) {
+        add(cs, b[0]);
+        if (nb == 2) add(cs, b[1]);
+      } else {
+        int* row = out + (int64_t)L * row_stride;
+        atomicAdd(&row[b[0]], 1);
+        if (nb == 2) atomicAdd(&row[b[1]], 1);
+      }
+    }
+  }
+  // Behind the caller's last barrier: thread v < nbins <= CGC_BLOCK adds bin v of every claimed slot to its row, where it is not zero.
+  __device__ __forceinline__ void flush(int* out, int64_t row_stride, int nbins) const {
+    const int v = threadIdx.x;
+    if (v >= nbins) return;
+    for (int s = 0; s < REGION_SLOTS; ++s) {
+      const int L = key[s];                                       // uniform
+      if (L == REGION_EMPTY) continue;
+      const int n = (int)(bins[s * 128 + (v >> 1)] >> ((v & 1) * 16) & 0xffffu);
+      if (n != 0) atomicAdd(&out[(int64_t)L * row_stride + v], n);
+    }
+  }
 };
 
 template <bool WITHIN>
-__global__ void __launch_bounds__(CGC_BLOCK) k_region_hist(const int* __restrict__ labels, const uint8_t* __restrict__ values,
-                                                           const void* __restrict__ within, int wbytes, int H, int W, int tiles_x,
-                                                           int max_label, int* hist, int* meta) {
-  __shared__ RegionHist t;
-  for (int i = threadIdx.x; i < REGION_SLOTS; i += CGC_BLOCK) t.key[i] = REGION_EMPTY;
-  for (int i = threadIdx.x; i < REGION_SLOTS * 128; i += CGC_BLOCK) t.bins[i] = 0;
+__global__ void __launch_bounds__(CGC_BLOCK) k_region_hist(RegionImage im, const uint8_t* __restrict__ values, int* hist, int* meta) {
+  __shared__ RegionBins t;
+  t.clear();
   RegionColumn<uint8_t, WITHIN> c;
-  c.load(labels, values, within, wbytes, H, W, tiles_x, max_label);
+  c.fetch(im, values, region_spot(im.tiles_x), 0, 0);
+  c.judge(im);
   __syncthreads();
-  int cl = REGION_EMPTY, cs = -1;                                 // the label of the pixel above and its slot
-#pragma unroll
-  for (int k = 0; k < REGION_BAND; ++k) {
-    if (!(c.counted >> k & 1u)) continue;
-    const int L = c.lab[k], v = c.val[k];
-    if (L != cl) {
-      cl = L;
-      cs = region_slot(t.key, L);
-    }
-    if (cs >= 0) atomicAdd(&t.bins[cs * 128 + (v >> 1)], 1u << ((v & 1) * 16));
-    else atomicAdd(&hist[(int64_t)L * 256 + v], 1);
-  }
-  if (c.refused != 0) atomicAdd(meta, (int)__builtin_popcount(c.refused));
+  t.walk(c.lab, c.counted, hist, 256, [&](int k, int (&b)[2]) { b[0] = c.val[k]; return 1; });      // one bin: the value
+  region_refused(meta, c.refused);
   __syncthreads();
-  const int v = threadIdx.x;                                      // CGC_BLOCK == 256: a thread flushes one value of every claimed slot
-  for (int s = 0; s < REGION_SLOTS; ++s) {
-    const int L = t.key[s];                                       // uniform
-    if (L == REGION_EMPTY) continue;
-    const int n = (int)(t.bins[s * 128 + (v >> 1)] >> ((v & 1) * 16) & 0xffffu);
-    if (n != 0) atomicAdd(&hist[(int64_t)L * 256 + v], n);
-  }
+  t.flush(hist, 256, 256);
 }
 
 struct RegionQuantiles {
@@ -291,8 +351,26 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_region_quantiles(const uint32_t* 
   }
 }
 
-static inline bool bad_region(int H, int W, int max_label, const void* within, int wbytes) {
-  return bad_image_dims(H, W) || max_label < 0 || max_label == 0x7fffffff || (within != nullptr && bad_elem_bytes(wbytes));
+struct RegionCall {                      // the host side that the four tile kernels share
+  RegionImage im;                        // wbytes is 0 where within is null
+  dim3 grid;                             // a workgroup per tile
+  bool empty;                            // H W = 0: no tile launch, the tables of empty rows
+};
+// False: the call is refused.  `planes`: every plane the mode reads was given; an empty image needs none.
+static inline bool region_call(RegionCall& c, const int* labels, bool planes, const void* within, int wbytes, int H, int W, int max_label) {
+  if (bad_image_dims(H, W) || max_label < 0 || max_label == 0x7fffffff || (within != nullptr && bad_elem_bytes(wbytes))) return false;
+  c.empty = (int64_t)H * W == 0;
+  if (!c.empty && !planes) return false;
+  const int tiles_x = ceil_div(W, REGION_TILE);
+  c.im = RegionImage{labels, within, within != nullptr ? wbytes : 0, H, W, tiles_x, max_label};
+  c.grid = dim3((unsigned)((int64_t)tiles_x * ceil_div(H, REGION_TILE)));      // < 2^31 / 4096 + H / 64 + W / 64 + 1
+  return true;
+}
+// launch(std::true_type{}) where the call has a `within`, launch(std::false_type{}) where not: the WITHIN of the kernel to launch
+template <typename Launch>
+static inline void region_launch(const RegionCall& c, Launch&& launch) {
+  if (c.im.within != nullptr) launch(std::true_type{});
+  else launch(std::false_type{});
 }
 static inline int region_blocks(int64_t rows) {
   const int64_t b = ceil_div64(rows, CGC_BLOCK);
@@ -303,88 +381,39 @@ struct CoocLut {
   uint32_t w[64];                        // the level of value v: byte v & 3 of dword v >> 2
 };
 
-struct RegionCooc {
-  int key[REGION_SLOTS];
-  uint32_t bins[REGION_SLOTS * 128];      // slot s, bin a * levels + b: as RegionHist's value
-  uint32_t level[64];                    // the lut, for lookups by lane
-};
-
-// One offset (dy, dx) of COOCCURRENCE: k_region_hist with a pair of pixels where the histogram has one.  The anchor p is the thread's
-// pixel, the partner q = p + (dy, dx) is loaded from global memory through an address clamped into the image; whether q lies inside the
-// image is decided from its coordinates, never from what the clamped address returned.  The tile that holds p counts the pair, wherever
-// q lies.  `out` is the table of this offset, tables + k * levels^2; a row is `row_stride` = noff * levels^2 counters further on.
+// One offset (dy, dx) of COOCCURRENCE.  The anchor p is the thread's pixel, the partner q = p + (dy, dx) a second column loaded beside
+// the first; a pair is counted where both are counted and their labels agree.  The tile that holds p counts the pair, wherever q
+// lies.  `out` is the table of this offset, tables + k * levels^2; a row is `row_stride` = noff * levels^2 counters further on.
 template <bool WITHIN>
-__global__ void __launch_bounds__(CGC_BLOCK) k_region_cooc(const int* __restrict__ labels, const uint8_t* __restrict__ values,
-                                                           const void* __restrict__ within, int wbytes, int H, int W, int tiles_x,
-                                                           int max_label, CoocLut lut, int levels, int dy, int dx, int symmetric,
-                                                           int count_refused, int* out, int64_t row_stride, int* meta) {
-  __shared__ RegionCooc t;
-  for (int i = threadIdx.x; i < REGION_SLOTS; i += CGC_BLOCK) t.key[i] = REGION_EMPTY;
-  for (int i = threadIdx.x; i < REGION_SLOTS * 128; i += CGC_BLOCK) t.bins[i] = 0;
-  if (threadIdx.x < 64) t.level[threadIdx.x] = lut.w[threadIdx.x];
-  RegionColumn<uint8_t, WITHIN> c;
-  c.load(labels, values, within, wbytes, H, W, tiles_x, max_label);
-  // the partners: same column for all 16, rows y0 + dy ..
-  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  const int qx = tx * REGION_TILE + (threadIdx.x & (REGION_TILE - 1)) + dx;
-  const int qy0 = ty * REGION_TILE + (threadIdx.x / REGION_TILE) * REGION_BAND + dy;
-  const int qxc = qx < 0 ? 0 : (qx < W ? qx : W - 1);
-  int plab[REGION_BAND], pval[REGION_BAND];
-  unsigned pon = 0;
-#pragma unroll
-  for (int k = 0; k < REGION_BAND; ++k) {
-    const int qy = qy0 + k;
-    const int qyc = qy < 0 ? 0 : (qy < H ? qy : H - 1);
-    const int64_t i = (int64_t)qyc * W + qxc;
-    plab[k] = labels[i];
-    pval[k] = (int)values[i];
-    if (WITHIN) pon |= (unsigned)image_nonzero(within, wbytes, i) << k;
-  }
+__global__ void __launch_bounds__(CGC_BLOCK) k_region_cooc(RegionImage im, const uint8_t* __restrict__ values, CoocLut lut, int levels, int dy,
+                                                           int dx, int symmetric, int count_refused, int* out, int64_t row_stride, int* meta) {
+  __shared__ RegionBins t;
+  __shared__ uint32_t level_words[64];                           // the lut, for lookups by lane
+  t.clear();
+  if (threadIdx.x < 64) level_words[threadIdx.x] = lut.w[threadIdx.x];
+  const RegionSpot s = region_spot(im.tiles_x);
+  RegionColumn<uint8_t, WITHIN> c, q;                             // the anchors, the partners
+  c.fetch(im, values, s, 0, 0);
+  q.fetch(im, values, s, dy, dx);
+  c.judge(im);
+  q.judge(im);
   unsigned pair = 0;                                              // bit k: anchor k and its partner are a counted pair
 #pragma unroll
-  for (int k = 0; k < REGION_BAND; ++k) {
-    const int qy = qy0 + k;
-    const bool inside = qx >= 0 && qx < W && qy >= 0 && qy < H;
-    pair |= (unsigned)(inside && plab[k] == c.lab[k] && (!WITHIN || (pon >> k & 1u))) << k;
-  }
-  pair &= c.counted;
+  for (int k = 0; k < REGION_BAND; ++k) pair |= (unsigned)(q.lab[k] == c.lab[k]) << k;
+  pair &= c.counted & q.counted;
   __syncthreads();
-  const uint8_t* level = reinterpret_cast<const uint8_t*>(t.level);
-  int cl = REGION_EMPTY, cs = -1;                                 // the label of the pair above and its slot
-#pragma unroll
-  for (int k = 0; k < REGION_BAND; ++k) {
-    if (!(pair >> k & 1u)) continue;
-    const int L = c.lab[k];
-    const int a = level[c.val[k]], b = level[pval[k]];
-    const int ab = a * levels + b, ba = b * levels + a;            // < levels^2 <= 256: the host checked every entry of the lut
-    if (L != cl) {
-      cl = L;
-      cs = region_slot(t.key, L);
-    }
-    if (cs >= 0) {
-      atomicAdd(&t.bins[cs * 128 + (ab >> 1)], 1u << ((ab & 1) * 16));
-      if (symmetric) atomicAdd(&t.bins[cs * 128 + (ba >> 1)], 1u << ((ba & 1) * 16));
-    } else {
-      int* row = out + (int64_t)L * row_stride;
-      atomicAdd(&row[ab], 1);
-      if (symmetric) atomicAdd(&row[ba], 1);
-    }
-  }
-  if (count_refused && c.refused != 0) atomicAdd(meta, (int)__builtin_popcount(c.refused));
+  const uint8_t* level = reinterpret_cast<const uint8_t*>(level_words);
+  t.walk(c.lab, pair, out, row_stride, [&](int k, int (&b)[2]) {
+    const int lc = level[c.val[k]], lq = level[q.val[k]];
+    b[0] = lc * levels + lq, b[1] = lq * levels + lc;             // < levels^2 <= 256: the host checked every entry of the lut
+    return symmetric ? 2 : 1;
+  });
+  if (count_refused) region_refused(meta, c.refused);
   __syncthreads();
-  const int v = threadIdx.x;                                      // CGC_BLOCK == 256: a thread flushes one bin of every claimed slot
-  if (v >= levels * levels) return;                               // after the last barrier
-  for (int s = 0; s < REGION_SLOTS; ++s) {
-    const int L = t.key[s];                                       // uniform
-    if (L == REGION_EMPTY) continue;
-    const int n = (int)(t.bins[s * 128 + (v >> 1)] >> ((v & 1) * 16) & 0xffffu);
-    if (n != 0) atomicAdd(&out[(int64_t)L * row_stride + v], n);
-  }
+  t.flush(out, row_stride, levels * levels);
 }
 
-// GEOMETRY (KernelSpec.region_geometry; DESIGN.md, "Region geometry"): the shape of every region from the label image alone.  A pixel
-// *belongs* to row L as it is counted above; a position outside the image, with a refused label or outside `within` belongs to none.
-constexpr int GEOM_NONE = REGION_EMPTY;
+constexpr int GEOM_NONE = REGION_EMPTY;                          // GEOMETRY: the row of a position that belongs to none
 constexpr int GEOM_DIRS = 8;                                     // directions (a, b) of the extents a x + b y; every b >= 0 (exported order)
 constexpr int GEOM_MAX_SIDE = 32767;                             // sum x^2 over 2^31 pixels stays inside int64 (exported)
 constexpr int GEOM_SIDE = REGION_TILE + 2;                       // a tile and the frame of one position its quads reach into
@@ -420,12 +449,24 @@ __device__ __forceinline__ void geom_max(int* p, int v) {
   if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, SCOPE)) atomicMax(p, v);
 }
 
+// n pixels of row L, `border` of them on the image's frame, and their five sums in the coordinates of the tile at (ox, oy): shifted to
+// image coordinates, in 64 bits, and added to the global tables.  A slot at the flush; on the direct route a run, a table of one.
+__device__ __forceinline__ void geom_add(const GeomTables& g, int L, int ox, int oy, int64_t n, int border, int64_t sy, int64_t sx, int64_t syy,
+                                         int64_t sxy, int64_t sxx) {
+  atomicAdd(&g.count[L], (int)n);
+  if (border != 0) atomicAdd(&g.border[L], border);
+  atomicAdd(&g.sy[L], (u64)(sy + n * oy));
+  atomicAdd(&g.sx[L], (u64)(sx + n * ox));
+  atomicAdd(&g.syy[L], (u64)(syy + 2 * oy * sy + n * oy * oy));
+  atomicAdd(&g.sxy[L], (u64)(sxy + ox * sy + oy * sx + n * ox * oy));
+  atomicAdd(&g.sxx[L], (u64)(sxx + 2 * ox * sx + n * ox * ox));
+}
+
 // One tile.  The label every position of the tile and of a frame of one position around it belongs to (GEOM_NONE: to none) is staged
 // in LDS, so that runs and quads are walked by loops over k, not by unrolled copies of their bodies: a fold is 23 atomics and a slot
 // lookup, and sixteen copies of it per thread do not fit the instruction cache.
 template <bool WITHIN>
-__global__ void __launch_bounds__(CGC_BLOCK) k_region_geometry(const int* __restrict__ labels, const void* __restrict__ within, int wbytes,
-                                                               int H, int W, int tiles_x, int max_label, GeomTables g, int* meta) {
+__global__ void __launch_bounds__(CGC_BLOCK) k_region_geometry(RegionImage im, GeomTables g, int* meta) {
   __shared__ GeomTile t;
   __shared__ int e[GEOM_SIDE][GEOM_SIDE];                          // position (ly, lx) of the tile, -1 .. REGION_TILE, at [ly + 1][lx + 1]
   for (int i = threadIdx.x; i < REGION_SLOTS; i += CGC_BLOCK) {
@@ -439,20 +480,14 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_region_geometry(const int* __rest
   }
   (&t.quad[0][0])[threadIdx.x] = 0;                               // CGC_BLOCK == REGION_SLOTS * 4
   if (threadIdx.x < GEOM_SIDE) e[0][threadIdx.x] = e[threadIdx.x][0] = GEOM_NONE;      // row and column -1: only the image's frame is ever read
-  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  const int ox = tx * REGION_TILE, oy = ty * REGION_TILE;
-  const int lx = threadIdx.x & (REGION_TILE - 1), ly0 = (threadIdx.x / REGION_TILE) * REGION_BAND;
-  const int x = ox + lx, y0 = oy + ly0;
-  const bool last_band = ly0 + REGION_BAND == REGION_TILE, last_lane = lx == REGION_TILE - 1;
-  // The row position (py, px) belongs to.  The address is clamped into the image; whether the position lies inside is decided from
-  // its coordinates.  `bad`: inside, and the label is outside [0, max_label].
-  auto belongs = [&](int py, int px, bool& bad) -> int {
-    const int64_t i = (int64_t)(py < H ? py : H - 1) * W + (px < W ? px : W - 1);
-    const int L = labels[i];
-    const bool on = !WITHIN || image_nonzero(within, wbytes, i);
-    const bool inside = py < H && px < W;
-    bad = inside && (L < 0 || L > max_label);
-    return inside && !bad && on ? L : GEOM_NONE;
+  const RegionSpot sp = region_spot(im.tiles_x);
+  const int H = im.H, W = im.W, ty = sp.ty, tx = sp.tx, ox = sp.ox, oy = sp.oy, lx = sp.lx, ly0 = sp.ly0, x = sp.x, y0 = sp.y0;
+  auto belongs = [&](int py, int px, bool& bad) -> int {          // the row position (py, px) belongs to; `bad`: it is refused
+    const int64_t i = region_index(im, py, px);
+    const int L = im.labels[i];
+    const RegionVerdict v = region_judge<WITHIN>(im, py, px, L, WITHIN && image_nonzero(im.within, im.wbytes, i));
+    bad = v.refused;
+    return v.counted ? L : GEOM_NONE;
   };
   unsigned on = 0, brk = 0, refused = 0;                          // bit k: pixel k belongs somewhere; not where pixel k - 1 does; is refused
   {
@@ -467,11 +502,11 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_region_geometry(const int* __rest
       prev = L;
       e[ly0 + k + 1][lx + 1] = L;
     }
-    if (last_band) e[REGION_TILE + 1][lx + 1] = belongs(oy + REGION_TILE, x, bad);      // the row below the tile
-    if (last_lane) {                                              // the column to its right
+    if (sp.last_band) e[REGION_TILE + 1][lx + 1] = belongs(oy + REGION_TILE, x, bad);      // the row below the tile
+    if (sp.last_lane) {                                              // the column to its right
 #pragma unroll
       for (int k = 0; k < REGION_BAND; ++k) e[ly0 + k + 1][REGION_TILE + 1] = belongs(y0 + k, x + 1, bad);
-      if (last_band) e[REGION_TILE + 1][REGION_TILE + 1] = belongs(oy + REGION_TILE, x + 1, bad);
+      if (sp.last_band) e[REGION_TILE + 1][REGION_TILE + 1] = belongs(oy + REGION_TILE, x + 1, bad);
     }
   }
   __syncthreads();
@@ -501,15 +536,8 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_region_geometry(const int* __rest
         geom_min<__HIP_MEMORY_SCOPE_WORKGROUP>(&t.ext[s][d][0], geom_a(d) * lx + geom_b(d) * ya);
         geom_max<__HIP_MEMORY_SCOPE_WORKGROUP>(&t.ext[s][d][1], geom_a(d) * lx + geom_b(d) * yb);
       }
-    } else {                                                      // no slot: the same atomics on the global tables, in image coordinates
-      const int64_t sy = (int64_t)rsy + (int64_t)n * oy, syy = (int64_t)rsyy + 2 * (int64_t)oy * rsy + (int64_t)n * oy * oy;
-      atomicAdd(&g.count[L], n);
-      if (rb != 0) atomicAdd(&g.border[L], rb);
-      atomicAdd(&g.sy[L], (u64)sy);
-      atomicAdd(&g.sx[L], (u64)((int64_t)n * x));
-      atomicAdd(&g.syy[L], (u64)syy);
-      atomicAdd(&g.sxy[L], (u64)(sy * x));
-      atomicAdd(&g.sxx[L], (u64)((int64_t)n * x * x));
+    } else {                                                      // no slot: the run goes to the global tables as a slot of its own would
+      geom_add(g, L, ox, oy, n, rb, rsy, n * lx, rsyy, rsy * lx, n * lx * lx);
       int* ext = g.ext + (int64_t)L * (GEOM_DIRS * 2);
 #pragma unroll
       for (int d = 0; d < GEOM_DIRS; ++d) {
@@ -556,7 +584,7 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_region_geometry(const int* __rest
       tr = br;
     }
   }
-  if (refused != 0) atomicAdd(meta, (int)__builtin_popcount(refused));
+  region_refused(meta, refused);
   __syncthreads();
 
   // flush: a wave per quarter of a slot's words, shifted to image coordinates
@@ -564,15 +592,8 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_region_geometry(const int* __rest
   const int L = t.key[s];
   if (L == REGION_EMPTY) return;                                  // after the last barrier
   if (part == 0) {
-    const int64_t n = t.cnt[s], sy = t.sy[s], sx = t.sx[s];
-    if (n == 0) return;                                           // a slot claimed by a quad alone
-    atomicAdd(&g.count[L], (int)n);
-    if (t.border[s] != 0) atomicAdd(&g.border[L], t.border[s]);
-    atomicAdd(&g.sy[L], (u64)(sy + n * oy));
-    atomicAdd(&g.sx[L], (u64)(sx + n * ox));
-    atomicAdd(&g.syy[L], (u64)((int64_t)t.syy[s] + 2 * oy * sy + n * oy * oy));
-    atomicAdd(&g.sxy[L], (u64)((int64_t)t.sxy[s] + ox * sy + oy * sx + n * ox * oy));
-    atomicAdd(&g.sxx[L], (u64)((int64_t)t.sxx[s] + 2 * ox * sx + n * ox * ox));
+    if (t.cnt[s] == 0) return;                                    // a slot claimed by a quad alone
+    geom_add(g, L, ox, oy, t.cnt[s], t.border[s], t.sy[s], t.sx[s], t.syy[s], t.sxy[s], t.sxx[s]);
   } else if (part == 3) {
 #pragma unroll
     for (int c = 0; c < 4; ++c)
@@ -597,7 +618,7 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_region_geometry(const int* __rest
     }
   }
 }
-static_assert(CGC_BLOCK == REGION_SLOTS * 4, "the flush of k_region_geometry gives a slot four threads, one per wave");
+static_assert(CGC_BLOCK == 256 && CGC_BLOCK == REGION_SLOTS * 4, "a flush: RegionBins, a thread per bin; k_region_geometry, a wave per quarter of a slot");
 
 __global__ void __launch_bounds__(CGC_BLOCK) k_geometry_init(int rows, GeomTables g, int* meta) {
   for (int64_t r = (int64_t)blockIdx.x * CGC_BLOCK + threadIdx.x; r < rows; r += (int64_t)gridDim.x * CGC_BLOCK) {
@@ -622,19 +643,6 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_geometry_finish(int rows, const i
   }
 }
 
-template <typename T>
-void launch_moments(const int* labels, const void* values, const void* within, int wbytes, int H, int W, int max_label,
-                    const RegionTables& g, int* meta, hipStream_t st) {
-  const int tiles_x = ceil_div(W, REGION_TILE);
-  const dim3 grid((unsigned)((int64_t)tiles_x * ceil_div(H, REGION_TILE)));      // < 2^31 / 4096 + H / 64 + W / 64 + 1
-  if (within != nullptr)
-    hipLaunchKernelGGL((k_region_moments<T, true>), grid, dim3(CGC_BLOCK), 0, st, labels, static_cast<const T*>(values), within, wbytes, H, W,
-                       tiles_x, max_label, g, meta);
-  else
-    hipLaunchKernelGGL((k_region_moments<T, false>), grid, dim3(CGC_BLOCK), 0, st, labels, static_cast<const T*>(values), within, 0, H, W,
-                       tiles_x, max_label, g, meta);
-}
-
 }  // namespace
 
 extern "C" int cgc_region_tile_side(void) { return REGION_TILE; }
@@ -648,26 +656,31 @@ extern "C" int64_t cgc_region_ws_bytes(int max_label) {
 extern "C" int cgc_region_moments(const int* labels, const void* values, int value_bytes, int value_signed, const void* within_or_null,
                                   int within_bytes, int H, int W, int max_label, void* ws, int* count, int64_t* sum,
                                   int64_t* sumsq_or_null, int* min, int* max, int* argmin, int* argmax, int* meta, cgc_stream_t stream) {
-  if (bad_region(H, W, max_label, within_or_null, within_bytes)) return CGC_EINVAL;
+  RegionCall c;
+  if (!region_call(c, labels, labels != nullptr && values != nullptr, within_or_null, within_bytes, H, W, max_label)) return CGC_EINVAL;
   const bool u8 = value_bytes == 1 && value_signed == 0, i8 = value_bytes == 1 && value_signed == 1;
   const bool i16 = value_bytes == 2 && value_signed == 1, i32 = value_bytes == 4 && value_signed == 1;
   if (!(u8 || i8 || i16 || i32) || (i32 && sumsq_or_null != nullptr)) return CGC_EINVAL;
   if (ws == nullptr || count == nullptr || sum == nullptr || min == nullptr || max == nullptr || argmin == nullptr || argmax == nullptr ||
       meta == nullptr)
     return CGC_EINVAL;
-  const bool empty = (int64_t)H * W == 0;
-  if (!empty && (labels == nullptr || values == nullptr)) return CGC_EINVAL;
   hipStream_t st = as_stream(stream);
   const int rows = max_label + 1;
   const RegionWs w = region_layout(Carver(ws), rows);
   const RegionTables g{count, reinterpret_cast<u64*>(sum), reinterpret_cast<u64*>(sumsq_or_null), w.kmin, w.kmax};
   hipLaunchKernelGGL(k_region_init, dim3(region_blocks(rows)), dim3(CGC_BLOCK), 0, st, rows, g, meta);
   CGC_RETURN_IF_LAUNCH_FAILED();
-  if (!empty) {
-    if (u8) launch_moments<uint8_t>(labels, values, within_or_null, within_bytes, H, W, max_label, g, meta, st);
-    else if (i8) launch_moments<int8_t>(labels, values, within_or_null, within_bytes, H, W, max_label, g, meta, st);
-    else if (i16) launch_moments<int16_t>(labels, values, within_or_null, within_bytes, H, W, max_label, g, meta, st);
-    else launch_moments<int32_t>(labels, values, within_or_null, within_bytes, H, W, max_label, g, meta, st);
+  if (!c.empty) {
+    region_launch(c, [&](auto within) {
+      auto of = [&](auto v) {                                     // v: a value of the plane's type
+        hipLaunchKernelGGL((k_region_moments<decltype(v), decltype(within)::value>), c.grid, dim3(CGC_BLOCK), 0, st, c.im,
+                           static_cast<const decltype(v)*>(values), g, meta);
+      };
+      if (u8) of(uint8_t{});
+      else if (i8) of(int8_t{});
+      else if (i16) of(int16_t{});
+      else of(int32_t{});
+    });
     CGC_RETURN_IF_LAUNCH_FAILED();
   }
   hipLaunchKernelGGL(k_region_finish, dim3(region_blocks(rows)), dim3(CGC_BLOCK), 0, st, rows, count, w.kmin, w.kmax, min, max, argmin, argmax);
@@ -677,22 +690,17 @@ extern "C" int cgc_region_moments(const int* labels, const void* values, int val
 
 extern "C" int cgc_region_histogram(const int* labels, const uint8_t* values, const void* within_or_null, int within_bytes, int H, int W,
                                     int max_label, int* hist, int* meta, cgc_stream_t stream) {
-  if (bad_region(H, W, max_label, within_or_null, within_bytes) || hist == nullptr || meta == nullptr) return CGC_EINVAL;
-  const bool empty = (int64_t)H * W == 0;
-  if (!empty && (labels == nullptr || values == nullptr)) return CGC_EINVAL;
+  RegionCall c;
+  if (!region_call(c, labels, labels != nullptr && values != nullptr, within_or_null, within_bytes, H, W, max_label)) return CGC_EINVAL;
+  if (hist == nullptr || meta == nullptr) return CGC_EINVAL;
   hipStream_t st = as_stream(stream);
   hipError_t e = hipMemsetAsync(hist, 0, ((size_t)max_label + 1) * 256 * sizeof(int), st);
   if (e == hipSuccess) e = hipMemsetAsync(meta, 0, sizeof(int), st);
   if (e != hipSuccess) return (int)e;
-  if (empty) return 0;
-  const int tiles_x = ceil_div(W, REGION_TILE);
-  const dim3 grid((unsigned)((int64_t)tiles_x * ceil_div(H, REGION_TILE)));
-  if (within_or_null != nullptr)
-    hipLaunchKernelGGL(k_region_hist<true>, grid, dim3(CGC_BLOCK), 0, st, labels, values, within_or_null, within_bytes, H, W, tiles_x, max_label,
-                       hist, meta);
-  else
-    hipLaunchKernelGGL(k_region_hist<false>, grid, dim3(CGC_BLOCK), 0, st, labels, values, within_or_null, 0, H, W, tiles_x, max_label, hist,
-                       meta);
+  if (c.empty) return 0;
+  region_launch(c, [&](auto within) {
+    hipLaunchKernelGGL(k_region_hist<decltype(within)::value>, c.grid, dim3(CGC_BLOCK), 0, st, c.im, values, hist, meta);
+  });
   CGC_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
@@ -703,7 +711,9 @@ extern "C" int cgc_region_cooc_max_offsets(void) { return COOC_MAX_OFFSETS; }
 extern "C" int cgc_region_cooccurrence(const int* labels, const uint8_t* values, const void* within_or_null, int within_bytes, int H, int W,
                                        int max_label, const uint8_t* lut256_host, int levels, const int* offsets_host, int noff,
                                        int symmetric, int* tables, int* meta, cgc_stream_t stream) {
-  if (bad_region(H, W, max_label, within_or_null, within_bytes) || (int64_t)H * W >= COOC_MAX_PIXELS) return CGC_EINVAL;
+  RegionCall c;
+  if (!region_call(c, labels, labels != nullptr && values != nullptr, within_or_null, within_bytes, H, W, max_label)) return CGC_EINVAL;
+  if ((int64_t)H * W >= COOC_MAX_PIXELS) return CGC_EINVAL;
   if (tables == nullptr || meta == nullptr || lut256_host == nullptr || offsets_host == nullptr) return CGC_EINVAL;
   if (levels < 2 || levels > COOC_MAX_LEVELS || noff < 1 || noff > COOC_MAX_OFFSETS) return CGC_EINVAL;
   CoocLut lut{};
@@ -716,25 +726,18 @@ extern "C" int cgc_region_cooccurrence(const int* labels, const uint8_t* values,
     if (dy < -COOC_MAX_OFFSET || dy > COOC_MAX_OFFSET || dx < -COOC_MAX_OFFSET || dx > COOC_MAX_OFFSET || (dy == 0 && dx == 0))
       return CGC_EINVAL;
   }
-  const bool empty = (int64_t)H * W == 0;
-  if (!empty && (labels == nullptr || values == nullptr)) return CGC_EINVAL;
   hipStream_t st = as_stream(stream);
   const int bins = levels * levels;
   const int64_t row_stride = (int64_t)noff * bins;
   hipError_t e = hipMemsetAsync(tables, 0, ((size_t)max_label + 1) * (size_t)row_stride * sizeof(int), st);
   if (e == hipSuccess) e = hipMemsetAsync(meta, 0, sizeof(int), st);
   if (e != hipSuccess) return (int)e;
-  if (empty) return 0;
-  const int tiles_x = ceil_div(W, REGION_TILE);
-  const dim3 grid((unsigned)((int64_t)tiles_x * ceil_div(H, REGION_TILE)));
+  if (c.empty) return 0;
   for (int k = 0; k < noff; ++k) {                                // one launch per offset; the first counts the refused pixels
-    const int dy = offsets_host[2 * k], dx = offsets_host[2 * k + 1];
-    if (within_or_null != nullptr)
-      hipLaunchKernelGGL(k_region_cooc<true>, grid, dim3(CGC_BLOCK), 0, st, labels, values, within_or_null, within_bytes, H, W, tiles_x,
-                         max_label, lut, levels, dy, dx, (int)(symmetric != 0), (int)(k == 0), tables + (int64_t)k * bins, row_stride, meta);
-    else
-      hipLaunchKernelGGL(k_region_cooc<false>, grid, dim3(CGC_BLOCK), 0, st, labels, values, within_or_null, 0, H, W, tiles_x, max_label,
-                         lut, levels, dy, dx, (int)(symmetric != 0), (int)(k == 0), tables + (int64_t)k * bins, row_stride, meta);
+    region_launch(c, [&](auto within) {
+      hipLaunchKernelGGL(k_region_cooc<decltype(within)::value>, c.grid, dim3(CGC_BLOCK), 0, st, c.im, values, lut, levels, offsets_host[2 * k],
+                         offsets_host[2 * k + 1], (int)(symmetric != 0), (int)(k == 0), tables + (int64_t)k * bins, row_stride, meta);
+    });
     CGC_RETURN_IF_LAUNCH_FAILED();
   }
   return 0;
@@ -744,25 +747,20 @@ extern "C" int cgc_region_geometry_max_side(void) { return GEOM_MAX_SIDE; }
 
 extern "C" int cgc_region_geometry(const int* labels, const void* within_or_null, int within_bytes, int H, int W, int max_label, int* count,
                                    int64_t* sums, int* extents, int* quads, int* border, int* meta, cgc_stream_t stream) {
-  if (bad_region(H, W, max_label, within_or_null, within_bytes)) return CGC_EINVAL;
+  RegionCall c;
+  if (!region_call(c, labels, labels != nullptr, within_or_null, within_bytes, H, W, max_label)) return CGC_EINVAL;
   if (H > GEOM_MAX_SIDE || W > GEOM_MAX_SIDE || ((int64_t)H + 1) * ((int64_t)W + 1) >= ((int64_t)1 << 31)) return CGC_EINVAL;
   if (count == nullptr || sums == nullptr || extents == nullptr || quads == nullptr || border == nullptr || meta == nullptr) return CGC_EINVAL;
-  const bool empty = (int64_t)H * W == 0;
-  if (!empty && labels == nullptr) return CGC_EINVAL;
   hipStream_t st = as_stream(stream);
   const int rows = max_label + 1;
   u64* s = reinterpret_cast<u64*>(sums);                          // [5, rows]: sy, sx, syy, sxy, sxx
   const GeomTables g{count, s, s + rows, s + 2 * (int64_t)rows, s + 3 * (int64_t)rows, s + 4 * (int64_t)rows, extents, quads, border};
   hipLaunchKernelGGL(k_geometry_init, dim3(region_blocks(rows)), dim3(CGC_BLOCK), 0, st, rows, g, meta);
   CGC_RETURN_IF_LAUNCH_FAILED();
-  if (!empty) {
-    const int tiles_x = ceil_div(W, REGION_TILE);
-    const dim3 grid((unsigned)((int64_t)tiles_x * ceil_div(H, REGION_TILE)));
-    if (within_or_null != nullptr)
-      hipLaunchKernelGGL(k_region_geometry<true>, grid, dim3(CGC_BLOCK), 0, st, labels, within_or_null, within_bytes, H, W, tiles_x, max_label, g,
-                         meta);
-    else
-      hipLaunchKernelGGL(k_region_geometry<false>, grid, dim3(CGC_BLOCK), 0, st, labels, within_or_null, 0, H, W, tiles_x, max_label, g, meta);
+  if (!c.empty) {
+    region_launch(c, [&](auto within) {
+      hipLaunchKernelGGL(k_region_geometry<decltype(within)::value>, c.grid, dim3(CGC_BLOCK), 0, st, c.im, g, meta);
+    });
     CGC_RETURN_IF_LAUNCH_FAILED();
   }
   hipLaunchKernelGGL(k_geometry_finish, dim3(region_blocks(rows)), dim3(CGC_BLOCK), 0, st, rows, count, extents);

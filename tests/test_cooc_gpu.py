@@ -166,6 +166,20 @@ def test_exactly_as_many_labels_as_slots_and_one_more(extra):
     check(labels, values, symmetric=False, levels=7)
 
 
+def test_the_direct_route_with_within_on_partial_tiles():
+    t, S = geometry()
+    n = t + 6                                                           # even; four tiles, three of them partial
+    perm = np.random.RandomState(13).permutation(n * n // 2).astype(np.int32)
+    labels = perm[np.arange(n * n) // 2].reshape(n, n)                  # a label is two pixels side by side: far more than S per tile
+    values = np.random.RandomState(14).randint(0, 256, (n, n)).astype(np.uint8)
+    within = np.ones((n, n), np.int32)
+    within[:, ::3] = 0                                                  # every third column: it splits some of the pairs
+    offsets = ((0, 1), (0, -1), (1, 0))
+    for symmetric in (True, False):
+        got = check(labels, values, offsets=offsets, symmetric=symmetric, within=within)
+        assert got[:, 0].sum() == got[:, 1].sum() > 0 and got[:, 2].sum() == 0
+
+
 def test_labels_that_collide_in_the_hash():
     t, S = geometry()
     source = open(os.path.join(ROOT, 'cgc-net_amd', 'csrc', 'region.hip')).read()

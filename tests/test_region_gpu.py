@@ -104,6 +104,16 @@ def test_every_pixel_its_own_label(dtype):
     assert (st.count == 1).all() and np.array_equal(st.argmin.cpu().numpy()[labels.reshape(-1)], np.arange(n * n))
 
 
+def test_the_direct_route_with_within_on_partial_tiles():
+    t, S = geometry()
+    n = t + 6                                                           # four tiles, three of them partial; 64 labels of each fold
+    labels = np.random.RandomState(6).permutation(n * n).astype(np.int32).reshape(n, n)
+    values = np.random.RandomState(7).randint(0, 256, (n, n)).astype(np.uint8)
+    within = (np.indices((n, n)).sum(0) % 2).astype(np.int16)           # a checkerboard
+    st = check(labels, values, within=within)
+    assert np.array_equal(st.count.cpu().numpy()[labels.reshape(-1)], within.reshape(-1))
+
+
 @pytest.mark.parametrize('extra', [0, 1])
 def test_exactly_as_many_labels_as_slots_and_one_more(extra):
     t, S = geometry()

@@ -185,6 +185,15 @@ def test_every_pixel_its_own_label():
     check(np.random.RandomState(8).permutation((t + 6) * (t + 6)).astype(np.int32).reshape(t + 6, t + 6))
 
 
+def test_the_direct_route_with_within_on_partial_tiles():
+    t, S = sizes()
+    n = t + 6                                                           # four tiles, three of them partial; 64 labels of each fold
+    labels = np.random.RandomState(6).permutation(n * n).astype(np.int32).reshape(n, n)
+    within = (np.indices((n, n)).sum(0) % 2).astype(np.int16)           # a checkerboard: every pixel that belongs is a run of one
+    g = check(labels, within=within)
+    assert np.array_equal(g.count.cpu().numpy()[labels.reshape(-1)], within.reshape(-1))
+
+
 @pytest.mark.parametrize('extra', [0, 1])
 def test_exactly_as_many_labels_as_slots_and_one_more(extra):
     t, S = sizes()
