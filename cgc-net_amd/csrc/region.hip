@@ -2,6 +2,7 @@
 // HISTOGRAM (the 256 bins of a uint8 plane) and QUANTILES read off such histograms: KernelSpec.region_statistics / region_histogram /
 // region_quantiles; DESIGN.md, "Region statistics".  COOCCURRENCE (pairs of levels per offset): KernelSpec.region_cooccurrence; "Region
 // co-occurrence".  GEOMETRY (count, second-order sums, extents, quads, frame pixels): KernelSpec.region_geometry; "Region geometry".
+// HULL (the exact convex hull of a row's pixel squares, behind GEOMETRY): KernelSpec.region_hull; "Region hull".
 //
 // A pixel p is *counted* in row L (*belongs* to it) iff labels[p] == L, 0 <= L <= max_label, and within is null or non-zero at p.  A
 // pixel whose label lies outside [0, max_label] is *refused*: counted nowhere, one more in *meta (region_refused), `within` or not.
@@ -33,6 +34,8 @@
 //   GEOMETRY        k_geometry_init, k_region_geometry, k_geometry_finish.  The label every position belongs to is staged in LDS with
 //                   a frame of one position; runs are folded by closed forms in tile coordinates and shifted to the image on the way
 //                   to global memory (geom_add: the flush and the direct route), quads classified where their four positions differ.
+//   HULL            k_hull_spans_init, k_region_hull_spans, k_region_hull.  No table in LDS: per image row of a label's bounding box the
+//                   smallest and largest column, two atomics per run of a tile row; then a lane (a wave for a tall region) per label.
 #include <stdint.h>
 #include <type_traits>
 
@@ -643,6 +646,259 @@ __global__ void __launch_bounds__(CGC_BLOCK) k_geometry_finish(int rows, const i
   }
 }
 
+// HULL: the convex hull of the pixel SQUARES of every row (KernelSpec.region_hull; DESIGN.md, "Region hull").  Stage 1, a tile kernel:
+// per row L and image row y of its bounding box, the smallest and largest column of its pixels, spans[ptr[L] + y - y0[L]] = (xmin,
+// xmax); y0 is the extent (0, 1) of GEOMETRY, ptr the prefix sum of the bounding boxes' heights.  Stage 2, per region: the points of
+// the lattice lines, Andrew's monotone chain down the left side and up the right, then area, diameter, width and perimeter.
+constexpr int HULL_NONE = REGION_EMPTY;
+constexpr int HULL_NO_MIN = 0x7fffffff, HULL_NO_MAX = (int)0x80000000;      // an image row in which the label has no pixel
+// Rows above which a region is hulled by a whole wave, not by one lane (exported).  Measured on an MI355X (tools/hull_bench.py,
+// profiles/hull_bench.json), the two hull launches on an image that is ONE region of H rows, lane / wave, ms:
+//   every pixel        H = 64: 0.096 / 0.081   128: 0.134 / 0.092   256: 0.216 / 0.101   512: 0.393 / 0.110   1024: 0.743 / 0.119   4096: 3.05 / 0.227
+//   inscribed ellipse  H = 64: 0.434 / 0.143   128: 0.852 / 0.192   256: 1.203 / 0.240   512: 2.245 / 0.290   1024: 3.056 / 0.342   4096: 47.4 / 1.38
+// A lone region is never slower on the wave: the other 63 lanes had nothing to do anyway.  But a wave takes its tall regions one
+// after another, 0.06 to 0.15 ms each at 64 to 256 rows, where 64 lanes hull 64 such regions at once in 0.35 to 1.1 ms: the
+// threshold belongs above everything that comes in crowds -- a nucleus is tens of rows high -- and it bounds what one lane can cost,
+// 1.2 ms at 256 rows and twice that at 512.
+constexpr int HULL_TALL_ROWS = 256;
+
+struct HullPoint { int y, x; };          // a lattice corner, as the vertices are returned
+
+struct HullSpans {
+  const int64_t* ptr;                    // [R + 1]
+  const int* ext;                        // [R, 8, 2] of GEOMETRY
+  int* spans;                            // [total, 2]
+  int64_t total;
+};
+
+__global__ void __launch_bounds__(CGC_BLOCK) k_hull_spans_init(int64_t total, int* __restrict__ spans) {
+  for (int64_t i = (int64_t)blockIdx.x * CGC_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * CGC_BLOCK) {
+    spans[2 * i] = HULL_NO_MIN;
+    spans[2 * i + 1] = HULL_NO_MAX;
+  }
+}
+
+// One tile.  A wave is one row of it: a pixel is the first of a run where the lane to its left holds another row (or is none, or is
+// the tile's first column) and the last where the lane to its right does; only these send an atomic, two per run and tile row.
+template <bool WITHIN>
+__global__ void __launch_bounds__(CGC_BLOCK) k_region_hull_spans(RegionImage im, HullSpans hs) {
+  const RegionSpot sp = region_spot(im.tiles_x);
+  RegionColumn<int, WITHIN> c;
+  c.fetch(im, im.labels, sp, 0, 0);      // no second plane: the labels stand in for the values
+  c.judge(im);
+  unsigned lo = 0, hi = 0;               // bit k: pixel k starts a run of its image row; ends one
+#pragma unroll
+  for (int k = 0; k < REGION_BAND; ++k) {
+    const int L = (c.counted >> k & 1u) ? c.lab[k] : HULL_NONE;
+    const int left = __shfl_up(L, 1), right = __shfl_down(L, 1);
+    lo |= (unsigned)(L != HULL_NONE && (sp.lx == 0 || left != L)) << k;
+    hi |= (unsigned)(L != HULL_NONE && (sp.last_lane || right != L)) << k;
+  }
+#pragma unroll
+  for (int k = 0; k < REGION_BAND; ++k) {                           // unrolled: lab[k] stays in registers
+    if (!((lo | hi) >> k & 1u)) continue;
+    const int L = c.lab[k];
+    const int64_t p0 = hs.ptr[L], p1 = hs.ptr[L + 1];
+    const int64_t i = p0 + (sp.y0 + k - hs.ext[(int64_t)L * (GEOM_DIRS * 2) + 8]);
+    if (i < p0 || i >= p1 || i < 0 || i >= hs.total) continue;      // a ptr that does not fit the extents: nothing is written outside
+    if (lo >> k & 1u) atomicMin(&hs.spans[2 * i], sp.x);
+    if (hi >> k & 1u) atomicMax(&hs.spans[2 * i + 1], sp.x);
+  }
+}
+
+struct HullJob {
+  const int64_t* ptr;
+  const int* ext;
+  const int* spans;
+  HullPoint* points;                     // [2 (total + rows)]: row L owns 2 (h + 1) from 2 (ptr[L] + L), its vertices first
+  int64_t total;
+  int rows, tall;
+};
+struct HullTables {
+  int* count;                            // [R]
+  long long *area2, *diameter2;          // [R]
+  int* ends;                             // [R, 2, 2]
+  long long* width_cross;                // [R]
+  int* width_edge;                       // [R, 2]
+  double* perimeter;                     // [R]
+};
+
+// (a - o) x (b - o) with x to the right and y down the image: negative at every vertex of a hull listed down its left side first
+__device__ __forceinline__ long long hull_cross(HullPoint o, HullPoint a, HullPoint b) {
+  return (long long)(a.x - o.x) * (b.y - o.y) - (long long)(a.y - o.y) * (b.x - o.x);
+}
+// p onto the stack st[0 .. top): what p makes reflex or collinear is dropped first
+__device__ __forceinline__ void hull_push(HullPoint* st, int& top, HullPoint p) {
+  for (; top >= 2; --top)
+    if (hull_cross(st[top - 2], st[top - 1], p) < 0) break;
+  st[top++] = p;
+}
+// The chain of the points t0 .. t1 - 1 of one side, in hull order: point t of the left side lies on lattice line r = t (down the
+// image), of the right side on r = h - t (up).  Line r has the rows r - 1 and r of the label's h rows beside it; the point is the
+// outermost corner of both, and there is none between two rows without a pixel.  Returns the number of points left in st.
+template <bool LEFT>
+__device__ __forceinline__ int hull_side(const int* __restrict__ spans, int h, int y0, int t0, int t1, HullPoint* st) {
+  constexpr int NO = LEFT ? HULL_NO_MIN : HULL_NO_MAX, word = LEFT ? 0 : 1;
+  int top = 0;
+  for (int t = t0; t < t1; ++t) {
+    const int r = LEFT ? t : h - t;
+    const int a = r > 0 ? spans[2 * (r - 1) + word] : NO, b = r < h ? spans[2 * r + word] : NO;
+    const int x = LEFT ? (a < b ? a : b) : (a > b ? a : b);
+    if (x != NO) hull_push(st, top, HullPoint{y0 + r, LEFT ? x : x + 1});
+  }
+  return top;
+}
+
+// is ca / sqrt(la) < cb / sqrt(lb)?  ca^2 lb against cb^2 la, exactly: crosses reach 2^31 and squared lengths 2^31, the products 2^93
+__device__ __forceinline__ bool hull_narrower(u64 ca, u64 la, u64 cb, u64 lb) {
+  const u64 pa = ca * ca, pb = cb * cb;
+  const u64 ha = __umul64hi(pa, lb), hb = __umul64hi(pb, la);
+  return ((int)(ha < hb) | ((int)(ha == hb) & (int)(pa * lb < pb * la))) != 0;      // no branch: see hull_measure
+}
+
+// The tables of row L from its k >= 4 vertices v, by one lane (WAVE false) or by the 64 lanes of a wave.  Diameter and width are
+// scans over all pairs: a lattice polygon inside a square of side n has O(n^(2/3)) vertices, a nucleus some twenty.
+template <bool WAVE>
+__device__ __forceinline__ void hull_measure(const HullPoint* v, int k, int lane, const HullTables& out, int64_t L) {
+  constexpr int NL = WAVE ? CGC_WAVE : 1;
+  // the diameter: of equal pairs the smallest (i, j), i < j -- in a lane by the strict comparison, between lanes by i
+  long long bd = -1;
+  int bi = 0, bj = 0;
+  for (int i = lane; i < k; i += NL) {
+    const HullPoint a = v[i];
+    for (int j = i + 1; j < k; ++j) {
+      const long long dy = v[j].y - a.y, dx = v[j].x - a.x, d = dy * dy + dx * dx;
+      const bool far = d > bd;
+      bd = far ? d : bd, bi = far ? i : bi, bj = far ? j : bj;
+    }
+  }
+  // the width: per edge the farthest vertex, of equal widths the first edge
+  // The best edge travels as (c, |e|^2, e) through selects, and (dy, dx) is read off the vertices at the end: with the update
+  // written as a branch around five assignments, hipcc -O3 (ROCm 7) kept the OLD (dy, dx) on the path where the high halves of the
+  // two 128-bit products are equal and the low halves decide -- both are 0 for any nucleus -- while c and e were updated.
+  u64 bc = 0, bl = 0;
+  int be = -1;
+  for (int e = lane; e < k; e += NL) {
+    const HullPoint a = v[e], b = v[e + 1 < k ? e + 1 : 0];
+    const int dy = b.y - a.y, dx = b.x - a.x;
+    long long c = 0;
+    for (int j = 0; j < k; ++j) {
+      const long long cj = (long long)dy * (v[j].x - a.x) - (long long)dx * (v[j].y - a.y);
+      c = cj > c ? cj : c;
+    }
+    const u64 len = (u64)((long long)dy * dy + (long long)dx * dx);
+    const bool take = ((int)(be < 0) | (int)hull_narrower((u64)c, len, bc, bl)) != 0;
+    bc = take ? (u64)c : bc, bl = take ? len : bl, be = take ? e : be;
+  }
+  if (WAVE) {
+#pragma unroll
+    for (int m = 1; m < CGC_WAVE; m <<= 1) {
+      const long long od = __shfl_xor(bd, m);
+      const int oi = __shfl_xor(bi, m), oj = __shfl_xor(bj, m);
+      const bool far = ((int)(od > bd) | ((int)(od == bd) & (int)(oi < bi))) != 0;
+      bd = far ? od : bd, bi = far ? oi : bi, bj = far ? oj : bj;
+      const u64 oc = __shfl_xor(bc, m), ol = __shfl_xor(bl, m);
+      const int oe = __shfl_xor(be, m);
+      const int first = (int)!hull_narrower(bc, bl, oc, ol) & (int)(oe < be);      // as narrow, and earlier in hull order
+      const bool take = ((int)(oe >= 0) & ((int)(be < 0) | (int)hull_narrower(oc, ol, bc, bl) | first)) != 0;
+      bc = take ? oc : bc, bl = take ? ol : bl, be = take ? oe : be;
+    }
+  }
+  if (lane != 0) return;
+  long long s = 0;
+  double per = 0.0;
+  for (int i = 0; i < k; ++i) {                                     // in hull order
+    const HullPoint a = v[i], b = v[i + 1 < k ? i + 1 : 0];
+    s += (long long)a.x * b.y - (long long)b.x * a.y;
+    const long long dy = b.y - a.y, dx = b.x - a.x;
+    per += sqrt((double)(dy * dy + dx * dx));
+  }
+  out.count[L] = k;
+  out.area2[L] = -s;
+  out.diameter2[L] = bd;
+  out.ends[4 * L] = v[bi].y, out.ends[4 * L + 1] = v[bi].x, out.ends[4 * L + 2] = v[bj].y, out.ends[4 * L + 3] = v[bj].x;
+  const HullPoint ea = v[be < 0 ? 0 : be], eb = v[be + 1 < k ? be + 1 : 0];
+  out.width_cross[L] = (long long)bc;
+  out.width_edge[2 * L] = eb.y - ea.y, out.width_edge[2 * L + 1] = eb.x - ea.x;
+  out.perimeter[L] = per;
+}
+
+// A tall region, by a whole wave (uniform arguments): each lane hulls a 64th of the lines of both sides in place, lane 0 merges the 64
+// chains -- a chain of chains is hulled like a chain of points -- and the wave measures.  What one lane wrote is read by another
+// only behind a fence.
+__device__ __forceinline__ void hull_tall(const HullJob& job, const HullTables& out, int64_t L, int h, int64_t p0, int lane) {
+  HullPoint* st = job.points + 2 * (p0 + L);
+  const int* spans = job.spans + 2 * p0;
+  const int y0 = job.ext[L * (GEOM_DIRS * 2) + 8];
+  const int n = h + 1, per = (n + CGC_WAVE - 1) / CGC_WAVE;
+  const int t0 = lane * per < n ? lane * per : n, t1 = t0 + per < n ? t0 + per : n;
+  const int cl = hull_side<true>(spans, h, y0, t0, t1, st + t0);
+  const int cr = hull_side<false>(spans, h, y0, t0, t1, st + n + t0);
+  __threadfence();
+  int nl = 0, nr = 0;
+  for (int c = 0; c < CGC_WAVE; ++c) {                              // the stack never passes the point it reads: top <= c per + p
+    const int cnt = __shfl(cl, c);
+    if (lane == 0)
+      for (int p = 0; p < cnt; ++p) hull_push(st, nl, st[c * per + p]);
+  }
+  nl = __shfl(nl, 0);
+  for (int c = 0; c < CGC_WAVE; ++c) {                              // ... and nl <= n: the right side lands behind the left
+    const int cnt = __shfl(cr, c);
+    if (lane == 0)
+      for (int p = 0; p < cnt; ++p) hull_push(st + nl, nr, st[n + c * per + p]);
+  }
+  nr = __shfl(nr, 0);
+  __threadfence();
+  hull_measure<true>(st, nl + nr, lane, out, L);
+}
+
+// A lane per region up to job.tall rows; then the wave takes the taller ones among its 64 one after the other.
+__global__ void __launch_bounds__(CGC_BLOCK) k_region_hull(HullJob job, HullTables out) {
+  const int lane = threadIdx.x & (CGC_WAVE - 1);
+  const int64_t L = (int64_t)blockIdx.x * CGC_BLOCK + threadIdx.x;
+  int h = 0;
+  int64_t p0 = 0;
+  if (L < job.rows) {
+    const int64_t a = job.ptr[L], b = job.ptr[L + 1];
+    if (a >= 0 && b >= a && b <= job.total && b - a <= GEOM_MAX_SIDE) p0 = a, h = (int)(b - a);      // else: an empty row
+  }
+  const bool tall = h > job.tall;
+  if (L < job.rows && !tall) {
+    if (h == 0) {
+      out.count[L] = 0;
+      out.area2[L] = out.diameter2[L] = out.width_cross[L] = 0;
+      out.ends[4 * L] = out.ends[4 * L + 1] = out.ends[4 * L + 2] = out.ends[4 * L + 3] = 0;
+      out.width_edge[2 * L] = out.width_edge[2 * L + 1] = 0;
+      out.perimeter[L] = 0.0;
+    } else {
+      HullPoint* st = job.points + 2 * (p0 + L);
+      const int y0 = job.ext[L * (GEOM_DIRS * 2) + 8];
+      const int nl = hull_side<true>(job.spans + 2 * p0, h, y0, 0, h + 1, st);
+      const int nr = hull_side<false>(job.spans + 2 * p0, h, y0, 0, h + 1, st + nl);
+      hull_measure<false>(st, nl + nr, 0, out, L);
+    }
+  }
+  u64 todo = __ballot(tall);
+  for (int round = 0; round < CGC_WAVE && todo != 0; ++round) {
+    const int src = __builtin_ctzll(todo);
+    todo &= todo - 1;
+    hull_tall(job, out, L - lane + src, __shfl(h, src), __shfl(p0, src), lane);
+  }
+}
+
+struct HullWs {
+  HullPoint* points;
+};
+static inline HullWs hull_layout(Carver&& c, int64_t rows, int64_t span_rows) {
+  HullWs w;
+  w.points = c.take<HullPoint>(2 * (span_rows + rows));
+  return w;
+}
+// span_rows = ptr[R], read by the caller: no label has more rows than the image
+static inline bool bad_hull_rows(int max_label, int H, int64_t span_rows) {
+  return max_label < 0 || max_label == 0x7fffffff || H < 0 || H > GEOM_MAX_SIDE || span_rows < 0 || span_rows > ((int64_t)max_label + 1) * H;
+}
+
 }  // namespace
 
 extern "C" int cgc_region_tile_side(void) { return REGION_TILE; }
@@ -764,6 +1020,49 @@ extern "C" int cgc_region_geometry(const int* labels, const void* within_or_null
     CGC_RETURN_IF_LAUNCH_FAILED();
   }
   hipLaunchKernelGGL(k_geometry_finish, dim3(region_blocks(rows)), dim3(CGC_BLOCK), 0, st, rows, count, extents);
+  CGC_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}
+
+extern "C" int cgc_region_hull_tall_rows(void) { return HULL_TALL_ROWS; }
+
+extern "C" int64_t cgc_region_hull_ws_bytes(int max_label, int64_t span_rows) {
+  if (bad_hull_rows(max_label, GEOM_MAX_SIDE, span_rows)) return 0;
+  return layout_bytes(hull_layout, (int64_t)max_label + 1, span_rows);
+}
+
+extern "C" int cgc_region_hull_spans(const int* labels, const void* within_or_null, int within_bytes, int H, int W, int max_label,
+                                     const int* extents, const int64_t* ptr, int64_t span_rows, int* spans, cgc_stream_t stream) {
+  RegionCall c;
+  if (!region_call(c, labels, labels != nullptr, within_or_null, within_bytes, H, W, max_label)) return CGC_EINVAL;
+  if (W > GEOM_MAX_SIDE || bad_hull_rows(max_label, H, span_rows)) return CGC_EINVAL;
+  if (extents == nullptr || ptr == nullptr || (span_rows > 0 && spans == nullptr)) return CGC_EINVAL;
+  if (span_rows == 0) return 0;                                    // an empty image, or no label with a pixel
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(k_hull_spans_init, dim3(region_blocks(span_rows)), dim3(CGC_BLOCK), 0, st, span_rows, spans);
+  CGC_RETURN_IF_LAUNCH_FAILED();
+  const HullSpans hs{ptr, extents, spans, span_rows};
+  region_launch(c, [&](auto within) {
+    hipLaunchKernelGGL(k_region_hull_spans<decltype(within)::value>, c.grid, dim3(CGC_BLOCK), 0, st, c.im, hs);
+  });
+  CGC_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}
+
+extern "C" int cgc_region_hull(int max_label, int H, const int* extents, const int64_t* ptr, int64_t span_rows, const int* spans, void* ws,
+                               int tall_rows, int* count, int64_t* area2, int64_t* diameter2, int* diameter_ends, int64_t* width_cross,
+                               int* width_edge, double* perimeter, cgc_stream_t stream) {
+  if (bad_hull_rows(max_label, H, span_rows) || tall_rows < 0) return CGC_EINVAL;
+  if (extents == nullptr || ptr == nullptr || (span_rows > 0 && spans == nullptr) || ws == nullptr) return CGC_EINVAL;
+  if (count == nullptr || area2 == nullptr || diameter2 == nullptr || diameter_ends == nullptr || width_cross == nullptr ||
+      width_edge == nullptr || perimeter == nullptr)
+    return CGC_EINVAL;
+  const int rows = max_label + 1;
+  const HullWs w = hull_layout(Carver(ws), rows, span_rows);
+  const HullJob job{ptr, extents, spans, w.points, span_rows, rows, tall_rows > 0 ? tall_rows : HULL_TALL_ROWS};
+  const HullTables out{count, reinterpret_cast<long long*>(area2), reinterpret_cast<long long*>(diameter2), diameter_ends,
+                       reinterpret_cast<long long*>(width_cross), width_edge, perimeter};
+  hipLaunchKernelGGL(k_region_hull, dim3((unsigned)ceil_div64(rows, CGC_BLOCK)), dim3(CGC_BLOCK), 0, as_stream(stream), job, out);
   CGC_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }

@@ -652,6 +652,51 @@ class KernelSpec(object):
         "inside the image" is decided from coordinates.  Only quads whose four positions differ are classified."""
         raise NotImplementedError
 
+    def region_hull_ptr(self, count, extents):
+        """Where the row spans of region_hull lie: int64 [R + 1], ptr[0] = 0 and ptr[L + 1] - ptr[L] = the height y1 - y0 + 1 of the
+        bounding box of row L (extents[L][4] of region_geometry), 0 for a row with count 0.  A prefix sum on the device; no host
+        read.  The caller reads ptr[R] together with region_geometry's meta: the ONE host read of a hull call."""
+        raise NotImplementedError
+
+    def region_hull(self, labels, max_label, extents, ptr, span_rows, within=None, tall_rows=0):
+        """The exact convex hull of every region of a label image (F20, behind region_geometry; csrc/region.hip).  Returns ((count
+        int32 [R], area2 int64 [R], diameter2 int64 [R], diameter_ends int32 [R, 2, 2], width_cross int64 [R], width_edge int32 [R, 2],
+        perimeter float64 [R]), points int32 [2 (span_rows + R), 2]) with R = max_label + 1, all on the device; no host read.
+
+        1.  labels, max_label, within, "a pixel is *counted* in row L" and the refused pixels: items 1, 3 and 4 of region_statistics,
+            sides as item 1 of region_geometry.  extents: region_geometry's of the same labels and within; ptr: region_hull_ptr's of
+            them; span_rows = ptr[R], read by the caller.  span_rows < 0 or > R * H is a ValueError (the library returns CGC_EINVAL
+            and launches nothing); a ptr that does not fit the extents writes nothing outside the tables (such rows come out empty
+            or wrong, never out of bounds).
+        2.  THE HULL of row L is the convex hull of the pixel SQUARES of its counted pixels: the pixel at row y, column x is [x, x +
+            1] x [y, y + 1], so vertices are lattice corners (y, x) -- the convention of region_shape's feret_max, feret_min and
+            16-gon.  Hence hull area >= count, and a rectangle has solidity 1.  Tied to no library's version: skimage counts the
+            pixels inside the hull, cv2 hulls a contour.
+        3.  Vertices are strictly convex (none lies on the segment between its neighbours) and listed from the left end of the top
+            lattice line y = y0 down the left side, along the bottom line and up the right side, without repeats: the list is
+            unique.  count = their number, at least 4.  Row L's vertices are points[2 (ptr[L] + L) : 2 (ptr[L] + L) + count[L]]; the
+            rest of ``points`` is workspace.
+        4.  area2 = twice the area (shoelace, exact).  perimeter = the edge lengths sqrt(dy^2 + dx^2), each correctly rounded from
+            the integer, summed in hull order from vertex 0 in float64.
+        5.  diameter2 = the largest squared distance between two vertices; diameter_ends = those vertices (y, x).  TIE RULE: of
+            several pairs the one with the smallest vertex indices (i, j), i < j, in hull order (smallest i, then smallest j).
+        6.  The width of edge e = (v[e], v[e + 1]) with (dy, dx) = v[e + 1] - v[e] is c / |e|, c = the largest dy (x - x_e) - dx (y -
+            y_e) over all vertices (y, x) -- non-negative in this order.  width_cross, width_edge = c and (dy, dx) of the edge of
+            smallest width.  Two edges are compared as c_a^2 |e_b|^2 against c_b^2 |e_a|^2 EXACTLY: with sides up to 32767 the
+            crosses reach 2^31 and the products 2^93, so they are formed in 128 bits.  TIE RULE: the first edge in hull order.
+        7.  A row without a counted pixel has zeros everywhere and no vertices.  H * W = 0 gives such rows only.
+        8.  tall_rows: a region of more rows is hulled by a whole wave (each lane a 64th of the lattice lines, one lane merges the
+            64 chains), one of at most that many by one lane; 0 = the library's own threshold (``region_hull_tall_rows``); negative
+            is a ValueError.  Both routes give identical tables and vertices.
+        9.  Stage 1 uses integer minima and maxima only, stage 2 no atomics: bit-identical from call to call.
+        Inside the kernels ("Region hull"): stage 1, region_geometry's tile; per row L and image row y of its bounding
+        box spans[ptr[L] + y - y0] = (smallest, largest column of its counted pixels); a wave is one row of a tile and only the
+        first and last pixel of a run of one label (seen through a lane shuffle; a tile's first and last column always) send an
+        atomic.  Stage 2: lattice line j = y0 .. y1 + 1 has the left point (min(xmin[j-1], xmin[j]), j) and the right point
+        (max(xmax[j-1], xmax[j]) + 1, j) over the non-empty rows beside it; Andrew's monotone chain with int64 cross products, in
+        place in ``points``; then the scans of items 4 to 6."""
+        raise NotImplementedError
+
     def region_quantiles(self, hist, q10k):
         """Quantiles of the rows of a table of 256-bin histograms (F17; csrc/region.hip).  Returns uint8 [R, len(q10k)] on the device;
         no host read.
@@ -1032,6 +1077,7 @@ class HipKernels(KernelSpec):
         self.region_cooc_max_offset = int(self.lib.cgc_region_cooc_max_offset())      # largest |dy|, |dx| of region_cooccurrence
         self.region_cooc_max_offsets = int(self.lib.cgc_region_cooc_max_offsets())    # offsets per call
         self.region_geometry_max_side = int(self.lib.cgc_region_geometry_max_side())  # largest H, W of region_geometry
+        self.region_hull_tall_rows = int(self.lib.cgc_region_hull_tall_rows())        # rows above which a wave hulls a region
         self.scan_chunk = int(self.lib.cgc_scan_chunk_pixels())               # ... and of od_moments / angle_histogram
         self._dirs_checked = (None, None)                                      # angle_histogram's last direction table and its C array
         self._exp_checked = (None, None)                                       # od_recolor's last exponential table and its C array
@@ -1801,6 +1847,54 @@ class HipKernels(KernelSpec):
         self._chk(self.lib.cgc_region_geometry(_ptr(labels), *_within_args(within), H, W, max_label, _ptr(count), _ptr(sums), _ptr(extents),
                                                _ptr(quads), _ptr(border), _ptr(meta), self._stream()), 'cgc_region_geometry')
         return (count, sums, extents, quads, border), meta
+
+    def region_hull_ptr(self, count, extents):
+        self._dev(count, extents)
+        e = extents.to(torch.int64)
+        rows = torch.where(count > 0, e[:, 4, 1] - e[:, 4, 0] + 1, torch.zeros_like(e[:, 4, 0]))
+        ptr = torch.zeros(count.shape[0] + 1, dtype=torch.int64, device=count.device)
+        torch.cumsum(rows, 0, out=ptr[1:])
+        return ptr
+
+    @staticmethod
+    def _check_hull_rows(max_label, H, span_rows, tall_rows):
+        for name, v in (('span_rows', span_rows), ('tall_rows', tall_rows)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError('region_hull: %s must be a non-negative integer, got %r' % (name, v))
+        if span_rows > (max_label + 1) * H:
+            raise ValueError('region_hull: span_rows = %d does not fit %d labels of at most %d rows' % (span_rows, max_label + 1, H))
+
+    def region_hull(self, labels, max_label, extents, ptr, span_rows, within=None, tall_rows=0):
+        HipKernels._check_max_label('region_hull', max_label)
+        HipKernels._check_geometry_dims('region_hull', *labels.shape)
+        HipKernels._check_hull_rows(max_label, labels.shape[0], span_rows, tall_rows)
+        assert not labels.is_floating_point() and labels.dtype != torch.bool
+        if labels.dtype == torch.int64:                                         # as _region_inputs: what does not fit int32 stays refused
+            labels = labels.clamp(-1, max_label + 1)
+        labels, within = self._image(labels.to(torch.int32)), self._image(within)
+        assert within is None or within.shape == labels.shape
+        self._dev(extents, ptr)
+        H, W = labels.shape
+        dev = labels.device
+        R = max_label + 1
+        assert extents.dtype == torch.int32 and tuple(extents.shape) == (R, 8, 2) and extents.is_contiguous()
+        assert ptr.dtype == torch.int64 and tuple(ptr.shape) == (R + 1,) and ptr.is_contiguous()
+        spans = torch.empty(span_rows, 2, dtype=torch.int32, device=dev)
+        ws_bytes = int(self.lib.cgc_region_hull_ws_bytes(max_label, ctypes.c_int64(span_rows)))
+        assert ws_bytes >= 2 * (span_rows + R) * 8
+        points = torch.empty(ws_bytes // 8, 2, dtype=torch.int32, device=dev)
+        ints = torch.empty(R * 7, dtype=torch.int32, device=dev)                   # count, width_edge, diameter_ends
+        count, width_edge, ends = ints[:R], ints[R:3 * R].view(R, 2), ints[3 * R:].view(R, 2, 2)
+        wide = torch.empty(3, R, dtype=torch.int64, device=dev)                    # area2, diameter2, width_cross
+        perimeter = torch.empty(R, dtype=torch.float64, device=dev)
+        self._chk(self.lib.cgc_region_hull_spans(_ptr(labels), *_within_args(within), H, W, max_label, _ptr(extents), _ptr(ptr),
+                                                 ctypes.c_int64(span_rows), _ptr(spans) if span_rows else None, self._stream()),
+                  'cgc_region_hull_spans')
+        self._chk(self.lib.cgc_region_hull(max_label, H, _ptr(extents), _ptr(ptr), ctypes.c_int64(span_rows),
+                                           _ptr(spans) if span_rows else None, _ptr(points), tall_rows, _ptr(count), _ptr(wide[0]),
+                                           _ptr(wide[1]), _ptr(ends), _ptr(wide[2]), _ptr(width_edge), _ptr(perimeter), self._stream()),
+                  'cgc_region_hull')
+        return (count, wide[0], wide[1], ends, wide[2], width_edge, perimeter), points[:2 * (span_rows + R)]
 
     def region_quantiles(self, hist, q10k):
         q = HipKernels._check_q10k(q10k)

@@ -107,6 +107,12 @@ Nine of ``nucleus_features``' sixteen columns are shape too and keep the referen
 foreground, one contour that may belong to a neighbour); these describe the pixels of their own label only, also where nuclei touch:
     x = torch.cat([features, stain_features(...), texture_features(...), shape_features(L, kept, max_label=n)], 1)
 
+``region_hull`` is the one thing the geometry tables cannot give: the exact convex hull of the pixel squares of every label
+(kernels.KernelSpec.region_hull) -- its vertices, twice its area, its diameter with the end points, its minimum width and its
+perimeter, integers but for the last.  ``hull_shape`` reads true solidity and the true Feret diameters off it, and ``hull_features``
+is seven columns of them per nucleus -- what a nucleus cut at a neck by ``split_touching`` or ``watershed`` needs:
+    x = torch.cat([..., shape_features(L, kept, max_label=n), hull_features(L, kept, max_label=n)], 1)
+
 ``nucleus_features(labels, gray)`` returns the reference's ``feature`` / ``coordinate`` arrays of one image (csrc/nuclei.hip; the
 arithmetic item by item: kernels.KernelSpec.nucleus_features), ``graph_item`` turns them into the ``Data`` that
 ``_read_one_raw_graph`` builds, and ``save_reference_files`` writes them where the reference's dataset preparation reads them.
@@ -2081,6 +2087,143 @@ def shape_features(labels, kept_labels, max_label=None, within=None):
     if bad_kept:
         raise ValueError('%s: %d of kept_labels lie outside [0, %d]' % (fn, bad_kept, hi))
     return out
+
+
+RegionHull = collections.namedtuple('RegionHull', ('count', 'area2', 'diameter2', 'diameter_ends', 'width_cross', 'width_edge', 'perimeter',
+                                                   'vertices', 'ptr'))
+RegionHull.__new__.__defaults__ = (None, None)
+HullShape = collections.namedtuple('HullShape', ('convex_area', 'solidity', 'convex_perimeter', 'feret_max', 'feret_min', 'feret_ratio',
+                                                 'feret_angle', 'vertices'))
+HULL_FEATURE_NAMES = ('solidity', 'convex_area', 'convex_perimeter', 'feret_max', 'feret_min', 'feret_ratio', 'feret_angle')
+
+
+def _check_kept(fn, kept_labels, labels):
+    if not torch.is_tensor(kept_labels) or kept_labels.dtype not in (torch.int32, torch.int64):
+        raise TypeError('%s: kept_labels must be an int32 or int64 tensor' % fn)
+    if kept_labels.dim() != 1 or kept_labels.device != labels.device:
+        raise ValueError('%s: kept_labels must be 1-D and on the device of labels' % fn)
+
+
+def _hull_tables(fn, labels, max_label, within, kept_labels=None, tall_rows=0):
+    """The refusals of the hull functions, the geometry launch, the ONE host read -- the refused pixels, the rows of all bounding boxes
+    and, with kept_labels, how many of them lie outside [0, max_label] -- and the hull launches: (RegionGeometry, the tables of
+    kernels.KernelSpec.region_hull, points, ptr, max_label)."""
+    geometry, meta, hi = _geometry_tables(fn, labels, max_label, within)
+    with torch.cuda.device(labels.device):
+        ptr = kernels.get().region_hull_ptr(geometry.count, geometry.extents)
+    parts = [meta[0].to(torch.int64), ptr[-1]]
+    if kept_labels is not None:
+        kept = kept_labels.to(torch.int64)
+        parts.append(((kept < 0) | (kept > hi)).sum())
+    read = torch.stack(parts).tolist()                                # host sync: the refused pixels, the span rows
+    _refuse_labels(fn, read[0], hi)
+    if kept_labels is not None and read[2]:
+        raise ValueError('%s: %d of kept_labels lie outside [0, %d]' % (fn, read[2], hi))
+    with torch.cuda.device(labels.device):
+        tables, points = kernels.get().region_hull(labels, hi, geometry.extents, ptr, int(read[1]), within, tall_rows)
+    return geometry, tables, points, ptr, hi
+
+
+def region_hull(labels, max_label=None, within=None, return_vertices=False):
+    """The exact convex hull of every region of a label image (csrc/region.hip; the contract item by item:
+    kernels.KernelSpec.region_hull).  labels, max_label, within and the limits on the sides: as region_geometry.
+
+    THE HULL of label L is the convex hull of the pixel SQUARES of its counted pixels: the pixel at row y, column x is the square [x, x
+    + 1] x [y, y + 1], so hull vertices are lattice corners -- the convention ``region_shape``'s feret_max, feret_min and 16-gon already
+    use.  It follows that hull area >= count, and that solidity is 1 for a rectangle.  The definition is tied to no library's version:
+    skimage counts the pixels inside a hull, cv2 hulls a contour.  Returns the named tuple ``RegionHull``, every table indexed by label
+    value -- row 0 is the background, a region like any other:
+
+      count          int32 [R]        the number of hull vertices (at least 4)
+      area2          int64 [R]        twice the hull's area (shoelace)
+      diameter2      int64 [R]        the largest squared distance between two vertices: the maximum Feret diameter, squared
+      diameter_ends  int32 [R, 2, 2]  its two end points as (y, x).  Of several pairs that attain it, the one with the smallest vertex
+                                      indices (i, j), i < j, in hull order
+      width_cross    int64 [R]        the minimum width is width_cross / |width_edge|: over the hull's edges e = (dy, dx) the smallest
+      width_edge     int32 [R, 2]     of c / |e|, c = the largest dy (x - x_e) - dx (y - y_e) over the vertices; edges are compared
+                                      exactly (c_a^2 |e_b|^2 against c_b^2 |e_a|^2 in 128 bits), of equal widths the first in hull order
+      perimeter      float64 [R]      the edge lengths sqrt(dy^2 + dx^2) summed in hull order
+
+    and, with ``return_vertices``, ``vertices`` int32 [V, 2] as (y, x) and ``ptr`` int64 [R + 1]: label L's vertices are
+    vertices[ptr[L]:ptr[L + 1]], strictly convex (none on the segment between its neighbours), listed from the left end of the top
+    lattice line down the left side, along the bottom and up the right side, without repeats -- the list is unique.  Both are None
+    otherwise.  A label without a counted pixel has zeros everywhere and no vertices.  Exact integers but for the perimeter (correctly
+    rounded square roots, one addition each), bit-identical from call to call.
+
+    Host syncs: as region_geometry -- the label range unless ``max_label`` is given, and ONE read that brings the refused pixels
+    (ValueError) and the number of rows of all bounding boxes, which sizes the second launch.  ``return_vertices`` adds one read: V."""
+    geometry, tables, points, rows, hi = _hull_tables('region_hull', labels, max_label, within)
+    if not return_vertices:
+        return RegionHull(*tables)
+    count = tables[0].to(torch.int64)
+    ptr = torch.zeros(hi + 2, dtype=torch.int64, device=count.device)
+    torch.cumsum(count, 0, out=ptr[1:])
+    total = int(ptr[-1].item())                                          # host sync: the number of vertices
+    first = 2 * (rows[:-1] + torch.arange(hi + 1, device=count.device))  # where each label's vertices start in ``points``
+    index = torch.repeat_interleave(first - ptr[:-1], count, output_size=total) + torch.arange(total, device=count.device)
+    return RegionHull(*tables, vertices=points[index], ptr=ptr)
+
+
+def hull_shape(hull, geometry):
+    """Shape properties from a ``RegionHull`` and the ``RegionGeometry`` of the same labels: the named tuple ``HullShape`` of tables
+    [R], float32, computed in float64 on the tables' device from the integers and rounded once, as ``region_shape`` does.  Rows with
+    count 0 are 0 everywhere.  With n = geometry.count:
+
+      convex_area       area2 / 2
+      solidity          n / convex_area: area over hull area, at most 1 and 1 for a rectangle -- what ``region_shape``'s convexity16
+                        bounds from below
+      convex_perimeter  perimeter
+      feret_max         sqrt(diameter2): the largest distance between two points of the pixel squares
+      feret_min         width_cross / |width_edge|: the smallest distance between two parallel lines that enclose them
+      feret_ratio       feret_min / feret_max
+      feret_angle       the angle of the diameter from +x towards +y (y points down the image), ``region_shape``'s convention for
+                        ``orientation``: atan2(dy, dx) of the vector between diameter_ends turned so that dx > 0, or dx = 0 and dy > 0,
+                        in (-pi/2, pi/2]
+      vertices          count
+
+    Host syncs: none."""
+    if not isinstance(hull, RegionHull) or not isinstance(geometry, RegionGeometry):
+        raise TypeError('hull_shape takes the RegionHull of region_hull and the RegionGeometry of region_geometry')
+    if hull.count.shape != geometry.count.shape or hull.count.device != geometry.count.device:
+        raise ValueError('hull_shape: the hull and the geometry must describe the same labels (%d and %d rows)'
+                         % (hull.count.shape[0], geometry.count.shape[0]))
+    f64 = torch.float64
+    some = hull.count > 0
+    one = torch.ones(hull.count.shape, dtype=f64, device=hull.count.device)
+    area = hull.area2.to(f64) * 0.5
+    fmax = hull.diameter2.to(f64).sqrt()
+    e = hull.width_edge.to(f64)
+    fmin = hull.width_cross.to(f64) / torch.where(some, (e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]).sqrt(), one)
+    d = (hull.diameter_ends[:, 1] - hull.diameter_ends[:, 0]).to(f64)
+    flip = (d[:, 1] < 0) | ((d[:, 1] == 0) & (d[:, 0] < 0))
+    d = torch.where(flip[:, None], -d, d)
+
+    def f32(t):
+        return torch.where(some, t, torch.zeros_like(t)).to(torch.float32)
+
+    return HullShape(convex_area=f32(area), solidity=f32(geometry.count.to(f64) / torch.where(some, area, one)),
+                     convex_perimeter=f32(hull.perimeter), feret_max=f32(fmax), feret_min=f32(fmin),
+                     feret_ratio=f32(fmin / torch.where(some, fmax, one)), feret_angle=f32(torch.atan2(d[:, 0], d[:, 1])),
+                     vertices=f32(hull.count.to(f64)))
+
+
+def hull_features(labels, kept_labels, max_label=None, within=None):
+    """Hull features per nucleus, to put beside ``shape_features``: float32 [len(kept_labels), 7]; ``HULL_FEATURE_NAMES`` names the
+    columns -- ``hull_shape``'s solidity, convex_area, convex_perimeter, feret_max, feret_min, feret_ratio and feret_angle.  labels,
+    kept_labels, within: as shape_features; row k describes label kept_labels[k], a label without a pixel gives a row of zeros.  Each
+    row describes the pixels of its own label only, also where nuclei touch or were cut apart:
+
+        x = torch.cat([..., shape_features(L, kept, max_label=n), hull_features(L, kept, max_label=n)], 1)
+
+    Host syncs: as shape_features -- the label range unless ``max_label`` is given, and one read that brings the refused pixels, the
+    check of kept_labels and the rows of the bounding boxes: labels or kept_labels outside [0, max_label] raise ValueError."""
+    fn = 'hull_features'
+    _check_image(fn, 'labels', labels, _INT_DTYPES)
+    _check_kept(fn, kept_labels, labels)
+    geometry, tables, _, _, hi = _hull_tables(fn, labels, max_label, within, kept_labels)
+    s = hull_shape(RegionHull(*tables), geometry)
+    table = torch.stack([getattr(s, name) for name in HULL_FEATURE_NAMES], dim=1)
+    return table[kept_labels.to(torch.int64)]
 
 
 def clear_border(labels, max_label=None):

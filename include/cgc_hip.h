@@ -85,8 +85,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *  24: region co-occurrence (per label value and offset: the grey-level co-occurrence table of a uint8 plane over pairs of pixels of
  *      one region): cgc_region_cooc_max_offset, cgc_region_cooc_max_offsets, cgc_region_cooccurrence
  *  25: region geometry (per label value: count, coordinate sums, extents in eight directions, bit-quad counts, pixels on the image
- *      frame): cgc_region_geometry_max_side, cgc_region_geometry */
-#define CGC_ABI_VERSION 25
+ *      frame): cgc_region_geometry_max_side, cgc_region_geometry
+ *  26: region hull (per label value: the exact convex hull of its pixel squares -- vertices, area, diameter with end points, minimum
+ *      width, perimeter): cgc_region_hull_tall_rows, cgc_region_hull_ws_bytes, cgc_region_hull_spans, cgc_region_hull */
+#define CGC_ABI_VERSION 26
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -544,6 +546,42 @@ int cgc_region_cooccurrence(const int* labels, const uint8_t* values, const void
 int cgc_region_geometry_max_side(void);
 int cgc_region_geometry(const int* labels, const void* within_or_null, int within_bytes, int H, int W, int max_label, int* count,
                         int64_t* sums, int* extents, int* quads, int* border, int* meta, cgc_stream_t stream);
+
+/* ---- F20 (behind F19, csrc/region.hip): the exact convex hull of every region of a label image.  The per-label form of the
+ * hull behind the reference's solidity (cv2.convexHull of one contour, dataflow/construct_feature_graph.py:84-88).  The contract item by item:
+ * cgc-net_amd/kernels.py KernelSpec.region_hull.  labels, max_label, within_or_null and "a pixel is counted in row L" as F17, sides
+ * as F19.  THE HULL of row L is the convex hull of the pixel SQUARES [x, x + 1] x [y, y + 1] of its counted pixels; vertices are
+ * lattice corners (y, x), strictly convex, listed from the left end of the top lattice line down the left side, along the bottom and
+ * up the right side, without repeats.  A hull call is three steps on one stream:
+ *   cgc_region_geometry first.  extents = its table; ptr int64 [R + 1] = the caller's prefix sum of the bounding boxes' heights (ptr[0] =
+ *     0, ptr[L + 1] - ptr[L] = extents[L][4][1] - extents[L][4][0] + 1, or 0 where count[L] = 0); span_rows = ptr[R], which the caller
+ *     reads together with F19's *meta.
+ *   cgc_region_hull_spans: spans int32 [span_rows, 2]; spans[ptr[L] + y - y0] = (smallest, largest column of the counted pixels of row
+ *     L in image row y), (INT32_MAX, INT32_MIN) where it has none.  One workgroup per tile as F17; integer minima and maxima only.
+ *   cgc_region_hull: ws = cgc_region_hull_ws_bytes(max_label, span_rows) bytes, 2 (span_rows + R) points (y, x) of two int32; on
+ *     return row L's vertices are the first count[L] points from point 2 (ptr[L] + L), the rest is scratch.  Out, per row:
+ *       count          int32 [R]        the number of vertices (>= 4), 0 for a row without a counted pixel -- such a row has zeros everywhere
+ *       area2          int64 [R]        twice the area (shoelace)
+ *       diameter2      int64 [R]        the largest squared distance between two vertices
+ *       diameter_ends  int32 [R, 2, 2]  its two ends (y, x); of equal pairs the one with the smallest vertex indices (i, j), i < j, in
+ *                                       hull order
+ *       width_cross    int64 [R]        c of the edge of smallest width c / |e|, where for the edge e = v[i + 1] - v[i] = (dy, dx) c is
+ *                                       the largest dy (x - x_i) - dx (y - y_i) over the vertices (y, x)
+ *       width_edge     int32 [R, 2]     (dy, dx) of that edge.  Edges are compared as c_a^2 |e_b|^2 against c_b^2 |e_a|^2 in 128 bits,
+ *                                       exactly; of equal widths the first edge in hull order
+ *       perimeter      double [R]       the edge lengths sqrt(dy^2 + dx^2), correctly rounded, summed in hull order
+ *     tall_rows: a region of more rows than this is hulled by a whole wave, others by one lane; 0 = cgc_region_hull_tall_rows().  Both
+ *     routes give identical tables.  H is the image's, as given to cgc_region_hull_spans.
+ * Bit-identical from call to call.  Bad dims, max_label, within_bytes, a side above 32767, span_rows < 0 or > R * H, tall_rows < 0 or a
+ * null pointer where one is needed: CGC_EINVAL, nothing launched; a ptr that does not fit the extents writes nothing outside the tables.
+ * H * W = 0 or span_rows = 0: rows of zeros. */
+int cgc_region_hull_tall_rows(void);
+int64_t cgc_region_hull_ws_bytes(int max_label, int64_t span_rows);
+int cgc_region_hull_spans(const int* labels, const void* within_or_null, int within_bytes, int H, int W, int max_label, const int* extents,
+                          const int64_t* ptr, int64_t span_rows, int* spans, cgc_stream_t stream);
+int cgc_region_hull(int max_label, int H, const int* extents, const int64_t* ptr, int64_t span_rows, const int* spans, void* ws,
+                    int tall_rows, int* count, int64_t* area2, int64_t* diameter2, int* diameter_ends, int64_t* width_cross, int* width_edge,
+                    double* perimeter, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
