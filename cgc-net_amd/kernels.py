@@ -48,6 +48,10 @@ COOC_MAX_PIXELS = 2 ** 30  # ... a symmetric diagonal bin holds at most 2 H W an
 GEOMETRY_MAX_SIDE = 32767  # region_geometry: largest H, W (cgc_region_geometry_max_side): sum x^2 over 2^31 pixels fits int64
 GEOMETRY_DIRECTIONS = ((1, 0), (2, 1), (1, 1), (1, 2), (0, 1), (-1, 2), (-1, 1), (-2, 1))      # (a, b) of the extents a x + b y
 REGION_VALUE_DTYPES = {torch.uint8: (1, 0), torch.int8: (1, 1), torch.int16: (2, 1), torch.int32: (4, 1)}      # (bytes, signed)
+RESAMPLE_MAX_SIDE = 32767  # resample_u8 / resample_labels: largest source and output side (cgc_resample_max_side): (2 d + 1) n < 2^31
+RESAMPLE_LABELS_MAX_FACTOR = 8      # resample_labels 'majority': largest n / m per axis (cgc_resample_labels_max_factor): a box spans <= 9 pixels
+RESAMPLE_MODES = {'linear': 0, 'area': 1}              # include/cgc_hip.h: CGC_RESAMPLE_LINEAR / _AREA
+RESAMPLE_LABEL_MODES = {'nearest': 0, 'majority': 1}   # CGC_RESAMPLE_NEAREST / _MAJORITY (2 = _MAJORITY_UNSIGNED: uint8 and bool)
 WS_JUMP_BATCH = 8        # pointer jumps of watershed_flood per host read: resolves parent chains of up to 2^7 pixels in one read
 
 
@@ -399,6 +403,58 @@ class KernelSpec(object):
         A lane takes 4 pixels as three dwords and stores three dwords (bytes on an unaligned base and on the last 1-3 pixels); both
         tables sit in LDS, the exponential one as bytes; the matrix stays in scalar registers.  The exponential table reaches the
         device as angle_histogram's directions do: small launches carry it as kernel arguments into a workspace."""
+        raise NotImplementedError
+
+    def resample_u8(self, image, size, mode):
+        """The pixel size of one uint8 plane or interleaved tile (F21; csrc/resample.hip).  Returns uint8 [H2, W2] or [H2, W2, 3],
+        contiguous; one launch, no workspace, no host read.  Below n is a source side and m the output side of the same axis; the axes
+        are independent.
+
+        1.  Sides.  image: uint8 [H, W] or [H, W, 3], any strides; size = (H2, W2); 1 <= n, m <= 32767 (``RESAMPLE_MAX_SIDE``,
+            cgc_resample_max_side()) on both axes, anything else is a ValueError before any launch (the library: CGC_EINVAL, nothing
+            launched).  A source with H * W = 0 is a ValueError.  size == image.shape[:2] is an ordinary case and returns an equal
+            copy in every mode.
+        2.  Geometry.  Pixel centres sit at half-integers (cv2, PIL, scipy.ndimage.zoom(grid_mode=True)).  Output index d samples the
+            source at s = ((2 d + 1) n - m) / (2 m), clamped to [0, n - 1] (the border is replicated): with num = clamp((2 d + 1) n -
+            m, 0, 2 m (n - 1)), i0 = floor(num / (2 m)), i1 = min(i0 + 1, n - 1) and the fraction numerator f = num - i0 * 2 m over
+            2 m.  (2 d + 1) n reaches 65533 * 32767 = 2^31 - 163837: it comes within 2 * 10^5 of the int32 limit and is computed in
+            uint32, as is 2 m (n - 1) < 2^31.
+        3.  mode 'linear'.  out = floor((2 S + D) / (2 D)) with S = sum over the four neighbours of p * wy * wx, wx in {2 W2 - fx, fx},
+            wy in {2 H2 - fy, fy}, D = 4 H2 W2: exact rational bilinear interpolation with ONE rounding, half up, in 64 bits (255 *
+            2^32 < 2^40).  It does no prefiltering, so it aliases below half size, where 'area' is the mode to use.  cv2.resize's
+            INTER_LINEAR works with 11-bit fixed-point weights and can differ from it by one level (the documented reason for stating
+            the arithmetic here; not a tested claim).
+        4.  mode 'area'.  Requires H2 <= H and W2 <= W (ValueError otherwise).  Output index d owns the source interval [d n / m,
+            (d + 1) n / m); in units of 1 / m of a pixel source pixel i has weight o_i = min((d + 1) n, (i + 1) m) - max(d n, i m),
+            positive for i = floor(d n / m) .. floor(((d + 1) n - 1) / m); the weights sum to n.  out = floor((2 S + D) / (2 D)) with
+            S = sum p * oy * ox and D = H W.  For integer factors this is the rounded block mean.
+        5.  Colour.  The three channels of [H, W, 3] are resampled independently, each by items 2 to 4; the tile is read interleaved.
+        8.  Purity.  Every result is a pure function of the input and bit-identical from call to call: integers only, no atomics, no
+            float arithmetic.
+        (Items 6 and 7 are resample_labels'.)  A lane produces 4 adjacent output pixels and stores them as one dword (three for a
+        tile); the groups start where the row's address is a multiple of 4, so only the first and last 1-3 pixels of a row's share
+        are written as bytes.  'area' walks a box with one lane: neighbouring lanes own neighbouring boxes."""
+        raise NotImplementedError
+
+    def resample_labels(self, labels, size, mode):
+        """The pixel size of one label image (F21; csrc/resample.hip).  Returns [H2, W2] of the input's dtype, contiguous; one launch,
+        no workspace, no host read.  n, m and the geometry as resample_u8.
+
+        1.  Sides.  labels: bool or a 1-, 2-, 4- or 8-byte integer type, [H, W], any strides; size = (H2, W2); 1 <= n, m <= 32767 on
+            both axes, a source with H * W = 0 included in the refusal (ValueError before any launch; the library: CGC_EINVAL, nothing
+            launched).  size == labels.shape is an ordinary case and returns an equal copy in both modes.
+        2.  Geometry.  Pixel centres at half-integers, exactly as resample_u8's item 2; (2 d + 1) n is computed in uint32.
+        6.  mode 'nearest'.  out[d] = src[floor((2 d + 1) n / (2 m))] per axis; the index is always in range.  An element of 1, 2, 4
+            or 8 bytes is copied as it is.  Upscaling by an integer k is np.repeat along both axes.
+        7.  mode 'majority'.  Requires H2 <= H, W2 <= W, H <= 8 H2 and W <= 8 W2 (``RESAMPLE_LABELS_MAX_FACTOR``,
+            cgc_resample_labels_max_factor(); ValueError otherwise).  Among the source pixels of the box of resample_u8's item 4 the
+            output takes the VALUE with the largest total weight sum oy * ox; the value 0 is a candidate like any other.  Ties go to the
+            smallest value: values compare as integers of the dtype (int8 .. int64 signed, uint8 unsigned), bool as 0 / 1.  A box
+            spans at most 9 pixels per axis, and its weights sum to H W < 2^30.
+        8.  Purity.  A pure function of the input, bit-identical from call to call: integers only, no atomics, no float arithmetic.
+        (Items 3 to 5 are resample_u8's.)  The library takes the element size; the unsigned order of uint8 and bool is its mode
+        CGC_RESAMPLE_MAJORITY_UNSIGNED.  A box of one value -- the inside of a nucleus, the background -- is decided by one walk over
+        it; a mixed box weighs every distinct candidate with a second walk, in registers."""
         raise NotImplementedError
 
     def binomial_smooth(self, image, radius):
@@ -1082,6 +1138,8 @@ class HipKernels(KernelSpec):
         self._dirs_checked = (None, None)                                      # angle_histogram's last direction table and its C array
         self._exp_checked = (None, None)                                       # od_recolor's last exponential table and its C array
         assert int(self.lib.cgc_angle_bins()) == ANGLE_BINS
+        assert int(self.lib.cgc_resample_max_side()) == RESAMPLE_MAX_SIDE
+        assert int(self.lib.cgc_resample_labels_max_factor()) == RESAMPLE_LABELS_MAX_FACTOR
 
     # -- helpers
     @staticmethod
@@ -1566,6 +1624,51 @@ class HipKernels(KernelSpec):
         self._chk(self.lib.cgc_od_recolor(_ptr(image), ctypes.c_int64(H * W), int(order), (ctypes.c_int * 256)(*lut),
                                           (ctypes.c_int * 9)(*a), exp_c, EXP_LUT_LEN, _ptr(ws), _ptr(out), self._stream()),
                   'cgc_od_recolor')
+        return out
+
+    @staticmethod
+    def _check_resample(fn, shape, size, mode, modes):
+        """The refusals of resample_u8 / resample_labels, which need no tensor: returns (H2, W2, the library's mode)."""
+        if not isinstance(mode, str) or mode not in modes:
+            raise ValueError('%s: mode must be %s, got %r' % (fn, ' or '.join(repr(k) for k in modes), mode))
+        try:
+            H2, W2 = (operator.index(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError('%s: size must be a pair of integers (H2, W2), got %r' % (fn, size))
+        H, W = int(shape[0]), int(shape[1])
+        if H < 1 or W < 1:
+            raise ValueError('%s: the image must not be empty (got %d x %d)' % (fn, H, W))
+        if max(H, W) > RESAMPLE_MAX_SIDE:
+            raise ValueError('%s: the image may have sides up to %d (got %d x %d)' % (fn, RESAMPLE_MAX_SIDE, H, W))
+        if not (1 <= H2 <= RESAMPLE_MAX_SIDE and 1 <= W2 <= RESAMPLE_MAX_SIDE):
+            raise ValueError('%s: size must lie in 1..%d on both axes (got %d x %d)' % (fn, RESAMPLE_MAX_SIDE, H2, W2))
+        if mode in ('area', 'majority') and (H2 > H or W2 > W):
+            raise ValueError("%s: mode %r only shrinks: size %d x %d exceeds the image's %d x %d" % (fn, mode, H2, W2, H, W))
+        if mode == 'majority' and (H > RESAMPLE_LABELS_MAX_FACTOR * H2 or W > RESAMPLE_LABELS_MAX_FACTOR * W2):
+            raise ValueError("%s: mode 'majority' shrinks by at most %d per axis (size %d x %d from %d x %d): repeat the call"
+                             % (fn, RESAMPLE_LABELS_MAX_FACTOR, H2, W2, H, W))
+        return H2, W2, modes[mode]
+
+    def resample_u8(self, image, size, mode):
+        H2, W2, code = HipKernels._check_resample('resample_u8', image.shape, size, mode, RESAMPLE_MODES)
+        self._dev(image)
+        assert image.dtype == torch.uint8 and (image.dim() == 2 or (image.dim() == 3 and image.shape[2] == 3))
+        image = image.contiguous()
+        H, W = image.shape[:2]
+        out = torch.empty((H2, W2) + tuple(image.shape[2:]), dtype=torch.uint8, device=image.device)
+        self._chk(self.lib.cgc_resample_u8(_ptr(image), H, W, 1 if image.dim() == 2 else 3, H2, W2, code, _ptr(out), self._stream()),
+                  'cgc_resample_u8')
+        return out
+
+    def resample_labels(self, labels, size, mode):
+        H2, W2, code = HipKernels._check_resample('resample_labels', labels.shape, size, mode, RESAMPLE_LABEL_MODES)
+        labels = self._image(labels)
+        if code == 1 and labels.dtype in (torch.uint8, torch.bool):
+            code = 2                                                            # CGC_RESAMPLE_MAJORITY_UNSIGNED
+        H, W = labels.shape
+        out = torch.empty(H2, W2, dtype=labels.dtype, device=labels.device)
+        self._chk(self.lib.cgc_resample_labels(_ptr(labels), labels.element_size(), H, W, H2, W2, code, _ptr(out), self._stream()),
+                  'cgc_resample_labels')
         return out
 
     def binomial_smooth(self, image, radius):

@@ -113,13 +113,27 @@ perimeter, integers but for the last.  ``hull_shape`` reads true solidity and th
 is seven columns of them per nucleus -- what a nucleus cut at a neck by ``split_touching`` or ``watershed`` needs:
     x = torch.cat([..., shape_features(L, kept, max_label=n), hull_features(L, kept, max_label=n)], 1)
 
+``resize``, ``rescale``, ``resize_labels``, ``rescale_labels`` and ``scale_points`` change the pixel size of a tile, a plane, a label
+image and the coordinates that go with them (csrc/resample.hip; kernels.KernelSpec.resample_u8, resample_labels).  Every length of
+the stage is a number of pixels -- radii, ``ring``, ``max_distance``, the area, axis and perimeter columns -- so tiles scanned at
+another magnification are brought to one working resolution first, and a cheap coarse pass (an Otsu floor, a tissue mask,
+``estimate_stains``) runs on an area-mean downscale:
+    norm = normalize_stains(rescale(tile, Fraction(1, 2), 'area'))
+Pixel centres sit at half-integers (cv2, PIL); 'linear' is exact rational bilinear interpolation with one rounding, 'area' the exact
+box mean, 'nearest' and 'majority' keep label values -- integers with a stated contract like everything else here.  A mask from a
+segmentation network that ran at another resolution than the tile meets the gray image either way round:
+``nucleus_features(L, resize(gray, L.shape))`` is the reference's dataflow/construct_feature_graph.py:61, and
+``resize_labels(L, gray.shape)`` keeps the tile's resolution instead.
+
 ``nucleus_features(labels, gray)`` returns the reference's ``feature`` / ``coordinate`` arrays of one image (csrc/nuclei.hip; the
 arithmetic item by item: kernels.KernelSpec.nucleus_features), ``graph_item`` turns them into the ``Data`` that
 ``_read_one_raw_graph`` builds, and ``save_reference_files`` writes them where the reference's dataset preparation reads them.
 
 Differences from the reference, all stated: an image without a surviving nucleus gives empty tensors (the reference's
 ``np.vstack`` raises); labels must be non-negative (``ValueError``, as skimage); gray and mask must have the same size
-(``ValueError``; the reference resizes, which is the identity then).  OpenCV, scikit-image and xtract-features are restated from their
+(``ValueError``; the reference resizes the gray image to the mask with cv2's bilinear interpolation, line 61 -- here that step is
+spelled out, ``nucleus_features(L, resize(gray, L.shape))``, with exact weights where cv2 rounds them to 11 bits, and
+``nucleus_features`` itself keeps its ``ValueError``).  OpenCV, scikit-image and xtract-features are restated from their
 documented behaviour, not linked: see DESIGN.md, "Nucleus features".
 """
 import collections
@@ -910,6 +924,108 @@ def smooth(image, radius):
     radius = _check_radius(radius)
     with torch.cuda.device(image.device):
         return kernels.get().binomial_smooth(image, radius)
+
+
+RESAMPLE_MAX_SIDE = kernels.RESAMPLE_MAX_SIDE                       # largest side of resize / resize_labels, source and output
+RESAMPLE_LABELS_MAX_FACTOR = kernels.RESAMPLE_LABELS_MAX_FACTOR     # largest shrink per axis and call of resize_labels(..., 'majority')
+
+
+def _check_u8_image(fn, image):
+    """A uint8 plane [H, W] or tile [H, W, 3] on the GPU."""
+    if torch.is_tensor(image) and image.dim() == 3:
+        _check_color(fn, image)
+    else:
+        _check_image(fn, 'image', image, (torch.uint8,))
+
+
+def resize(image, size, mode='linear'):
+    """A uint8 [H, W] plane or uint8 [H, W, 3] tile on the GPU (any strides) at another pixel size: ``size`` = (H2, W2), every side in
+    1..32767.  ``mode`` 'linear': exact rational bilinear interpolation with pixel centres at half-integers, the border replicated, one
+    rounding (half up) -- no prefiltering, so it aliases below half size; 'area': the exact mean over the source box of every output
+    pixel, pixels weighted by their overlap (shrinking only; for integer factors the rounded block mean).  The channels of a tile are
+    resampled independently.  Returns a contiguous uint8 tensor of the new size; ``size == image.shape[:2]`` returns an equal copy.  The
+    contract item by item: kernels.KernelSpec.resample_u8.  ``nucleus_features(L, resize(gray, L.shape))`` is the reference's
+    dataflow/construct_feature_graph.py:61.
+
+    Host syncs: none."""
+    _check_u8_image('resize', image)
+    kernels.HipKernels._check_resample('resize', image.shape, size, mode, kernels.RESAMPLE_MODES)
+    with torch.cuda.device(image.device):
+        return kernels.get().resample_u8(image, size, mode)
+
+
+def resize_labels(labels, size, mode='nearest'):
+    """A bool or integer [H, W] label image on the GPU (any strides) at another pixel size: ``size`` = (H2, W2), every side in 1..32767.
+    ``mode`` 'nearest': every output pixel copies the source pixel under its centre (integer upscaling is np.repeat on both axes);
+    'majority': it takes the value that covers most of its source box, 0 included, ties to the smallest value -- shrinking only, by at
+    most 8 per axis and call.  Returns the input's dtype, contiguous; every output value is one of the input's.  The contract item by
+    item: kernels.KernelSpec.resample_labels.  Labels keep their values, so ``max_label`` and ``kept_labels`` stay valid; a nucleus
+    thinner than the new pixel can vanish.
+
+    Host syncs: none."""
+    _check_image('resize_labels', 'labels', labels)
+    kernels.HipKernels._check_resample('resize_labels', labels.shape, size, mode, kernels.RESAMPLE_LABEL_MODES)
+    with torch.cuda.device(labels.device):
+        return kernels.get().resample_labels(labels, size, mode)
+
+
+def _exact_factor(fn, f):
+    if isinstance(f, bool) or not isinstance(f, (int, Fraction, float)):
+        raise TypeError('%s: factor must be an int, a Fraction, a float or a pair (fy, fx) of those, got %r' % (fn, f))
+    if isinstance(f, float) and not math.isfinite(f):
+        raise ValueError('%s: factor must be finite, got %r' % (fn, f))
+    f = Fraction(f)                      # a float is taken as the exact binary fraction it holds
+    if f <= 0:
+        raise ValueError('%s: factor must be positive, got %r' % (fn, f))
+    return f
+
+
+def _scaled_size(shape, factor, fn='rescale'):
+    """The size rescale / rescale_labels give an image of ``shape``: per axis max(1, floor(n * f + 1/2)), in exact fractions."""
+    fy, fx = factor if isinstance(factor, (tuple, list)) and len(factor) == 2 else (factor, factor)
+    return tuple(max(1, math.floor(int(n) * _exact_factor(fn, f) + Fraction(1, 2))) for n, f in zip(shape[:2], (fy, fx)))
+
+
+def rescale(image, factor, mode='linear'):
+    """resize(image, size, mode) with size = max(1, floor(n * factor + 1/2)) per axis, computed in exact fractions.  ``factor``: an int,
+    a Fraction, a pair (fy, fx) of those, or a float taken as its exact Fraction.
+    ``normalize_stains(rescale(tile, Fraction(1, 2), 'area'))`` is a 40x tile at 20x.
+
+    Host syncs: none."""
+    _check_u8_image('rescale', image)
+    return resize(image, _scaled_size(image.shape, factor, 'rescale'), mode)
+
+
+def rescale_labels(labels, factor, mode='nearest'):
+    """resize_labels(labels, size, mode) with rescale's size rule.
+
+    Host syncs: none."""
+    _check_image('rescale_labels', 'labels', labels)
+    return resize_labels(labels, _scaled_size(labels.shape, factor, 'rescale_labels'), mode)
+
+
+def scale_points(points, from_size, to_size):
+    """Float [N, 2] (row, column) coordinates, such as centroids, from a raster of ``from_size`` = (H, W) to the same image at
+    ``to_size`` = (H2, W2), under the pixel-centre convention of resize: c2 = (c + 1/2) * n2 / n - 1/2 per axis, computed in float64
+    and returned in the input's dtype.  Plain torch, on whatever device the points live; scale_points(., b, a) inverts
+    scale_points(., a, b).
+
+    Host syncs: none."""
+    if not torch.is_tensor(points) or not points.is_floating_point():
+        raise TypeError('scale_points takes a float tensor [N, 2] (points)')
+    if points.dim() != 2 or points.shape[1] != 2:
+        raise ValueError('scale_points: points must be [N, 2] (got %s)' % (tuple(points.shape),))
+    sizes = []
+    for name, size in (('from_size', from_size), ('to_size', to_size)):
+        try:
+            h, w = (operator.index(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError('scale_points: %s must be a pair of integers, got %r' % (name, size))
+        if h < 1 or w < 1:
+            raise ValueError('scale_points: %s must be positive, got %r' % (name, size))
+        sizes.append((h, w))
+    n, n2 = (torch.tensor(v, dtype=torch.float64, device=points.device) for v in sizes)
+    return ((points.to(torch.float64) + 0.5) * n2 / n - 0.5).to(points.dtype)
 
 
 def stain_foreground(image, stain=0, radius=2, stains=None, order='bgr', within=None):

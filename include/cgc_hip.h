@@ -87,8 +87,10 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *  25: region geometry (per label value: count, coordinate sums, extents in eight directions, bit-quad counts, pixels on the image
  *      frame): cgc_region_geometry_max_side, cgc_region_geometry
  *  26: region hull (per label value: the exact convex hull of its pixel squares -- vertices, area, diameter with end points, minimum
- *      width, perimeter): cgc_region_hull_tall_rows, cgc_region_hull_ws_bytes, cgc_region_hull_spans, cgc_region_hull */
-#define CGC_ABI_VERSION 26
+ *      width, perimeter): cgc_region_hull_tall_rows, cgc_region_hull_ws_bytes, cgc_region_hull_spans, cgc_region_hull
+ *  27: resampling (the pixel size of a uint8 plane or tile -- linear, area -- and of a label image -- nearest, majority):
+ *      cgc_resample_max_side, cgc_resample_labels_max_factor, cgc_resample_u8, cgc_resample_labels */
+#define CGC_ABI_VERSION 27
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -582,6 +584,32 @@ int cgc_region_hull_spans(const int* labels, const void* within_or_null, int wit
 int cgc_region_hull(int max_label, int H, const int* extents, const int64_t* ptr, int64_t span_rows, const int* spans, void* ws,
                     int tall_rows, int* count, int64_t* area2, int64_t* diameter2, int* diameter_ends, int64_t* width_cross, int* width_edge,
                     double* perimeter, cgc_stream_t stream);
+
+/* ---- F21 (in front of F10, and between any two steps of the stage): the pixel size of an image (csrc/resample.hip).  The contract
+ * item by item: cgc-net_amd/kernels.py KernelSpec.resample_u8 / resample_labels.  src [H, W] (or [H, W, channels] interleaved) and dst
+ * [H2, W2] likewise, both contiguous; every side in 1 .. cgc_resample_max_side() = 32767.  Pixel centres sit at half-integers: output
+ * index d of an axis of n source and m output pixels samples the source at ((2 d + 1) n - m) / (2 m), clamped to [0, n - 1], and owns
+ * the source interval [d n / m, (d + 1) n / m).  One launch per call, no workspace, integers only, no atomics: bit-identical from
+ * call to call.
+ *   cgc_resample_u8: channels 1 or 3, each channel on its own.  mode CGC_RESAMPLE_LINEAR: exact rational bilinear interpolation of
+ *     the four neighbours, one rounding (half up).  CGC_RESAMPLE_AREA: H2 <= H and W2 <= W; the mean over the owned interval of both
+ *     axes, pixels weighted by their overlap, one rounding (half up).
+ *   cgc_resample_labels: elem_bytes 1, 2, 4 or 8.  mode CGC_RESAMPLE_NEAREST: dst[d] = src[floor((2 d + 1) n / (2 m))] per axis, the
+ *     element copied as it is.  CGC_RESAMPLE_MAJORITY: H2 <= H <= 8 H2 and W2 <= W <= 8 W2 (cgc_resample_labels_max_factor() = 8); the
+ *     value of the largest total overlap weight among the pixels that meet the owned box, ties to the smallest value, values compared
+ *     as signed integers of elem_bytes bytes.  CGC_RESAMPLE_MAJORITY_UNSIGNED: the same with unsigned comparison, elem_bytes 1 only
+ *     (uint8, bool).
+ * A side outside 1 .. 32767, another channels, elem_bytes or mode, a size the mode refuses or a null pointer: CGC_EINVAL, nothing
+ * launched. */
+#define CGC_RESAMPLE_LINEAR 0
+#define CGC_RESAMPLE_AREA 1
+#define CGC_RESAMPLE_NEAREST 0
+#define CGC_RESAMPLE_MAJORITY 1
+#define CGC_RESAMPLE_MAJORITY_UNSIGNED 2
+int cgc_resample_max_side(void);
+int cgc_resample_labels_max_factor(void);
+int cgc_resample_u8(const uint8_t* src, int H, int W, int channels, int H2, int W2, int mode, uint8_t* dst, cgc_stream_t stream);
+int cgc_resample_labels(const void* src, int elem_bytes, int H, int W, int H2, int W2, int mode, void* dst, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
