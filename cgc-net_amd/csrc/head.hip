@@ -99,7 +99,8 @@ __global__ __launch_bounds__(256) void k_head_bwd_simple(HeadArgs a, const float
     const float inv = 1.f / s;
     for (int l = 0; l < a.L; ++l) {
       float v = 0.f;
-      if (a.y != nullptr && head_label_ok(a, b)) v = g * (expf(logits[(size_t)b * a.L + l] - m) * inv - ((int)a.y[b] == l ? 1.f : 0.f));
+      if (a.y != nullptr && a.y[b] != -100)   // (a corrupt label takes g itself: NaN where a loss gradient is asked for, also at B = 1)
+        v = head_label_ok(a, b) ? g * (expf(logits[(size_t)b * a.L + l] - m) * inv - ((int)a.y[b] == l ? 1.f : 0.f)) : g;
       if (dlogits_ext != nullptr) v += dlogits_ext[(size_t)b * a.L + l];
       dl[(size_t)b * a.L + l] = v;
     }
@@ -223,7 +224,8 @@ __global__ __launch_bounds__(HEAD_THREADS) void k_head_bwd(HeadArgs a, const flo
     const float inv = 1.f / s;
     for (int l = 0; l < a.L; ++l) {
       float v = 0.f;
-      if (a.y != nullptr && head_label_ok(a, b)) v = g * (expf(logits[(size_t)b * a.L + l] - m) * inv - ((int)a.y[b] == l ? 1.f : 0.f));
+      if (a.y != nullptr && a.y[b] != -100)   // (a corrupt label takes g itself: NaN where a loss gradient is asked for, also at B = 1)
+        v = head_label_ok(a, b) ? g * (expf(logits[(size_t)b * a.L + l] - m) * inv - ((int)a.y[b] == l ? 1.f : 0.f)) : g;
       if (dlogits_ext != nullptr) v += dlogits_ext[(size_t)b * a.L + l];
       dls[b * a.L + l] = v;
     }
