@@ -195,3 +195,34 @@ def output_to_gexf(coordinate, adj, assign_matrix_list, path):
         os.makedirs(d, exist_ok=True)
     nx.write_gexf(G, path)
     return G
+
+
+def outlines_to_geojson(polygons, path, properties=None):
+    """Write nucleus outlines as a GeoJSON FeatureCollection, one Polygon feature per polygon: the annotation layer a slide viewer
+    (QuPath and the like) reads.  ``polygons``: what ``nuclei.outline_polygons`` returns -- per label a list of polygons, each a list
+    [outer ring, hole ring, ...] of [m, 2] arrays of (x, y).  The outer ring is the feature's exterior ring, the holes its interior
+    rings; every ring is closed here (its first point repeated at the end), as GeoJSON asks.  ``properties``: None, or one dict per
+    label -- the predicted class, say -- copied into every feature of that label; ``label_index`` (the position in ``polygons``) is
+    added where the dict does not set it.  Only the standard ``json`` module is used.  Returns the collection as written."""
+    import json
+    if properties is not None and len(properties) != len(polygons):
+        raise ValueError('outlines_to_geojson: properties must hold one dict per label (%d), got %d' % (len(polygons), len(properties)))
+    features = []
+    for k, label_polygons in enumerate(polygons):
+        props = dict(properties[k]) if properties is not None else {}
+        props.setdefault('label_index', k)
+        for rings in label_polygons:
+            coords = []
+            for ring in rings:
+                pts = [[float(x), float(y)] for x, y in np.asarray(ring, dtype=np.float64).reshape(-1, 2)]
+                if len(pts) < 3:
+                    raise ValueError('outlines_to_geojson: a ring needs at least 3 points, got %d' % len(pts))
+                coords.append(pts + [list(pts[0])])
+            features.append({'type': 'Feature', 'properties': dict(props), 'geometry': {'type': 'Polygon', 'coordinates': coords}})
+    collection = {'type': 'FeatureCollection', 'features': features}
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, 'w') as f:
+        json.dump(collection, f)
+    return collection

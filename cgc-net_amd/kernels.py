@@ -47,6 +47,8 @@ COOC_MAX_LEVELS = 16       # ... levels: levels^2 bins are the 256 16-bit bins o
 COOC_MAX_PIXELS = 2 ** 30  # ... a symmetric diagonal bin holds at most 2 H W and must fit int32
 GEOMETRY_MAX_SIDE = 32767  # region_geometry: largest H, W (cgc_region_geometry_max_side): sum x^2 over 2^31 pixels fits int64
 GEOMETRY_DIRECTIONS = ((1, 0), (2, 1), (1, 1), (1, 2), (0, 1), (-1, 2), (-1, 1), (-2, 1))      # (a, b) of the extents a x + b y
+OUTLINE_MAX_PIXELS = 2 ** 29      # region_outlines: a crack id 4 (y W + x) + side and the number of cracks fit int32
+OUTLINE_MODES = ('corners', 'cracks')
 REGION_VALUE_DTYPES = {torch.uint8: (1, 0), torch.int8: (1, 1), torch.int16: (2, 1), torch.int32: (4, 1)}      # (bytes, signed)
 RESAMPLE_MAX_SIDE = 32767  # resample_u8 / resample_labels: largest source and output side (cgc_resample_max_side): (2 d + 1) n < 2^31
 RESAMPLE_LABELS_MAX_FACTOR = 8      # resample_labels 'majority': largest n / m per axis (cgc_resample_labels_max_factor): a box spans <= 9 pixels
@@ -751,6 +753,52 @@ class KernelSpec(object):
         atomic.  Stage 2: lattice line j = y0 .. y1 + 1 has the left point (min(xmin[j-1], xmin[j]), j) and the right point
         (max(xmax[j-1], xmax[j]) + 1, j) over the non-empty rows beside it; Andrew's monotone chain with int64 cross products, in
         place in ``points``; then the scans of items 4 to 6."""
+        raise NotImplementedError
+
+    def region_outlines(self, labels, max_label, connectivity=1, within=None, mode='corners', background=False):
+        """The ordered boundary of every region of a label image as closed polygons of lattice corners (F22, behind region_geometry;
+        csrc/outline.hip).  Returns ((label_ptr int64 [R + 1], loop_ptr int64 [n_loops + 1], loop_label int32 [n_loops], loop_start
+        int32 [n_loops], loop_cracks int32 [n_loops], loop_area2 int64 [n_loops], vertices int32 [n, 2]), meta int32 [1], refused) with
+        R = max_label + 1, every tensor on the device; ``refused`` is meta[0] as the first host read brought it, and where it is not
+        0 the tables are None: nothing more is launched and the caller refuses.
+
+        1.  labels, max_label, within, "a pixel is *counted* in row L", the refused pixels and meta: items 1, 3 and 4 of
+            region_statistics; sides as item 1 of region_geometry (at most 32767).  Also H * W < 2^29, so that a crack id and the
+            number of cracks fit int32 (ValueError; the library returns CGC_EINVAL and launches nothing).  connectivity: 1 or 2; mode:
+            'corners' or 'cracks' (ValueError).  background=False: rows 1 .. max_label get outlines; background=True: row 0 is a
+            region like any other.
+        2.  CRACKS.  The pixel (y, x) is the square [x, x + 1] x [y, y + 1].  A side of a counted pixel of row v is a crack of v
+            when the pixel across it is not counted in row v; outside the image counts as "not".  Sides are numbered 0 top, 1
+            right, 2 bottom, 3 left; a crack is directed so that its own pixel lies on its right: top east, right south, bottom
+            west, left north.  Its id is 4 (y W + x) + side.  Vertices are lattice corners (y, x), 0 <= y <= H and 0 <= x <= W, row
+            first.  A border between two rows is cracked from both sides.
+        3.  SUCCESSOR, decided at the crack's head from the 2 x 2 block around that vertex alone.  A = the pixel ahead on the
+            region's side, B = the pixel ahead on the other side.  TIE RULE, connectivity 1: a right turn (the next side of the same
+            pixel) if A is not in v, else straight on (the same side of A) if B is not in v, else a left turn (the previous side of
+            B).  TIE RULE, connectivity 2: left if B is in v, else straight if A is in v, else right.  The two differ only where two
+            pixels of v touch by a corner: connectivity 1 keeps them apart, connectivity 2 passes through the vertex twice.
+        4.  The successor map is a permutation of the cracks; its cycles are the LOOPS.  ORDER: a loop starts at its crack of
+            smallest id; the loops of a label are ordered by start id; labels ascend.  The output is therefore unique.  Loops
+            label_ptr[L] .. label_ptr[L + 1] - 1 belong to row L, vertices loop_ptr[j] .. loop_ptr[j + 1] - 1 to loop j.
+        5.  mode='cracks': one vertex, the tail, per crack, in loop order from the start crack.  mode='corners': the same list
+            without every vertex whose incoming and outgoing crack have the same direction -- an even number, at least 4.  The first
+            vertex of a hole is then in general NOT the start crack's tail.
+        6.  loop_label = the row; loop_start = the id of the start crack; loop_cracks = the number of cracks, whatever the mode;
+            loop_area2 = the shoelace sum of x1 y2 - x2 y1 over the loop's cracks (tail 1, head 2): twice the enclosed area, positive
+            for an outer boundary and negative for a hole.  Over the loops of a row it sums to twice the row's count.
+        7.  An empty image, an image without foreground and labels that do not occur give empty rows: label_ptr[L] = label_ptr[L +
+            1].  H * W = 0 makes no host read at all.
+        8.  HOST READS: two.  The first brings the number of cracks and the refused pixels; it sizes the compact crack list and
+            fixes the doubling rounds.  The second brings the number of loops and, for mode='corners', the number of vertices; it
+            sizes the tables.  No cracks: the second is not made.
+        9.  Integer work only: bit-identical from call to call.  The one place where an order of arrival exists, the int64 additions
+            to loop_area2, does not depend on it.
+        Inside the kernels ("Region outlines"): no loop is walked.  A thread per pixel counts its cracks (a prefix sum
+        gives the compact list in id order) and writes each crack's successor as a compact index; pointer doubling over all cracks,
+        in ceil(log2(n_cracks)) rounds per phase (``region_outline_rounds``), finds first the smallest index of every cycle -- the
+        loop's start -- and then, with the cycle cut there, every crack's position and the loop's length; the loops' 64-bit keys
+        (label, start) are sorted; one scatter puts every tail at loop_ptr[loop] + position, for 'corners' through a prefix sum over
+        the kept vertices in that order.  The prefix sums and the sort are torch's; everything else is a library kernel."""
         raise NotImplementedError
 
     def region_quantiles(self, hist, q10k):
@@ -1998,6 +2046,96 @@ class HipKernels(KernelSpec):
                                            _ptr(wide[1]), _ptr(ends), _ptr(wide[2]), _ptr(width_edge), _ptr(perimeter), self._stream()),
                   'cgc_region_hull')
         return (count, wide[0], wide[1], ends, wide[2], width_edge, perimeter), points[:2 * (span_rows + R)]
+
+    @staticmethod
+    def _check_outline(H, W, connectivity, mode):
+        """The refusals of region_outlines that need shapes only."""
+        HipKernels._check_geometry_dims('region_outlines', H, W)
+        if H * W >= OUTLINE_MAX_PIXELS:
+            raise ValueError('region_outlines takes images of fewer than 2^29 pixels (got %d x %d): a crack id must fit int32' % (H, W))
+        if isinstance(connectivity, bool) or connectivity not in (1, 2):
+            raise ValueError('region_outlines: connectivity must be 1 or 2, got %r' % (connectivity,))
+        if mode not in OUTLINE_MODES:
+            raise ValueError("region_outlines: mode must be 'corners' or 'cracks', got %r" % (mode,))
+
+    def region_outline_rounds(self, n_cracks):
+        """The doubling rounds of each phase for ``n_cracks`` cracks: the smallest r with 2^r >= n_cracks."""
+        return int(self.lib.cgc_region_outline_rounds(ctypes.c_int64(n_cracks)))
+
+    def region_outlines(self, labels, max_label, connectivity=1, within=None, mode='corners', background=False):
+        HipKernels._check_max_label('region_outlines', max_label)
+        HipKernels._check_outline(labels.shape[0], labels.shape[1], connectivity, mode)
+        assert not labels.is_floating_point() and labels.dtype != torch.bool
+        if labels.dtype == torch.int64:                                         # as _region_inputs: what does not fit int32 stays refused
+            labels = labels.clamp(-1, max_label + 1)
+        labels, within = self._image(labels.to(torch.int32)), self._image(within)
+        assert within is None or within.shape == labels.shape
+        H, W = labels.shape
+        dev = labels.device
+        R = max_label + 1
+        i32, i64, u8 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev), dict(dtype=torch.uint8, device=dev)
+        L = ctypes.c_int64
+        lib, st = self.lib, self._stream()
+        image = (_ptr(labels),) + tuple(_within_args(within)) + (H, W, max_label)
+        meta = torch.empty(1, **i32)
+
+        def empty_tables():
+            return (torch.zeros(R + 1, **i64), torch.zeros(1, **i64), torch.empty(0, **i32), torch.empty(0, **i32), torch.empty(0, **i32),
+                    torch.empty(0, **i64), torch.empty(0, 2, **i32))
+
+        if H * W == 0:
+            self._chk(lib.cgc_region_outline_count(*image, 1 if background else 0, None, None, _ptr(meta), st), 'cgc_region_outline_count')
+            return empty_tables(), meta, 0
+        sides = torch.empty(2, H * W, **u8)                                       # mask, count
+        self._chk(lib.cgc_region_outline_count(*image, 1 if background else 0, _ptr(sides[0]), _ptr(sides[1]), _ptr(meta), st),
+                  'cgc_region_outline_count')
+        offsets = torch.cumsum(sides[1], 0, dtype=torch.int32)
+        n, refused = torch.stack([offsets[-1], meta[0]]).tolist()                 # host read 1: the cracks, the refused pixels
+        if refused:
+            return None, meta, refused
+        if n == 0:
+            return empty_tables(), meta, 0
+        lists = torch.empty(4, n, **i32)
+        crack, succ, start, steps = lists[0], lists[1], lists[2], lists[3]
+        self._chk(lib.cgc_region_outline_cracks(*image, connectivity, _ptr(sides[0]), _ptr(offsets), L(n), _ptr(crack), _ptr(succ), st),
+                  'cgc_region_outline_cracks')
+        ws = torch.empty(int(lib.cgc_region_outlines_ws_bytes(L(n))), **u8)
+        assert ws.numel() >= 16 * n
+        self._chk(lib.cgc_region_outline_loops(L(n), _ptr(succ), _ptr(ws), _ptr(start), _ptr(steps), st), 'cgc_region_outline_loops')
+        del ws
+        rank = torch.cumsum(start == torch.arange(n, **i32), 0, dtype=torch.int32)
+        counts = [rank[-1]]
+        if mode == 'corners':                                                     # a vertex is kept where the direction changes
+            counts.append((((crack ^ crack[succ.to(torch.int64)]) & 3) != 0).sum().to(torch.int32))
+        counts = torch.stack(counts).tolist()                                     # host read 2: the loops, the vertices
+        n_loops, n_vertices = counts[0], counts[-1] if mode == 'corners' else n
+        keys = torch.empty(n_loops, **i64)
+        self._chk(lib.cgc_region_outline_keys(L(n), L(n_loops), _ptr(labels), _ptr(crack), _ptr(start), _ptr(rank), _ptr(keys), st),
+                  'cgc_region_outline_keys')
+        keys = torch.sort(keys).values
+        loops = torch.empty(3, n_loops, **i32)
+        loop_label, loop_start, loop_cracks = loops[0], loops[1], loops[2]
+        area2 = torch.empty(n_loops, **i64)
+        loop_of = rank                                                            # no longer read: the loop's number at its start crack
+        self._chk(lib.cgc_region_outline_tables(L(n), L(n_loops), _ptr(keys), _ptr(crack), _ptr(steps), _ptr(loop_label), _ptr(loop_start),
+                                                _ptr(loop_cracks), _ptr(area2), _ptr(loop_of), st), 'cgc_region_outline_tables')
+        crack_ptr = torch.zeros(n_loops + 1, **i64)
+        torch.cumsum(loop_cracks, 0, out=crack_ptr[1:])
+        slots = torch.empty(n, 2, **i32)
+        keep = torch.empty(n, **u8) if mode == 'corners' else None
+        self._chk(lib.cgc_region_outline_scatter(L(n), L(n_loops), W, _ptr(crack), _ptr(succ), _ptr(start), _ptr(steps), _ptr(loop_of),
+                                                 _ptr(crack_ptr), _ptr(area2), _ptr(slots), _ptr(keep), st), 'cgc_region_outline_scatter')
+        if mode == 'cracks':
+            loop_ptr, vertices = crack_ptr, slots
+        else:
+            place = torch.zeros(n + 1, **i32)
+            torch.cumsum(keep, 0, dtype=torch.int32, out=place[1:])
+            vertices = torch.empty(n_vertices, 2, **i32)
+            self._chk(lib.cgc_region_outline_compact(L(n), L(n_vertices), _ptr(keep), _ptr(place[1:]), _ptr(slots), _ptr(vertices), st),
+                      'cgc_region_outline_compact')
+            loop_ptr = place[crack_ptr].to(torch.int64)
+        label_ptr = torch.searchsorted(loop_label.to(torch.int64), torch.arange(R + 1, **i64))
+        return (label_ptr, loop_ptr, loop_label, loop_start, loop_cracks, area2, vertices), meta, 0
 
     def region_quantiles(self, hist, q10k):
         q = HipKernels._check_q10k(q10k)

@@ -113,6 +113,12 @@ perimeter, integers but for the last.  ``hull_shape`` reads true solidity and th
 is seven columns of them per nucleus -- what a nucleus cut at a neck by ``split_touching`` or ``watershed`` needs:
     x = torch.cat([..., shape_features(L, kept, max_label=n), hull_features(L, kept, max_label=n)], 1)
 
+``region_outlines`` gives the outline itself back: the ordered boundary of every label as closed polygons of lattice corners, outer
+boundaries and holes (csrc/outline.hip; kernels.KernelSpec.region_outlines), in the convention of ``region_hull`` and
+``perimeter_crack``.  ``outline_tables`` counts them per label, ``outline_polygons`` brings them to the host as rings with their holes,
+at another resolution if asked, and ``evalio.outlines_to_geojson`` writes them as an annotation layer for a slide viewer:
+    polygons = outline_polygons(region_outlines(L, max_label=n), kept, scale=(L.shape, slide_shape))
+
 ``resize``, ``rescale``, ``resize_labels``, ``rescale_labels`` and ``scale_points`` change the pixel size of a tile, a plane, a label
 image and the coordinates that go with them (csrc/resample.hip; kernels.KernelSpec.resample_u8, resample_labels).  Every length of
 the stage is a number of pixels -- radii, ``ring``, ``max_distance``, the area, axis and perimeter columns -- so tiles scanned at
@@ -2340,6 +2346,163 @@ def hull_features(labels, kept_labels, max_label=None, within=None):
     s = hull_shape(RegionHull(*tables), geometry)
     table = torch.stack([getattr(s, name) for name in HULL_FEATURE_NAMES], dim=1)
     return table[kept_labels.to(torch.int64)]
+
+
+OUTLINE_MODES = kernels.OUTLINE_MODES
+OUTLINE_MAX_PIXELS = kernels.OUTLINE_MAX_PIXELS
+RegionOutlines = collections.namedtuple('RegionOutlines', ('label_ptr', 'loop_ptr', 'loop_label', 'loop_start', 'loop_cracks', 'loop_area2',
+                                                           'vertices', 'meta'))
+OutlineTables = collections.namedtuple('OutlineTables', ('outer', 'holes', 'cracks', 'area2'))
+
+
+def region_outlines(labels, max_label=None, connectivity=1, within=None, mode='corners', background=False):
+    """The outline of every region of a label image: its ordered boundary as closed polygons of lattice corners, outer boundaries
+    and holes (csrc/outline.hip; the contract item by item: kernels.KernelSpec.region_outlines).  labels, max_label, within: as
+    region_geometry, sides of at most 32767 pixels, and H * W < 2^29 (ValueError).  connectivity 1 or 2, mode 'corners' or 'cracks'
+    (ValueError otherwise).  Labels 1 .. max_label get outlines; with ``background`` label 0 is a region like any other.
+
+    THE OUTLINE follows the cracks between pixels: the pixel at row y, column x is the square [x, x + 1] x [y, y + 1], and a side of a
+    pixel of label v is a crack of v when the pixel across it does not belong to v (the image's frame included) -- the convention of
+    ``region_hull`` and of ``region_shape``'s perimeter_crack.  A crack runs with its own pixel on its right (top east, right south,
+    bottom west, left north), so an outer boundary runs clockwise on the screen and a hole the other way; its id is 4 (y W + x) + side
+    with sides 0 top, 1 right, 2 bottom, 3 left.  Where two pixels of v touch by a corner only, connectivity 1 turns right and keeps them
+    apart, connectivity 2 turns left and passes through the corner twice.  Returns the named tuple ``RegionOutlines``, all on the device:
+
+      label_ptr    int64 [R + 1]         label L owns loops label_ptr[L] .. label_ptr[L + 1] - 1, R = max_label + 1
+      loop_ptr     int64 [n_loops + 1]   loop j owns vertices[loop_ptr[j] : loop_ptr[j + 1]]
+      loop_label   int32 [n_loops]       ascending; the loops of a label are ordered by loop_start
+      loop_start   int32 [n_loops]       the id of the loop's smallest crack, where it starts
+      loop_cracks  int32 [n_loops]       its number of cracks: its length in pixel sides
+      loop_area2   int64 [n_loops]       twice the area it encloses (shoelace): positive for an outer boundary, negative for a hole
+      vertices     int32 [n, 2]          corners (y, x), 0 <= y <= H, 0 <= x <= W.  'cracks': the tail of every crack; 'corners': only
+                                         where the direction changes -- the first vertex of a hole is then in general not the start
+                                         crack's tail
+      meta         int32 [1]             0: the refused pixels
+
+    Per label the areas sum to twice its pixel count, the cracks to perimeter_crack, and outer boundaries minus holes is euler4
+    (connectivity 1) or euler8 (connectivity 2).  A label without a pixel has no loops.  Exact integers, unique, bit-identical from
+    call to call.
+
+    Host syncs: the label range unless ``max_label`` is given, and two reads: the number of cracks with the refused pixels (ValueError),
+    then the number of loops and vertices.  An empty image makes neither."""
+    fn = 'region_outlines'
+    _check_image(fn, 'labels', labels, _INT_DTYPES)
+    _check_within(fn, within, labels)
+    kernels.HipKernels._check_outline(labels.shape[0], labels.shape[1], connectivity, mode)
+    hi = _label_top(fn, labels, max_label)
+    with torch.cuda.device(labels.device):
+        tables, meta, refused = kernels.get().region_outlines(labels, hi, connectivity, within, mode, bool(background))
+    _refuse_labels(fn, refused, hi)
+    return RegionOutlines(*tables, meta=meta)
+
+
+def _check_outlines(fn, outlines):
+    if not isinstance(outlines, RegionOutlines):
+        raise TypeError('%s takes a RegionOutlines (region_outlines)' % fn)
+
+
+def outline_tables(outlines):
+    """Per-label counts from a ``RegionOutlines``: the named tuple ``OutlineTables(outer, holes, cracks, area2)`` of int32 [R] tables
+    on its device -- the number of outer boundaries (loops of positive area), of holes (negative area), the cracks of all loops (=
+    region_shape's perimeter_crack) and the sum of loop_area2 (= twice the pixel count).  Integer additions only.
+
+    Host syncs: none."""
+    _check_outlines('outline_tables', outlines)
+    R = outlines.label_ptr.shape[0] - 1
+    index = outlines.loop_label.to(torch.int64)
+    out = torch.zeros(4, R, dtype=torch.int64, device=index.device)
+    area = outlines.loop_area2
+    out[0].index_add_(0, index, (area > 0).to(torch.int64))
+    out[1].index_add_(0, index, (area < 0).to(torch.int64))
+    out[2].index_add_(0, index, outlines.loop_cracks.to(torch.int64))
+    out[3].index_add_(0, index, area)
+    return OutlineTables(*out.to(torch.int32))
+
+
+def _ring_holds(ring, py, px):
+    """Whether the rectilinear ring of (y, x) corners encloses the point (py, px), whose coordinates are half-integers: the vertical
+    edges right of it that span its row, counted even-odd."""
+    y1, x1 = ring[:, 0], ring[:, 1]
+    y2 = np.roll(y1, -1)
+    spans = (np.minimum(y1, y2) < py) & (py < np.maximum(y1, y2)) & (x1 == np.roll(x1, -1)) & (x1 > px)
+    return int(spans.sum()) % 2 == 1
+
+
+def outline_polygons(outlines, kept_labels=None, scale=None):
+    """The outlines as polygons on the host.  Returns a list with one entry per label of ``kept_labels`` (an int32 / int64 tensor or a
+    sequence of integers; None: every label 0 .. R - 1): the list of that label's polygons, each a list [outer ring, hole ring, ...] of
+    float64 numpy arrays [m, 2] of (x, y) -- x first, as GeoJSON and slide viewers take them; rings are not closed (the first point is
+    not repeated).  A label without a pixel gives an empty list.
+
+    scale = (from_size, to_size), pairs (H, W): corners are mapped as ``scale_points`` maps pixel-centre coordinates between the two
+    rasters -- a corner c sits half a pixel before centre c, so it goes to c * to / from per axis, the image's frame to the frame.
+
+    HOLES.  A hole (a loop of negative area) goes to the outer ring of the same label that encloses it, the innermost (smallest area)
+    if several do (an island inside a hole).  For connectivity 1 a hole never touches an outer ring, and "encloses its first vertex"
+    is well defined.  For connectivity 2 a hole can touch its outer ring at a corner, where a vertex test has no answer, so for BOTH the
+    point tested is the centre of the pixel across the hole's first crack -- a pixel of the hole itself, strictly inside it and on no
+    lattice line; for connectivity 1 this is the same ring the first vertex gives.
+
+    Host syncs: one transfer of the tables (with kept_labels, if they are a tensor)."""
+    fn = 'outline_polygons'
+    _check_outlines(fn, outlines)
+    R = outlines.label_ptr.shape[0] - 1
+    n_loops = outlines.loop_label.shape[0]
+    sx = sy = 1.0
+    if scale is not None:
+        try:
+            (h, w), (h2, w2) = ((operator.index(v) for v in size) for size in scale)
+        except (TypeError, ValueError):
+            raise ValueError('%s: scale must be (from_size, to_size), pairs of integers, got %r' % (fn, scale))
+        if min(h, w, h2, w2) < 1:
+            raise ValueError('%s: the sizes of scale must be positive, got %r' % (fn, scale))
+        sy, sx = h2 / float(h), w2 / float(w)
+    parts = [outlines.label_ptr, outlines.loop_ptr, outlines.loop_area2, outlines.vertices.reshape(-1)]
+    if torch.is_tensor(kept_labels):
+        if kept_labels.dtype not in (torch.int32, torch.int64) or kept_labels.dim() != 1:
+            raise TypeError('%s: kept_labels must be a 1-D int32 or int64 tensor, or a sequence of integers' % fn)
+        parts.append(kept_labels.to(outlines.label_ptr.device))
+    flat = torch.cat([p.to(torch.int64) for p in parts]).cpu().numpy()      # host sync: the one transfer
+    sizes = np.cumsum([p.numel() for p in parts])
+    label_ptr, loop_ptr, area2, vertices = np.split(flat, sizes)[:4]
+    vertices = vertices.reshape(-1, 2)
+    if torch.is_tensor(kept_labels):
+        kept = [int(v) for v in flat[sizes[3]:]]
+    elif kept_labels is None:
+        kept = list(range(R))
+    else:
+        try:
+            kept = [operator.index(v) for v in kept_labels]
+        except TypeError:
+            raise TypeError('%s: kept_labels must be a 1-D int32 or int64 tensor, or a sequence of integers' % fn)
+    bad = [v for v in kept if not 0 <= v < R]
+    if bad:
+        raise ValueError('%s: %d of kept_labels lie outside [0, %d]' % (fn, len(bad), R - 1))
+    assert len(loop_ptr) == n_loops + 1
+
+    def ring(j):
+        return vertices[loop_ptr[j]:loop_ptr[j + 1]]
+
+    def as_xy(r):
+        return np.stack([r[:, 1] * sx, r[:, 0] * sy], axis=1).astype(np.float64)
+
+    out = []
+    for v in kept:
+        loops = range(int(label_ptr[v]), int(label_ptr[v + 1]))
+        outer = sorted((j for j in loops if area2[j] > 0), key=lambda j: area2[j])      # the innermost first
+        polygons = {j: [as_xy(ring(j))] for j in outer}
+        for j in loops:
+            if area2[j] >= 0:
+                continue
+            r = ring(j)
+            dy, dx = np.sign(r[1] - r[0])                                 # the first crack; the hole lies on its left, at (-dx, dy)
+            py, px = r[0][0] + 0.5 * dy - 0.5 * dx, r[0][1] + 0.5 * dx + 0.5 * dy
+            home = next((k for k in outer if _ring_holds(ring(k), py, px)), None)
+            if home is None:
+                raise ValueError('%s: loop %d of label %d is a hole that no outer loop of the label encloses' % (fn, j, v))
+            polygons[home].append(as_xy(r))
+        out.append([polygons[j] for j in sorted(outer)])
+    return out
 
 
 def clear_border(labels, max_label=None):

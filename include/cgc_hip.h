@@ -89,8 +89,12 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *  26: region hull (per label value: the exact convex hull of its pixel squares -- vertices, area, diameter with end points, minimum
  *      width, perimeter): cgc_region_hull_tall_rows, cgc_region_hull_ws_bytes, cgc_region_hull_spans, cgc_region_hull
  *  27: resampling (the pixel size of a uint8 plane or tile -- linear, area -- and of a label image -- nearest, majority):
- *      cgc_resample_max_side, cgc_resample_labels_max_factor, cgc_resample_u8, cgc_resample_labels */
-#define CGC_ABI_VERSION 27
+ *      cgc_resample_max_side, cgc_resample_labels_max_factor, cgc_resample_u8, cgc_resample_labels
+ *  28: region outlines (per label value: the ordered boundary of its pixel squares as closed loops of lattice corners, by pointer
+ *      doubling over the cracks): cgc_region_outline_rounds, cgc_region_outlines_ws_bytes, cgc_region_outline_count,
+ *      cgc_region_outline_cracks, cgc_region_outline_loops, cgc_region_outline_keys, cgc_region_outline_tables,
+ *      cgc_region_outline_scatter, cgc_region_outline_compact */
+#define CGC_ABI_VERSION 28
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -610,6 +614,53 @@ int cgc_resample_max_side(void);
 int cgc_resample_labels_max_factor(void);
 int cgc_resample_u8(const uint8_t* src, int H, int W, int channels, int H2, int W2, int mode, uint8_t* dst, cgc_stream_t stream);
 int cgc_resample_labels(const void* src, int elem_bytes, int H, int W, int H2, int W2, int mode, void* dst, cgc_stream_t stream);
+
+/* ---- F22 (behind F19, csrc/outline.hip): the ordered boundary of every region of a label image, as closed loops of lattice corners.
+ * The per-label form of the reference's contours (cv2.findContours of one nucleus, dataflow/construct_feature_graph.py).  The contract
+ * item by item: cgc-net_amd/kernels.py KernelSpec.region_outlines.  labels, max_label, within_or_null and "a pixel is counted in row L"
+ * as F17, sides as F19, and H * W < 2^29 so that a crack id 4 (y W + x) + side fits int32.  A crack of row v is a side (0 top, 1 right,
+ * 2 bottom, 3 left) of a counted pixel of v across which no pixel counted in v lies; it runs with its pixel on its right.  The
+ * successor of a crack is decided from the 2 x 2 block at its head (connectivity 1: right, straight, left; 2: left, straight,
+ * right); the successors are a permutation whose cycles are the loops.  A call is these steps on one stream; between them the caller
+ * makes prefix sums, one sort of the loop keys, and two host reads (n_cracks; then n_loops and, for corners, n_vertices):
+ *   cgc_region_outline_count: mask uint8 [H, W] = the crack sides of each pixel as bits, count uint8 [H, W] = their number (rows 1 ..
+ *     max_label, or 0 .. max_label with background != 0); *meta = the refused pixels.  offsets int32 [H, W] = the caller's INCLUSIVE
+ *     prefix sum of count; n_cracks = its last entry.
+ *   cgc_region_outline_cracks: crack int32 [n_cracks] = the ids in ascending order, succ int32 [n_cracks] = the compact index of each
+ *     crack's successor.
+ *   cgc_region_outline_loops: ws = cgc_region_outlines_ws_bytes(n_cracks) bytes.  2 cgc_region_outline_rounds(n_cracks) + 3 launches,
+ *     rounds = ceil(log2(n_cracks)): start int32 [n_cracks] = the compact index of the smallest crack of each crack's loop, steps int32
+ *     [n_cracks] = the cracks that follow it before the loop returns to its start (position = steps[start] - steps, length =
+ *     steps[start] + 1).  rank int32 [n_cracks] = the caller's INCLUSIVE prefix sum of (start[k] == k); n_loops = its last entry.
+ *   cgc_region_outline_keys: keys int64 [n_loops] = label << 32 | compact index of each loop's start; the caller sorts them ascending.
+ *   cgc_region_outline_tables: from the sorted keys loop_label, loop_start (crack ids), loop_cracks int32 [n_loops]; loop_area2 int64
+ *     [n_loops] zeroed; loop_of int32 [n_cracks], the loop's number at its start crack (other entries are not written).  crack_ptr int64
+ *     [n_loops + 1] = the caller's prefix sum of loop_cracks, crack_ptr[0] = 0.
+ *   cgc_region_outline_scatter: slots int32 [n_cracks, 2] = the tail (y, x) of every crack at crack_ptr[loop] + position: the vertex
+ *     list of mode 'cracks'.  loop_area2 += x1 y2 - x2 y1 per crack (tail 1, head 2).  keep_or_null uint8 [n_cracks]: keep[t] = 1 iff
+ *     the cracks that meet at the vertex of slot t differ in direction.  place int32 [n_cracks] = the caller's INCLUSIVE prefix sum of
+ *     keep; n_vertices = its last entry.
+ *   cgc_region_outline_compact: vertices int32 [n_vertices, 2] = the kept slots in order: the vertex list of mode 'corners'.
+ * Integer work only, bit-identical from call to call.  Bad dims, max_label, within_bytes, connectivity, a side above 32767, H * W >=
+ * 2^29, a count outside its range or a null pointer where one is needed: CGC_EINVAL, nothing launched; tables that do not belong
+ * together write nothing outside the outputs.  H * W = 0, n_cracks = 0, n_loops = 0 or n_vertices = 0: nothing to do, 0. */
+int cgc_region_outline_rounds(int64_t n_cracks);
+int64_t cgc_region_outlines_ws_bytes(int64_t n_cracks);
+int cgc_region_outline_count(const int* labels, const void* within_or_null, int within_bytes, int H, int W, int max_label, int background,
+                             uint8_t* mask, uint8_t* count, int* meta, cgc_stream_t stream);
+int cgc_region_outline_cracks(const int* labels, const void* within_or_null, int within_bytes, int H, int W, int max_label,
+                              int connectivity, const uint8_t* mask, const int* offsets, int64_t n_cracks, int* crack, int* succ,
+                              cgc_stream_t stream);
+int cgc_region_outline_loops(int64_t n_cracks, const int* succ, void* ws, int* start, int* steps, cgc_stream_t stream);
+int cgc_region_outline_keys(int64_t n_cracks, int64_t n_loops, const int* labels, const int* crack, const int* start, const int* rank,
+                            int64_t* keys, cgc_stream_t stream);
+int cgc_region_outline_tables(int64_t n_cracks, int64_t n_loops, const int64_t* keys, const int* crack, const int* steps, int* loop_label,
+                              int* loop_start, int* loop_cracks, int64_t* loop_area2, int* loop_of, cgc_stream_t stream);
+int cgc_region_outline_scatter(int64_t n_cracks, int64_t n_loops, int W, const int* crack, const int* succ, const int* start,
+                               const int* steps, const int* loop_of, const int64_t* crack_ptr, int64_t* loop_area2, int* slots,
+                               uint8_t* keep_or_null, cgc_stream_t stream);
+int cgc_region_outline_compact(int64_t n_cracks, int64_t n_vertices, const uint8_t* keep, const int* place, const int* slots,
+                               int* vertices, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
