@@ -692,10 +692,12 @@ static int gemm_dispatch(GemmArgs& a, int transA, int transB, int batch, int max
     return launch_cfg<2, 2, 2, 2>(a, transA, transB, batch, m_extent, k_extent, shortk, w, ws_floats, stream);
   };
   // tuning hook (cgc_gemm_tuning): 1..6 forces a tile shape (128x128, 128x64, 64x128, 64x64, 128x32, 32x128), +10 forces the
-  // pipelined kernel, +20 the short-K kernel
+  // pipelined kernel, +20 the short-K kernel.  The short-K kernel has no loop over the extra K segments: a call that carries any
+  // (a.nx > 0) takes the pipelined kernel of the forced tile shape instead, as the automatic route does (`sk` above), so that a
+  // forced route never drops a segment
   const int force = g_force_cfg;
   if (force > 0) {
-    const bool fsk = force >= 20 ? true : force >= 10 ? false : sk;
+    const bool fsk = force >= 20 ? a.nx == 0 : force >= 10 ? false : sk;
     switch (force % 10) {
       case 1: return big_route(fsk, ws);
       case 2: return launch_cfg<4, 1, 1, 2>(a, transA, transB, batch, m_extent, k_extent, fsk, ws, ws_floats, stream);

@@ -778,7 +778,8 @@ int64_t cgc_gemm_half_ws_floats(void); /* the part of cgc_gemm_ws_floats() that 
 int64_t cgc_gemm_half_min_work(int64_t v);
 int64_t cgc_gemm_ws_floats(void);
 /* Tuning hook for experiments (tools/gemm_cfg_sweep.py): cfg 1..6 forces the tile shape 128x128, 128x64, 64x128, 64x64, 128x32,
- * 32x128 for every following product of this process, +10 the pipelined kernel, +20 the short-K kernel; 0 restores the automatic
+ * 32x128 for every following product of this process, +10 the pipelined kernel, +20 the short-K kernel (a call with extra K
+ * segments, which that kernel does not walk, takes the pipelined kernel of the forced tile shape instead); 0 restores the automatic
  * selection.  Returns the previous value.  Results do not depend on it (same arithmetic per output element up to tile-edge order). */
 int cgc_gemm_tuning(int cfg);
 

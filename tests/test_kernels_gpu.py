@@ -2,7 +2,8 @@
 (oracle/flat_ref.py) on the same seeded inputs.  Index work must be bit-exact; fp32 work within 1e-4 relative
 (sum-order differences only).  Shapes cover: ragged graphs, widths that are / are not multiples of 4 (16-byte lanes
 vs scalar lanes), rows narrower and wider than a wavefront, empty rows, duplicates, isolated nodes.
-The per-element check of the row kernels (csrc/rowops.hip) against float64 is tests/test_rowops_fp64_gpu.py."""
+The per-element check of the row kernels (csrc/rowops.hip) against float64 is tests/test_rowops_fp64_gpu.py; that of the exact
+fp32 GEMM (csrc/gemm.hip: every tile shape, kernel, layout and route) and of the reduce kernels is tests/test_gemm_fp64_gpu.py."""
 import numpy as np
 import pytest
 import torch
