@@ -286,10 +286,11 @@ __global__ __launch_bounds__(JK_THREADS) void k_jk_bwd(const float* __restrict__
     }
 }
 
-// npad is the row stride of HS / CS / DHC and a third of DGT's / INT's: at least n and a multiple of 64.  k_jk_bwd_mfma walks the
-// npad / 32 node tiles in pairs (an odd count would put the second tile of the last pair past the end of every DGT / INT row),
-// and rows of DGT / INT that start 16-byte aligned keep the parameter-gradient GEMM on its 16-byte operand loads.  Checked by all
-// four entry points before anything is launched, so that a pair of buffers is valid for every one of them or for none.
+// npad is the row stride of HS / CS / DHC and a third of DGT's / INT's: at least n and a multiple of 64.  No kernel needs more
+// than npad >= n (k_jk_bwd zeroes the columns n .. npad-1 of DGT / INT one thread per column); the multiple keeps the rows of
+// DGT / INT (3 npad floats) 16-byte aligned, i.e. the parameter-gradient GEMM on its 16-byte operand loads, and has been the
+// contract since ABI 21.  Checked by all four entry points before anything is launched, so that a pair of buffers is valid for
+// every one of them or for none.
 static bool jk_npad_ok(int n, int npad) { return npad >= n && npad % 64 == 0; }
 
 static void fill_weights(JkWeights& w, const float* const* lstm, const float* w_att, const float* b_att) {
@@ -303,13 +304,19 @@ static void fill_weights(JkWeights& w, const float* const* lstm, const float* w_
   w.b_att = b_att;
 }
 
-// Channel counts the fused kernels are compiled for: every even C up to 32 (hidden H = 3C/2 <= 48; model/network.py:27-33 needs C
-// even for the bidirectional split).  C in {4, 8, 12, 16, 20} (C % 4 == 0, H <= 32) run on the matrix-core kernels (jk_mfma.hip),
-// the others on the thread-per-direction kernels of this file.
+// Channel counts the fused kernels are compiled for (JK_FOR_EACH_C).  Those of JK_FOR_EACH_MFMA_C run their forward and their
+// backward with in-kernel parameter gradients on the matrix-core kernels (jk_mfma.hip); the others, unaligned buffers and every
+// staged backward run on the thread-per-direction kernels of this file.
 extern "C" int cgc_jk_supported(int C) { return C >= 2 && C <= 32 && C % 2 == 0; }
-extern "C" int cgc_jk_matrix_core(int C) { return C == 4 || C == 8 || C == 12 || C == 16 || C == 20; }
-
-#define JK_FOR_EACH_C(X) X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18) X(20) X(22) X(24) X(26) X(28) X(30) X(32)
+extern "C" int cgc_jk_matrix_core(int C) {
+  switch (C) {
+#define X(C_) case C_:
+    JK_FOR_EACH_MFMA_C(X)
+#undef X
+      return 1;
+    default: return 0;
+  }
+}
 
 template <int C>
 static void jk_allow_lds() {      // the LDS image of the weights exceeds the 64 KB default for C >= 24
@@ -358,8 +365,6 @@ extern "C" int cgc_jk_lstm_bwd(const float* xs, const float* dout, int n, int np
   if (!jk_npad_ok(n, npad)) return CGC_EINVAL;
   JkWeights w;
   fill_weights(w, lstm, w_att, b_att);
-  const int rc = jk_mfma_bwd(xs, dout, n, npad, C, w, HS, CS, dxs, DGT, INT, as_stream(stream));
-  if (rc != CGC_EINVAL) return rc;
   switch (C) {
 #define X(C_) case C_: return launch_jk_bwd<C_>(xs, dout, n, npad, w, HS, CS, dxs, DGT, INT, DHC, as_stream(stream));
     JK_FOR_EACH_C(X)

@@ -843,16 +843,19 @@ int cgc_segment_max_bwd_full(const float* dout, const int* arg, const int* gptr,
  * {w_ih[4H,C], w_hh[4H,H], b_ih[4H], b_hh[4H]} for the forward direction, then the same four for the reverse direction
  * (torch.nn.LSTM layout, gate order i,f,g,o).  HS, CS: [6H, npad] saved hidden / cell states.
  * npad (the same value in the forward and the backward of a call pair): npad >= n and npad % 64 == 0, else every entry point
- * below returns CGC_EINVAL before it launches anything.  64 = the pair of 32-node tiles the staged matrix-core backward walks
- * npad in, and rows of DGT / INT (3 * npad floats) then start 16-byte aligned (cgc_gemm_f32's 16-byte loads).  The forward
- * writes columns < n of HS / CS (the matrix-core forward also the rest of the last 32-node tile: finite values nobody reads);
- * no backward reads a column >= n, so the buffers need not be cleared.  n <= 0 returns 0 at once.
- * cgc_jk_supported(C): 1 if this C is compiled in (every even C <= 32); cgc_jk_matrix_core(C): 1 if it runs on the matrix-core
- * kernels (C in 4, 8, 12, 16, 20: those also have cgc_jk_lstm_bwd_params), else on the thread-per-direction kernels.
- * Backward writes dxs [n, 3C] and, for the parameter gradients, the transposed buffers DGT [2][4H+1][3*npad] and
- * INT [2][C+2H+1][3*npad] (every column written; in the padded ones DGT is zero and INT finite) whose per-direction product
- * DGT_d * INT_d^T (cgc_gemm_f32, NT) holds
- * [dW_ih | dW_hh | db | .] in rows 0..4H-1 and [. | . | d b_att | d w_att[dH:(d+1)H]] in row 4H.  DHC: [2][2][H][npad] scratch. */
+ * below returns CGC_EINVAL before it launches anything.  One rule for all four, so that a pair of HS / CS buffers is valid for
+ * every entry point or for none; rows of DGT / INT (3 * npad floats) then start 16-byte aligned (cgc_gemm_f32's 16-byte loads).
+ * The forward writes columns < n of HS / CS (the matrix-core forward also the rest of the last 32-node tile: finite values
+ * nobody reads); no backward reads a column >= n, so the buffers need not be cleared.  n <= 0 returns 0 at once.
+ * cgc_jk_supported(C): 1 if this C is compiled in (every even C <= 32); cgc_jk_matrix_core(C): 1 if cgc_jk_lstm_fwd,
+ * cgc_jk_lstm_bwd_params and cgc_jk_lstm_bwd_flat run it on the matrix-core kernels (C in 4, 8, 12, 16, 20, buffers 16-byte
+ * aligned); cgc_jk_lstm_fwd otherwise runs the thread-per-direction kernel, which takes any alignment.
+ * cgc_jk_lstm_bwd (the staged backward) always runs the thread-per-direction kernel, for every supported C and any alignment.
+ * It writes dxs [n, 3C] and, for the parameter gradients, the transposed buffers DGT [2][4H+1][3*npad] and
+ * INT [2][C+2H+1][3*npad] (every column written; the padded columns n .. npad-1 of each time slot are zero in both) whose
+ * per-direction product DGT_d * INT_d^T (cgc_gemm_f32, NT) holds
+ * [dW_ih | dW_hh | db | .] in rows 0..4H-1 and [. | . | d b_att | d w_att[dH:(d+1)H]] in row 4H.  DHC: [2][2][H][npad] scratch
+ * (written and read back, for every C). */
 int cgc_jk_supported(int C);
 int cgc_jk_matrix_core(int C);
 int cgc_jk_lstm_fwd(const float* xs, int n, int npad, int C, const float* const* lstm, const float* w_att,

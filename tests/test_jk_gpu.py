@@ -82,8 +82,8 @@ class Io(object):
         hip().jk_bwd(self.xs.v, self.dout.v, n, npad, C, self.lstm, self.w_att, self.b_att, self.HS, self.CS, self.dxs.v, DGT, INT, DHC)
         assert self.dxs.intact() and bool(torch.isfinite(self.dxs.v).all())
         assert bool(torch.isfinite(DGT).all()) and bool(torch.isfinite(INT).all())       # every column is written ...
-        pad = DGT.view(2, 4 * H + 1, 3, npad)[..., n:]
-        assert not bool(pad.any())                                                       # ... padding drops out of the product
+        for T in (DGT.view(2, 4 * H + 1, 3, npad), INT.view(2, C + 2 * H + 1, 3, npad)):
+            assert not bool(T[..., n:].any())                                            # ... padding drops out of the product
         G = torch.stack([DGT[d].double().cpu() @ INT[d].double().cpu().t() for d in range(2)])
         return self.dxs.v.cpu().clone(), R.unpack_G(G, C)
 
@@ -148,7 +148,8 @@ def full_check(C, n, npad, kind='plain', unaligned=False, staged=True):
 @pytest.mark.parametrize('C', R.ALL_C)
 def test_every_channel_count(C):
     """n = 77 = two full 32-node tiles and a tail of 13.  C = 2, 10, 14, 18, 22, 26, 28, 30 ran in no test before this one
-    (26-30: over 64 KB of LDS); 4, 8, 12, 16, 20 run on the matrix cores."""
+    (26-30: over 64 KB of LDS); 4, 8, 12, 16, 20 run on the matrix cores, but for jk_bwd, which is k_jk_bwd<C> for every C
+    (there on HS / CS of the matrix-core forward)."""
     K = hip()
     assert K.jk_supported(C) and bool(K.lib.cgc_jk_matrix_core(C)) == (C in R.MATRIX_CORE_C)
     H = 3 * C // 2
@@ -188,6 +189,25 @@ def test_unaligned_fallback(C):
     assert io.raw('cgc_jk_lstm_bwd_params', G, ws) == -1
     torch.cuda.synchronize()
     assert bool(torch.isnan(G).all()) and bool(torch.isnan(ws).all()) and bits_equal(io.dxs.buf, before)     # nothing launched
+
+
+@pytest.mark.parametrize('C', [4, 20, 6])
+def test_staged_backward_ignores_alignment(C):
+    """jk_bwd on the same HS / CS / weights, once with aligned xs / dout / dxs and once with copies one float past a 16-byte
+    boundary: one kernel (k_jk_bwd<C>) for both, so dxs, DGT and INT agree bit for bit, padded columns included."""
+    n, npad, H = 77, 1024, 3 * C // 2
+    io = Io(R.case(C, n), npad)
+    io.fwd()
+    got = []
+    for unaligned in (False, True):
+        xs, dout = Guarded(n, 3 * C, unaligned, io.xs.v), Guarded(n, C, unaligned, io.dout.v)
+        dxs = Guarded(n, 3 * C, unaligned)
+        DGT, INT, DHC = nans(2, 4 * H + 1, 3 * npad), nans(2, C + 2 * H + 1, 3 * npad), nans(2, 2, H, npad)
+        hip().jk_bwd(xs.v, dout.v, n, npad, C, io.lstm, io.w_att, io.b_att, io.HS, io.CS, dxs.v, DGT, INT, DHC)
+        assert dxs.intact() and xs.intact() and dout.intact()
+        got.append((dxs.v.contiguous(), DGT, INT))
+    for name, a, b in zip(('dxs', 'DGT', 'INT'), got[0], got[1]):
+        assert bits_equal(a, b), name
 
 
 # ---------------------------------------------------------------------------------------------- 4: cgc_jk_lstm_bwd_flat
