@@ -956,6 +956,9 @@ extern "C" int cgc_softmax_bwd(const float* S, const float* dS, int n, int C, in
 // max readout per graph (with the implicit zero padding rows of the dense layout)
 // ------------------------------------------------------------------------------------------------
 #define SEGMAX_WAVES 16
+// v replaces best: v is larger, or v is the first NaN (torch.max: a NaN is the maximum, the first one wins).  Once best is NaN
+// nothing replaces it; without a NaN this is v > best.
+__device__ __forceinline__ bool segmax_takes(float v, float best) { return !(v <= best) && best == best; }
 // one workgroup per (graph, 64-column group); with D <= 32 columns a wave carries 64 / D' rows at a time (D' = D rounded up to a
 // power of two) instead of idling 44 of its 64 lanes on the 20-column readouts of this network
 __global__ __launch_bounds__(64 * SEGMAX_WAVES) void k_segment_max_fwd(const float* __restrict__ x, const int* __restrict__ gptr,
@@ -981,11 +984,11 @@ __global__ __launch_bounds__(64 * SEGMAX_WAVES) void k_segment_max_fwd(const flo
       for (int u = 0; u < 4; ++u) v[u] = x[(size_t)(r + u * stride) * D + d];
 #pragma unroll
       for (int u = 0; u < 4; ++u)
-        if (v[u] > best) { best = v[u]; idx = r + u * stride; }
+        if (segmax_takes(v[u], best)) { best = v[u]; idx = r + u * stride; }
     }
-    for (; r < hi; r += stride) {                        // increasing rows + strict '>' keeps the FIRST maximum
+    for (; r < hi; r += stride) {                        // increasing rows + a strict comparison keeps the FIRST maximum
       const float v = x[(size_t)r * D + d];
-      if (v > best) { best = v; idx = r; }
+      if (segmax_takes(v, best)) { best = v; idx = r; }
     }
   }
   bv[wave][lane] = best;
@@ -996,8 +999,10 @@ __global__ __launch_bounds__(64 * SEGMAX_WAVES) void k_segment_max_fwd(const flo
       for (int s2 = (w == 0 ? 1 : 0); s2 < rpw; ++s2) {
         const float v = bv[w][s2 * dp + dl];
         const int i = bi[w][s2 * dp + dl];
-        if (i >= 0 && (v > best || (v == best && i < idx) || idx < 0)) { best = v; idx = i; }
+        const bool tie = v == best || (v != v && best != best);    // equal, or both NaN: the earlier row stays
+        if (i >= 0 && (idx < 0 || segmax_takes(v, best) || (tie && i < idx))) { best = v; idx = i; }
       }
+    if (idx < 0 && hi > lo) idx = lo;                              // no row was taken: every real row is -inf, the first one is the maximum
     if (idx < 0) { best = 0.f; }                                   // empty graph: only padding rows
     else if (hi - lo < nmax && best < 0.f) { best = 0.f; idx = -1; }  // a zero padding row wins (ties go to the real row)
     out[(size_t)b * D + d] = best;

@@ -831,6 +831,12 @@ int cgc_colsum(const float* x, int ld, int n, int F, float* out, float* ws, cgc_
 int cgc_softmax_fwd(const float* x, int n, int C, int ld /*row stride of x and out*/, float* out, cgc_stream_t stream);
 int cgc_softmax_bwd(const float* S, const float* dS, int n, int C, int ld /*row stride of S, dS, dx*/, float* dx,
                     float* dx_colsum /*[C] or NULL: fused column sums of dx*/, float* ws, cgc_stream_t stream);
+/* torch.max over dim 1 of the dense padded [B, nmax, D] layout, from the flat rows x [n, D] (row stride D) of graphs
+ * [gptr[b], gptr[b+1]).  out[b,d] = the maximum over the real rows of graph b, and over one zero as well when the graph has fewer
+ * than nmax rows; arg[b,d] = the first real row (index into x) that attains it.  arg = -1 when the padding zero wins strictly or the
+ * graph is empty (out = 0 then).  A real row that ties with the padding wins, so a real -0.0 comes out as -0.0.  If any real row of
+ * the column is NaN, out is NaN and arg the first NaN row, padded or not.  All real rows -inf: without padding out = -inf and
+ * arg = gptr[b]; with padding out = 0 and arg = -1.  +inf wins at its first occurrence. */
 int cgc_segment_max_fwd(const float* x, const int* gptr, int B, int D, int nmax, float* out, int* arg, cgc_stream_t stream);
 int cgc_segment_max_bwd(const float* dout, const int* arg, int B, int D, float* dx_zeroed, cgc_stream_t stream);
 /* The same gradient written in full: dx [n,D] need not be zeroed -- every element of every graph's rows is written (dout where
