@@ -49,6 +49,12 @@ GEOMETRY_MAX_SIDE = 32767  # region_geometry: largest H, W (cgc_region_geometry_
 GEOMETRY_DIRECTIONS = ((1, 0), (2, 1), (1, 1), (1, 2), (0, 1), (-1, 2), (-1, 1), (-2, 1))      # (a, b) of the extents a x + b y
 OUTLINE_MAX_PIXELS = 2 ** 29      # region_outlines: a crack id 4 (y W + x) + side and the number of cracks fit int32
 OUTLINE_MODES = ('corners', 'cracks')
+SLIC_MAX_PIXELS = 2 ** 29         # slic_iterate: as region_adjacency, which reads the result
+SLIC_MIN_STEP, SLIC_MAX_STEP = 4, 256      # ... the grid step S (cgc_slic_max_step)
+SLIC_MAX_COMPACTNESS = 1024       # ... m: m^2 times a squared distance stays far inside int64
+SLIC_MAX_ITER = 64                # ... rounds per call
+SLIC_MAX_PLANES = 4               # ... C
+SLIC_MERGE_FIRST_BATCH, SLIC_MERGE_MAX_BATCH = 4, 64      # slic_merge: rounds per host read, doubled after each
 REGION_VALUE_DTYPES = {torch.uint8: (1, 0), torch.int8: (1, 1), torch.int16: (2, 1), torch.int32: (4, 1)}      # (bytes, signed)
 RESAMPLE_MAX_SIDE = 32767  # resample_u8 / resample_labels: largest source and output side (cgc_resample_max_side): (2 d + 1) n < 2^31
 RESAMPLE_LABELS_MAX_FACTOR = 8      # resample_labels 'majority': largest n / m per axis (cgc_resample_labels_max_factor): a box spans <= 9 pixels
@@ -801,6 +807,57 @@ class KernelSpec(object):
         the kept vertices in that order.  The prefix sums and the sort are torch's; everything else is a library kernel."""
         raise NotImplementedError
 
+    def slic_iterate(self, planes, step, compactness, n_iter, within=None):
+        """SLIC superpixel clustering of one tile in integers (F23, behind stain_separate / od_recolor, in front of label_components
+        and region_adjacency; csrc/slic.hip).  Returns (labels int32 [H, W], centres int32 [K, 2 + C], count int32 [K]) on the device;
+        no host read.
+
+        1.  planes: uint8 [C, H, W], 1 <= C <= 4, any strides (copied if not contiguous), H * W < 2^29 (TypeError for another dtype,
+            ValueError otherwise; the library returns CGC_EINVAL and launches nothing).  step S: an integer in 4..256; compactness m:
+            an integer in 0..1024; n_iter: an integer in 1..64 (ValueError).  within: None or [H, W] of a 1-, 2-, 4- or 8-byte
+            integer type or bool; only "is zero" is read.
+        2.  GRID.  ny = max(1, (2 H + S) // (2 S)), nx likewise from W, K = ny * nx.  Pixel (y, x) has HOME cell (y * ny // H, x * nx //
+            W).  Centre k = i * nx + j starts at y = ((2 i + 1) H) // (2 ny), x = ((2 j + 1) W) // (2 nx), with the colour of the pixel
+            there, whether or not within holds there.
+        3.  ASSIGNMENT.  A pixel where within is non-zero looks at the centres of the up to 9 cells around its home cell (those
+            inside the grid) -- at those centres' identities, wherever they have moved -- and takes the one with the smallest D = S^2 *
+            sum_c (p_c - c_c)^2 + m^2 * ((y - c_y)^2 + (x - c_x)^2), computed in 64 bits; of equal D the smallest k.  A gather: no
+            atomics and no launch order decide anything.
+        4.  UPDATE.  Per centre: n, the number of its pixels, and the sums of y, x and every plane over them.  Every coordinate and
+            colour becomes (2 * sum + n) // (2 * n): the mean, rounded half up.  A centre with n == 0 keeps its values.
+        5.  A call is n_iter rounds of assignment, then update.  labels = k + 1 of the LAST assignment, 0 where within is zero;
+            centres = (y, x, colours) after the last update; count = n of the last assignment.
+        6.  H * W = 0 gives labels [H, W], centres [0, 2 + C] and count [0] without a launch.
+        7.  Integer additions only: bit-identical from call to call.  The regions of one label need not be connected; slic_merge and
+            nuclei.superpixels see to that.
+        Inside the kernels ("Superpixels"): 1 + 2 n_iter launches.  A round is one launch over tiles of ``slic_tile`` x
+        ``slic_tile`` (64) pixels that assigns and accumulates -- a thread sums the run of equal centres down its 16 pixels of a
+        column in registers and folds it into a table in LDS of the ``slic_table`` x ``slic_table`` (12) cells around the tile's
+        first pixel, which goes to global memory with one integer atomic per centre and quantity -- and one launch of a thread per
+        centre that divides and clears.  A tile meets at most 64 // (H // ny) + 4 cells per axis, neighbours included, so the
+        table holds them all from cells of 8 pixels up; sums of cells outside it (small steps) go to global memory directly, exactly."""
+        raise NotImplementedError
+
+    def slic_merge(self, sizes, pairs, count, min_size):
+        """The order-free merge of small pieces into settled neighbours (F23; csrc/slic.hip): what makes superpixels connected.
+        Returns (group int32 [P + 1], launched rounds); one host read per batch of rounds.
+
+        1.  sizes: int32 [P], the pixels of pieces 1 .. P (label_components with sizes); pairs int32 [Q, 2] and count int32 [Q]:
+            region_adjacency's outputs on the piece image, connectivity 1.  min_size: an integer >= 0.
+        2.  A piece is SMALL iff sizes < min_size; the others are SETTLED from the start, each its own group: group[p] = p.
+        3.  ROUND r: every unsettled piece that has a neighbour settled BEFORE round r joins the group of the settled neighbour q
+            with the largest count; of equal counts the smallest q (one 64-bit key, count << 32 | ~q, under an unsigned maximum).
+            Pieces that join are settled from round r + 1 on.  Rounds repeat until one settles nothing.
+        4.  group[p] = the piece whose group p ended in, 0 for a piece that never met a settled one (its whole component of the
+            mask is made of small pieces); group[0] = 0.
+        5.  The result does not depend on the order of the pairs, of arrival, or on how many rounds run past the last useful one;
+            they run in batches of SLIC_MERGE_FIRST_BATCH, twice that, ... with one host read after each (_relax_until_still)."""
+        raise NotImplementedError
+
+    def slic_relabel(self, pieces, table):
+        """out int32 [H, W] = table[pieces] for pieces in 1 .. len(table) - 1, 0 elsewhere (F23; one launch, no host read)."""
+        raise NotImplementedError
+
     def region_quantiles(self, hist, q10k):
         """Quantiles of the rows of a table of 256-bin histograms (F17; csrc/region.hip).  Returns uint8 [R, len(q10k)] on the device;
         no host read.
@@ -1184,6 +1241,9 @@ class HipKernels(KernelSpec):
         self.region_cooc_max_offsets = int(self.lib.cgc_region_cooc_max_offsets())    # offsets per call
         self.region_geometry_max_side = int(self.lib.cgc_region_geometry_max_side())  # largest H, W of region_geometry
         self.region_hull_tall_rows = int(self.lib.cgc_region_hull_tall_rows())        # rows above which a wave hulls a region
+        self.slic_tile = int(self.lib.cgc_slic_tile_side())                    # side of the tiles of slic_iterate (tests)
+        self.slic_table = int(self.lib.cgc_slic_table_side())                  # cells per axis such a tile folds in LDS (tests)
+        assert int(self.lib.cgc_slic_max_step()) == SLIC_MAX_STEP
         self.scan_chunk = int(self.lib.cgc_scan_chunk_pixels())               # ... and of od_moments / angle_histogram
         self._dirs_checked = (None, None)                                      # angle_histogram's last direction table and its C array
         self._exp_checked = (None, None)                                       # od_recolor's last exponential table and its C array
@@ -2138,6 +2198,76 @@ class HipKernels(KernelSpec):
             loop_ptr = place[crack_ptr].to(torch.int64)
         label_ptr = torch.searchsorted(loop_label.to(torch.int64), torch.arange(R + 1, **i64))
         return (label_ptr, loop_ptr, loop_label, loop_start, loop_cracks, area2, vertices), meta, 0
+
+    @staticmethod
+    def _check_slic(shape, step, compactness, n_iter):
+        """The refusals of slic_iterate that need shapes only."""
+        for name, v, lo, hi in (('step', step, SLIC_MIN_STEP, SLIC_MAX_STEP), ('compactness', compactness, 0, SLIC_MAX_COMPACTNESS),
+                                ('n_iter', n_iter, 1, SLIC_MAX_ITER)):
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError('slic_iterate: %s must be an integer in %d..%d, got %r' % (name, lo, hi, v))
+        if len(shape) != 3 or not 1 <= shape[0] <= SLIC_MAX_PLANES:
+            raise ValueError('slic_iterate: planes must be [C, H, W] with 1 <= C <= %d (got %s)' % (SLIC_MAX_PLANES, tuple(shape)))
+        if shape[1] * shape[2] >= SLIC_MAX_PIXELS:
+            raise ValueError('slic_iterate takes images of fewer than 2^29 pixels (got %d x %d)' % (shape[1], shape[2]))
+
+    @staticmethod
+    def slic_grid(H, W, step):
+        """(ny, nx) of slic_iterate's grid."""
+        return max(1, (2 * H + step) // (2 * step)), max(1, (2 * W + step) // (2 * step))
+
+    def slic_iterate(self, planes, step, compactness, n_iter, within=None):
+        HipKernels._check_slic(planes.shape, step, compactness, n_iter)
+        if planes.dtype != torch.uint8:
+            raise TypeError('slic_iterate: planes must be uint8, got %s' % planes.dtype)
+        if within is not None and (tuple(within.shape) != tuple(planes.shape[1:]) or within.device != planes.device):
+            raise ValueError('slic_iterate: within must have the shape and device of a plane (got %s on %s and %s on %s)'
+                             % (tuple(within.shape), within.device, tuple(planes.shape[1:]), planes.device))
+        self._dev(planes)
+        within = self._image(within)
+        planes = planes.contiguous()
+        C, H, W = planes.shape
+        i32 = dict(dtype=torch.int32, device=planes.device)
+        if H * W == 0:
+            return torch.empty(H, W, **i32), torch.empty(0, 2 + C, **i32), torch.empty(0, **i32)
+        ny, nx = HipKernels.slic_grid(H, W, step)
+        labels, centres, count = torch.empty(H, W, **i32), torch.empty(ny * nx, 2 + C, **i32), torch.empty(ny * nx, **i32)
+        ws = torch.empty(int(self.lib.cgc_slic_ws_bytes(C, H, W, step)), dtype=torch.uint8, device=planes.device)
+        assert ws.numel() >= 8 * ny * nx * (3 + C)
+        self._chk(self.lib.cgc_slic_iterate(_ptr(planes), C, H, W, step, compactness, n_iter, *_within_args(within), _ptr(ws), _ptr(labels),
+                                            _ptr(centres), _ptr(count), self._stream()), 'cgc_slic_iterate')
+        return labels, centres, count
+
+    def slic_merge(self, sizes, pairs, count, min_size):
+        if isinstance(min_size, bool) or not isinstance(min_size, int) or not 0 <= min_size < 2 ** 31:
+            raise ValueError('slic_merge: min_size must be an integer in 0..2^31 - 1, got %r' % (min_size,))
+        self._dev(sizes, pairs, count)
+        assert sizes.dtype == pairs.dtype == count.dtype == torch.int32 and sizes.dim() == 1
+        assert pairs.dim() == 2 and pairs.shape[1] == 2 and tuple(count.shape) == (pairs.shape[0],)
+        sizes, pairs, count = sizes.contiguous(), pairs.contiguous(), count.contiguous()
+        P, Q = sizes.shape[0], pairs.shape[0]
+        dev = sizes.device
+        group = torch.empty(P + 1, dtype=torch.int32, device=dev)
+        best = torch.empty(P + 1, dtype=torch.int64, device=dev)
+        self._chk(self.lib.cgc_slic_merge_begin(_ptr(sizes), P, min_size, _ptr(group), _ptr(best), self._stream()), 'cgc_slic_merge_begin')
+        if P == 0 or Q == 0:
+            return group, 0
+        changed = torch.empty(1, dtype=torch.int32, device=dev)
+
+        def launch(first, rounds):
+            self._chk(self.lib.cgc_slic_merge_rounds(_ptr(pairs), _ptr(count), ctypes.c_int64(Q), P, rounds, _ptr(group), _ptr(best),
+                                                     _ptr(changed), self._stream()), 'cgc_slic_merge_rounds')
+
+        return group, HipKernels._relax_until_still(launch, changed, SLIC_MERGE_FIRST_BATCH, SLIC_MERGE_MAX_BATCH)
+
+    def slic_relabel(self, pieces, table):
+        self._dev(pieces, table)
+        assert pieces.dtype == table.dtype == torch.int32 and pieces.dim() == 2 and table.dim() == 1 and table.numel() >= 1
+        pieces, table = pieces.contiguous(), table.contiguous()
+        out = torch.empty_like(pieces)
+        self._chk(self.lib.cgc_slic_relabel(_ptr(pieces), ctypes.c_int64(pieces.numel()), table.numel() - 1, _ptr(table), _ptr(out),
+                                            self._stream()), 'cgc_slic_relabel')
+        return out
 
     def region_quantiles(self, hist, q10k):
         q = HipKernels._check_q10k(q10k)

@@ -119,6 +119,16 @@ boundaries and holes (csrc/outline.hip; kernels.KernelSpec.region_outlines), in 
 at another resolution if asked, and ``evalio.outlines_to_geojson`` writes them as an annotation layer for a slide viewer:
     polygons = outline_polygons(region_outlines(L, max_label=n), kept, scale=(L.shape, slide_shape))
 
+``superpixels`` is the one step that is not about nuclei: it cuts the tile into compact, colour-homogeneous, 4-connected tissue
+regions -- stroma, epithelium, lumen -- by SLIC in exact integers (csrc/slic.hip; kernels.KernelSpec.slic_iterate, slic_merge), on
+``separate_stains``' planes or the tile's own channels.  ``superpixel_graph`` (region contacts as edges), ``superpixel_features`` (area,
+centroid, mean and spread of every plane) and ``regions_at`` (the region under every nucleus) make the tissue graph that hierarchical
+cell-graph models place beside the cell graph:
+    planes = separate_stains(tile)
+    T, nt = superpixels(planes, 32)
+    tissue = graph_item(*superpixel_features(T, planes, nt), y, edge_index=superpixel_graph(T, nt))
+    node_of_nucleus = regions_at(T, cen) - 1
+
 ``resize``, ``rescale``, ``resize_labels``, ``rescale_labels`` and ``scale_points`` change the pixel size of a tile, a plane, a label
 image and the coordinates that go with them (csrc/resample.hip; kernels.KernelSpec.resample_u8, resample_labels).  Every length of
 the stage is a number of pixels -- radii, ``ring``, ``max_distance``, the area, axis and perimeter columns -- so tiles scanned at
@@ -2515,6 +2525,197 @@ def clear_border(labels, max_label=None):
     out = torch.where(cut[labels.clamp(0, hi).to(torch.int64)], torch.zeros_like(labels), labels)
     _refuse_labels('clear_border', int(meta.item()), hi)           # host sync: the refused pixels
     return out
+
+
+SLIC_MIN_STEP, SLIC_MAX_STEP = kernels.SLIC_MIN_STEP, kernels.SLIC_MAX_STEP
+SLIC_MAX_PLANES = kernels.SLIC_MAX_PLANES
+SLIC_MAX_PIXELS = kernels.SLIC_MAX_PIXELS
+# superpixel_features' columns for 4 planes; C planes give the first 3 + 2 C
+SUPERPIXEL_FEATURE_NAMES = ('area', 'centroid_y', 'centroid_x') + tuple('plane%d_%s' % (c, what) for c in range(SLIC_MAX_PLANES)
+                                                                         for what in ('mean', 'std'))
+
+
+def _check_superpixel_args(planes, step, compactness, n_iter, min_size, within):
+    """The refusals of superpixels, all before any launch: returns min_size with its default filled in."""
+    fn = 'superpixels'
+    if not torch.is_tensor(planes):
+        raise TypeError('%s takes torch tensors on the GPU (planes)' % fn)
+    if planes.dtype != torch.uint8:
+        raise TypeError('%s: planes must be uint8, got %s' % (fn, planes.dtype))
+    if planes.dim() != 3:
+        raise ValueError('%s: planes must be [C, H, W] (got %s)' % (fn, tuple(planes.shape)))
+    kernels.HipKernels._check_slic(planes.shape, step, compactness, n_iter)
+    _check_image(fn, 'planes', planes[0], (torch.uint8,))            # on the GPU
+    if min_size is None:
+        min_size = max(1, step * step // 4)
+    if isinstance(min_size, bool) or not isinstance(min_size, numbers.Integral) or not 0 <= min_size < 2 ** 31:
+        raise ValueError('%s: min_size must be an integer in 0..2^31 - 1, got %r' % (fn, min_size))
+    if within is not None:
+        _check_image(fn, 'within', within)
+        if tuple(within.shape) != tuple(planes.shape[1:]) or within.device != planes.device:
+            raise ValueError('%s: within must have the shape and device of a plane (got %s on %s and %s on %s)'
+                             % (fn, tuple(within.shape), within.device, tuple(planes.shape[1:]), planes.device))
+    return int(min_size)
+
+
+def _superpixel_numbers(group, piece_blob):
+    """Rule (f) of superpixels on tables: group int32 [P + 1] (slic_merge's; 0 = never settled), piece_blob int64 [P + 1] (the
+    leftover blob, 1 .., of every piece that never settled; anything elsewhere) or None when every piece settled.  Returns (table
+    int32 [P + 1], the number of regions as a 0-d tensor): table[p] = the final number of piece p, table[0] = 0.  Pieces are numbered
+    by first pixel, so a region's first pixel belongs to its smallest piece, and regions are numbered in the order of those."""
+    P = group.shape[0] - 1
+    dev = group.device
+    ids = torch.arange(1, P + 1, dtype=torch.int64, device=dev)
+    region = group[1:].to(torch.int64)                               # settled: the group's piece, 1 .. P
+    if piece_blob is not None:
+        region = torch.where(region == 0, P + piece_blob[1:], region)       # leftovers: P + 1 ..
+    smallest = torch.full((2 * P + 2,), P + 1, dtype=torch.int64, device=dev)
+    smallest.scatter_reduce_(0, region, ids, 'amin')                 # the smallest piece of every region
+    lead = smallest[region]                                          # ... seen from each of its pieces
+    number = torch.cumsum(lead == ids, 0)                            # at a region's smallest piece: the region's number
+    table = torch.zeros(P + 1, dtype=torch.int32, device=dev)
+    table[1:] = number[lead - 1].to(torch.int32)
+    return table, number[-1] if P > 0 else torch.zeros((), dtype=torch.int64, device=dev)
+
+
+def superpixels(planes, step, compactness=10, n_iter=10, min_size=None, within=None, return_centres=False):
+    """The tile cut into compact, colour-homogeneous, 4-connected regions: SLIC superpixels (Achanta et al. 2012) in exact integers
+    (csrc/slic.hip; the contract item by item: kernels.KernelSpec.slic_iterate and slic_merge) -- the nodes of a tissue graph beside
+    the cell graph.  planes: uint8 [C, H, W] on the GPU, 1 <= C <= 4, any strides, fewer than 2^29 pixels -- ``separate_stains``'
+    planes, or a tile as ``tile.permute(2, 0, 1)``.  step: the grid step S in pixels, 4..256 (a region has about S^2 pixels);
+    compactness m: 0..1024, the weight of distance against colour (0: colour alone); n_iter: 1..64 rounds; within (bool / integer
+    [H, W], same device): only its non-zero pixels are clustered.  TypeError for another dtype, ValueError for everything else, before
+    any launch.  Returns (labels int32 [H, W], n): regions 1 .. n, each 4-connected, numbered by the raster order of their first
+    pixels; 0 exactly where ``within`` is zero.  With ``return_centres`` also (centres int32 [K, 2 + C], count int32 [K]) of the
+    clustering, before connectivity is enforced.  A pure function of its inputs, bit for bit from call to call.
+
+    The clustering leaves labels that need not be connected.  The rule that connects them is order-free (skimage's depends on the
+    scan order):
+      (a) pieces, P, sizes = label_instances(clustered, connectivity=1, return_sizes=True).
+      (b) A piece is small iff sizes < min_size (default max(1, S * S // 4)); the other pieces are settled, each a group of its own.
+      (c) pairs, count = region_adjacency(pieces, 1).
+      (d) In round r every unsettled piece with a neighbour settled before round r joins the group of the settled neighbour with the
+          largest count, of equal counts the smallest piece number, and is settled from then on; until a round settles nothing.
+      (e) Pixels that never settled -- a component of ``within`` made of small pieces only -- become one region per 4-connected blob.
+      (f) Groups and blobs are numbered in the raster order of their first pixels; one launch writes the image.
+
+    Host syncs: the one of label_instances, the two of region_adjacency, one per batch of merge rounds (4 rounds, then 8, ...: one
+    read for an ordinary tile), one that brings "did every piece settle" and n, and only when rule (e) applies the one of a second
+    label_instances and a second read of n.  None for an empty image."""
+    min_size = _check_superpixel_args(planes, step, compactness, n_iter, min_size, within)
+    C, H, W = planes.shape
+    dev = planes.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    if H * W == 0:
+        out = (torch.zeros(H, W, **i32), 0)
+        return out + ((torch.zeros(0, 2 + C, **i32), torch.zeros(0, **i32)),) if return_centres else out
+    with torch.cuda.device(dev):
+        k = kernels.get()
+        clustered, centres, count = k.slic_iterate(planes, int(step), int(compactness), int(n_iter), within)
+        pieces, P, sizes = label_instances(clustered, 1, return_sizes=True)
+        if P == 0:
+            final, n = pieces, 0
+        else:
+            pairs, contacts = region_adjacency(pieces, 1)
+            group, _ = k.slic_merge(sizes, pairs, contacts, min_size)
+            table, n_t = _superpixel_numbers(group, None)
+            left, n = torch.stack([(group[1:] == 0).sum(), n_t]).tolist()        # host sync: pieces that never settled; n
+            if left:
+                unsettled = (group[pieces.to(torch.int64)] == 0) & (pieces != 0)
+                blobs, _ = label_instances(unsettled, 1)
+                piece_blob = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+                piece_blob[pieces.reshape(-1).to(torch.int64)] = blobs.reshape(-1).to(torch.int64)      # one value per piece
+                table, n_t = _superpixel_numbers(group, piece_blob)
+                n = int(n_t.item())                                              # host sync: n with the leftover blobs
+            final = k.slic_relabel(pieces, table)
+    return (final, n, (centres, count)) if return_centres else (final, n)
+
+
+def _check_superpixel_labels(fn, labels, n):
+    _check_labels32(fn, 'labels', labels)
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or not 0 <= n < INT32_MAX:
+        raise ValueError('%s: n must be an integer in 0..2^31 - 2, got %r' % (fn, n))
+    return int(n)
+
+
+def superpixel_graph(labels, n, loop=True, return_attr=False):
+    """The tissue graph of a superpixel image: node i is label i + 1, and two nodes are joined iff their regions share a border
+    (``region_adjacency(labels, 1)``).  labels: ``superpixels``' int32 [H, W] (0 = outside), n: its region count.  Returns edge_index
+    int64 [2, E] in ``radius_knn``'s convention -- rows are centres in ascending order, then columns in ascending order; both
+    directions of every pair, and (i, i) for every node iff ``loop`` -- and with ``return_attr`` also border int32 [E], the pixel pairs
+    along which the two regions touch (0 on loops).  It goes into ``graph_item(features, centroids, y, edge_index=...)``.  A label
+    above n is a ValueError.
+
+    Host syncs: the two of region_adjacency and one that checks the label range."""
+    n = _check_superpixel_labels('superpixel_graph', labels, n)
+    dev = labels.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    pairs, border = region_adjacency(labels, 1)
+    if pairs.shape[0]:
+        lo, hi = torch.stack([pairs.min(), pairs.max()]).tolist()      # host sync: the label range
+        if lo < 1 or hi > n:
+            raise ValueError('superpixel_graph: labels outside 1..%d' % n)
+    ends = pairs.to(torch.int64) - 1
+    rows, cols = torch.cat([ends[:, 0], ends[:, 1]]), torch.cat([ends[:, 1], ends[:, 0]])
+    border = torch.cat([border, border])
+    if loop:
+        nodes = torch.arange(n, **i64)
+        rows, cols = torch.cat([rows, nodes]), torch.cat([cols, nodes])
+        border = torch.cat([border, torch.zeros(n, dtype=torch.int32, device=dev)])
+    order = torch.argsort(rows * max(n, 1) + cols)      # (row, col) pairs are distinct
+    edge_index = torch.stack([rows[order], cols[order]])
+    return (edge_index, border[order]) if return_attr else edge_index
+
+
+def superpixel_features(labels, planes, n):
+    """The node table of a tissue graph: (features float32 [n, 3 + 2 C], centroids float32 [n, 2]) of regions 1 .. n of a superpixel
+    image over uint8 planes [C, H, W] -- row i is label i + 1.  Columns (``SUPERPIXEL_FEATURE_NAMES``, the first 3 + 2 C): the area
+    in pixels, the centroid (row, column), then the mean and the population standard deviation of every plane.  From the integer
+    tables of ``region_geometry`` and ``region_statistics`` through ``region_mean_std``, computed in float64 and rounded once; a label
+    without a pixel gives a row of zeros.
+
+    Host syncs: the refused-pixel reads of region_geometry and of region_statistics, one per plane (a label outside 0..n raises)."""
+    n = _check_superpixel_labels('superpixel_features', labels, n)
+    if not torch.is_tensor(planes) or planes.dtype != torch.uint8:
+        raise TypeError('superpixel_features: planes must be a uint8 tensor [C, H, W]')
+    if planes.dim() != 3 or not 1 <= planes.shape[0] <= SLIC_MAX_PLANES or tuple(planes.shape[1:]) != tuple(labels.shape):
+        raise ValueError('superpixel_features: planes must be [C, H, W] with 1 <= C <= %d and the shape of labels (got %s and %s)'
+                         % (SLIC_MAX_PLANES, tuple(planes.shape), tuple(labels.shape)))
+    geometry = region_geometry(labels, max_label=n)
+    area = geometry.count[1:].to(torch.float64)
+    some = area > 0
+    den = torch.where(some, area, 1.0)
+    cy, cx = geometry.sy[1:].to(torch.float64) / den, geometry.sx[1:].to(torch.float64) / den
+    columns = [area, cy, cx]
+    for c in range(planes.shape[0]):
+        mean, std = region_mean_std(region_statistics(labels, planes[c], max_label=n))
+        columns += [mean[1:], std[1:]]
+    features = torch.stack([col.to(torch.float32) for col in columns], 1)
+    return features, torch.stack([cy, cx], 1).to(torch.float32)
+
+
+def regions_at(labels, points):
+    """The label under each point: int32 [N] for float (row, column) coordinates [N, 2] on the labels' device, in the pixel-centre
+    convention of ``scale_points`` -- pixel (i, j) has its centre at (i, j) and covers [i - 1/2, i + 1/2) x [j - 1/2, j + 1/2), so a
+    point falls into pixel floor(c + 1/2) per axis, computed in float64.  0 for a point outside the image (and where the label is 0).
+    ``regions_at(superpixel_labels, centroids)`` assigns every nucleus to the tissue node under it.
+
+    Host syncs: none."""
+    if not torch.is_tensor(labels) or labels.dim() != 2 or labels.is_floating_point():
+        raise TypeError('regions_at takes an integer label image [H, W] (labels)')
+    if not torch.is_tensor(points) or not points.is_floating_point():
+        raise TypeError('regions_at takes a float tensor [N, 2] (points)')
+    if points.dim() != 2 or points.shape[1] != 2 or points.device != labels.device:
+        raise ValueError('regions_at: points must be [N, 2] on the device of labels (got %s on %s)' % (tuple(points.shape), points.device))
+    H, W = labels.shape
+    out = torch.zeros(points.shape[0], dtype=torch.int32, device=labels.device)
+    if H * W == 0 or points.shape[0] == 0:
+        return out
+    at = torch.floor(points.to(torch.float64) + 0.5)
+    inside = (at[:, 0] >= 0) & (at[:, 0] < H) & (at[:, 1] >= 0) & (at[:, 1] < W)      # NaN compares false: outside
+    y = torch.where(inside, at[:, 0], 0.0).to(torch.int64)
+    x = torch.where(inside, at[:, 1], 0.0).to(torch.int64)
+    return torch.where(inside, labels[y, x].to(torch.int32), out)
 
 
 def graph_item(features, centroids, y, edge_index=None):

@@ -93,8 +93,11 @@ typedef void* cgc_stream_t; /* hipStream_t */
  *  28: region outlines (per label value: the ordered boundary of its pixel squares as closed loops of lattice corners, by pointer
  *      doubling over the cracks): cgc_region_outline_rounds, cgc_region_outlines_ws_bytes, cgc_region_outline_count,
  *      cgc_region_outline_cracks, cgc_region_outline_loops, cgc_region_outline_keys, cgc_region_outline_tables,
- *      cgc_region_outline_scatter, cgc_region_outline_compact */
-#define CGC_ABI_VERSION 28
+ *      cgc_region_outline_scatter, cgc_region_outline_compact
+ *  29: superpixels (SLIC on integer planes: a gather assignment and an integer centre update per round; the order-free merge of
+ *      small connected pieces; one relabel): cgc_slic_max_step, cgc_slic_tile_side, cgc_slic_table_side, cgc_slic_ws_bytes,
+ *      cgc_slic_iterate, cgc_slic_merge_begin, cgc_slic_merge_rounds, cgc_slic_relabel */
+#define CGC_ABI_VERSION 29
 int cgc_abi_version(void);
 
 /* ---- A1: graph structure.  Replaces to_dense_adj (model/utils.py:3-36, called at model/network.py:241).
@@ -661,6 +664,38 @@ int cgc_region_outline_scatter(int64_t n_cracks, int64_t n_loops, int W, const i
                                uint8_t* keep_or_null, cgc_stream_t stream);
 int cgc_region_outline_compact(int64_t n_cracks, int64_t n_vertices, const uint8_t* keep, const int* place, const int* slots,
                                int* vertices, cgc_stream_t stream);
+
+/* ---- F23 (behind F11 / F12, in front of F13 and F17 .. F19; csrc/slic.hip): superpixels, the tissue regions between the nuclei.  The
+ * contract item by item: cgc-net_amd/kernels.py KernelSpec.slic_iterate and KernelSpec.slic_merge.
+ *   cgc_slic_iterate: planes uint8 [C, H, W] contiguous, 1 <= C <= 4, H * W < 2^29; 4 <= step <= cgc_slic_max_step() = 256; 0 <=
+ *     compactness <= 1024; 1 <= n_iter <= 64; within_or_null as F17 (only "is zero" is read).  ny = max(1, (2 H + S) / (2 S)), nx
+ *     likewise, K = ny nx.  Pixel (y, x) has home cell (y ny / H, x nx / W); centre k = i nx + j starts at y = (2 i + 1) H / (2 ny), x =
+ *     (2 j + 1) W / (2 nx) with the colour of that pixel.  A round: every counted pixel takes, among the centres of the up to 9 cells
+ *     around its home cell, the one with the smallest D = S^2 sum_c (p_c - c_c)^2 + m^2 ((y - c_y)^2 + (x - c_x)^2) (64 bits), of equal
+ *     D the smallest k; then every centre with n > 0 pixels moves to (2 sum + n) / (2 n) per coordinate and colour.  n_iter rounds of two
+ *     launches (assign + accumulate, finalize) behind one init launch; no host read.  labels int32 [H, W] = k + 1 of the last
+ *     assignment, 0 where within is zero; centres int32 [K, 2 + C] = (y, x, colours) after the last update; count int32 [K] = the
+ *     pixels of the last assignment.  ws = cgc_slic_ws_bytes(C, H, W, step) bytes (0 for arguments that are refused).  The assign
+ *     launch works on tiles of cgc_slic_tile_side() pixels a side and folds the sums of the cgc_slic_table_side()^2 cells around a
+ *     tile's first pixel in LDS; sums of other cells go to global memory directly, with the same integer atomics.
+ *   cgc_slic_merge_begin: pieces 1 .. n_pieces of sizes int32 [n_pieces]; group int32 [n_pieces + 1] = p where sizes[p - 1] >= min_size
+ *     (settled), 0 elsewhere (group[0] = 0); best uint64 [n_pieces + 1] = 0.
+ *   cgc_slic_merge_rounds: `rounds` >= 1 rounds over pairs int32 [n_pairs, 2] (a < b, piece numbers) and count int32 [n_pairs] (F13's
+ *     outputs): an unsettled piece p with settled neighbours takes group[q] of the neighbour q with the largest count << 32 | ~q.
+ *     Two launches per round.  *changed = the pieces the LAST round settled.  Pairs with an end outside 1 .. n_pieces are skipped.
+ *   cgc_slic_relabel: out[i] = table[pieces[i]] for pieces[i] in 1 .. n_pieces, else 0; table int32 [n_pieces + 1].
+ * Integer work only, bit-identical from call to call.  An argument outside its range or a null pointer where one is needed:
+ * CGC_EINVAL, nothing launched.  H * W = 0, n_pieces = 0: nothing to do, 0. */
+int cgc_slic_max_step(void);
+int cgc_slic_tile_side(void);
+int cgc_slic_table_side(void);
+int64_t cgc_slic_ws_bytes(int C, int H, int W, int step);
+int cgc_slic_iterate(const uint8_t* planes, int C, int H, int W, int step, int compactness, int n_iter, const void* within_or_null,
+                     int within_bytes, void* ws, int* labels, int* centres, int* count, cgc_stream_t stream);
+int cgc_slic_merge_begin(const int* sizes, int n_pieces, int min_size, int* group, uint64_t* best, cgc_stream_t stream);
+int cgc_slic_merge_rounds(const int* pairs, const int* count, int64_t n_pairs, int n_pieces, int rounds, int* group, uint64_t* best,
+                          int* changed, cgc_stream_t stream);
+int cgc_slic_relabel(const int* pieces, int64_t n_pixels, int n_pieces, const int* table, int* out, cgc_stream_t stream);
 
 /* ---- A6 (level 1): _re_norm_adj on the CSR (model/network.py:183-191): val[k] = p on the diagonal,
  * (1/(c+1e-15))*(1-p) elsewhere, c = off-diagonal entries of the row.  The CSR must hold its diagonal. */
